@@ -1,6 +1,12 @@
 """Benchmark of the DLRM embedding + interaction hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step, ...).  --full adds every secondary measurement to the line: the sustained rate, the
+drop-in operator chain, the per-stage timings and roofline (with the GPU's measured ceiling) and
+the CPU baseline (--sustain / --chain / --stage-timing / --ceiling / --no-cpu-baseline select
+among them).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 
 One step = one training pass of the hot path over one batch (src/train/train.jl:215-227 minus
 the dense MLPs): maplookup -> DotInteraction -> dot_back -> update!(Descent) of the tables,
@@ -56,6 +62,14 @@ def parse():
                          "all-to-alls inside (falls back to 'segments' where the capture is refused, e.g. gloo); "
                          "'segments' = the compute between eager collectives")
     ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the sustained rate, the drop-in "
+                         "operator chain, the per-stage timings + roofline + measured ceiling and the CPU baseline "
+                         "(each still subject to its own option below); off: those fields of the line are null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed as float32 DIR/<name>.npy: "
+                         "out and dx (rank 0's) and table_rows, the rows of this rank's tables that step's "
+                         "batch updated (a fixed seeded sample of its positions where they exceed the size cap)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--mode", choices=["auto", "graph", "eager"], default="auto",
@@ -347,6 +361,30 @@ def load_prof(workload):
     return prof
 
 
+DUMP_CAP = 60_000_000  # bytes of --dump-outputs files in all (under 64 MB)
+
+
+def dump_outputs(path, out, dx, tables, last_idx, seed=51234):
+    """--dump-outputs: what the last timed step handed its caller, as float32 <path>/<name>.npy:
+    out [B][width] and dx [B][d], and table_rows [T][m][D]: the rows of each table at the positions
+    of that step's index batch (last_idx [T][N]), i.e. the rows it updated -- all N positions, or,
+    where those exceed DUMP_CAP, m of them drawn once by a generator seeded with `seed` (the same
+    positions for every table and every run)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {"out": out.detach().float().cpu().numpy(), "dx": dx.detach().float().cpu().numpy()}
+    T = len(tables)
+    if T:
+        N, D = int(last_idx.shape[1]), int(tables[0].shape[1])
+        left = DUMP_CAP - sum(v.nbytes for v in arrs.values())
+        m = max(1, min(N, left // (T * D * 4)))
+        pos = np.arange(N) if m == N else np.sort(np.random.default_rng(seed).choice(N, size=m, replace=False))
+        pos = torch.from_numpy(pos).to(last_idx.device)
+        arrs["table_rows"] = np.stack([tables[t][last_idx[t].index_select(0, pos).long()].float().cpu().numpy()
+                                       for t in range(T)])
+    for name, v in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -543,6 +581,15 @@ def main():
             print(json.dumps({"probe_region_ms_per_step": {n: v for n, v in res.items()}}))
         return
     ms = timed(a.steps)
+    if a.dump_outputs and rank == 0:
+        # before anything below steps the tables further: the state the K-th timed step left
+        last = (a.steps - 1) % nb
+        if world == 1:
+            dump_outputs(a.dump_outputs, engine.out, engine.dx, tables, packs[last].data.flatten(1))
+        else:
+            mine = [t.data for t in (getattr(engine.ops, "ts", None) or [])]
+            dump_outputs(a.dump_outputs, engine.out, engine.dx, mine,
+                         engine.bench_packs[last].data.flatten(1))
     dist_info = None
     if world > 1:
         # what the job ran on, as the collectives saw it: the rank count of an all-reduce over the
@@ -565,7 +612,7 @@ def main():
     # sustained: >= a.sustain seconds of back-to-back steps (whole cycles over the nb batches), so a
     # short K does not hide clock ramp or cache effects; reported beside value, not instead of it
     sustained = None
-    if a.sustain > 0:
+    if a.full and a.sustain > 0:
         per = chunk // nb  # (whole graphs: every piece of the run was captured)
         cyc = max(1, int(np.ceil(a.sustain * 1e3 / (ms * nb))))
         cyc = per * int(np.ceil(cyc / per))
@@ -582,7 +629,7 @@ def main():
     # maplookup -> rrule(DotInteraction) -> pullback -> maplookup_pullback -> update!) on HipTables,
     # i.e. the fused step kernels reached through the reference's operator API (dlrm.jl_amd/lazy.py)
     chain = None
-    if world == 1 and L == 1 and a.chain and graphs is not None:
+    if a.full and world == 1 and L == 1 and a.chain and graphs is not None:
         ht = pkg.HipTables(ts, lr=a.lr, index_base=0)
         dot = pkg.DotInteraction()
         strat = pkg.PreallocationStrategy(D)
@@ -637,7 +684,7 @@ def main():
     # ---- per-kernel timing (HIP events on the launch stream) + roofline, rank 0
     roofline = None
     stages = None
-    if rank == 0 and world == 1 and a.stage_timing:
+    if a.full and rank == 0 and world == 1 and a.stage_timing:
         uniq = chunks = 0
         for k in range(nb):
             engine.build_indexer(packs[k])
@@ -824,7 +871,7 @@ def main():
                 roofline["mfma"] = mf
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and w["dtype"] == "f32":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and w["dtype"] == "f32":
         # every CPU this process may run on, capped by the OMP_NUM_THREADS share the host grants a
         # one-GPU job (16 on the GPU box; its machine has more: host_cpus in the line)
         allowed = len(os.sched_getaffinity(0))
