@@ -45,6 +45,15 @@ struct dlrm_tables {
     bool aligned16 = true;
 };
 
+// Sparse Adagrad state of one table set: the caller's per-table fp32 state pointers, uploaded once
+struct dlrm_adagrad {
+    int T = 0, D = 0;
+    bool rowwise = false;     // one word per table row instead of one row
+    bool aligned16 = true;    // every state pointer is 16-B aligned
+    float** d_state = nullptr;
+    std::vector<float*> h_state;
+};
+
 struct dlrm_indexer {
     dlrm_ctx* ctx = nullptr;
     int T = 0;
@@ -982,6 +991,84 @@ int dlrm_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, unsigned f
                          index_base, batch * lookups};
     return launch_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, tb->T, tb->D, tb->dtype, lookups,
                             (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr, sa);
+}
+
+// ------------------------------------------------------------------------- sparse Adagrad
+int dlrm_adagrad_create(dlrm_ctx* ctx, const dlrm_tables* tb, int rowwise, float* const* state, dlrm_adagrad** out) {
+    CHECK_ARG(ctx && tb && out, "dlrm_adagrad_create: null argument");
+    *out = nullptr;
+    CHECK_ARG(tb->T == 0 || state, "dlrm_adagrad_create: null state");
+    for (int t = 0; t < tb->T; ++t)
+        CHECK_ARG(state[t] || tb->h_desc[t].nrows == 0, "dlrm_adagrad_create: table %d has no state", t);
+    dlrm_adagrad* op = new (std::nothrow) dlrm_adagrad();
+    if (!op) return DLRM_E_NOMEM;
+    op->T = tb->T;
+    op->D = tb->D;
+    op->rowwise = rowwise != 0;
+    op->h_state.assign(state, state + tb->T);
+    // (rows of D floats from a 16-B aligned base: aligned when D % 4 == 0, which the vector kernels need anyway)
+    for (int t = 0; t < tb->T; ++t)
+        if ((uintptr_t)state[t] % 16) op->aligned16 = false;
+    int rc = hip_set(ctx);
+    if (rc == DLRM_OK && tb->T > 0) {
+        rc = ctx_hip(ctx, hipMalloc((void**)&op->d_state, sizeof(float*) * tb->T), "hipMalloc(adagrad state)");
+        if (rc == DLRM_OK)
+            rc = ctx_hip(ctx, hipMemcpy(op->d_state, op->h_state.data(), sizeof(float*) * tb->T, hipMemcpyHostToDevice),
+                         "hipMemcpy(adagrad state)");
+    }
+    if (rc != DLRM_OK) {
+        if (op->d_state) (void)hipFree(op->d_state);
+        delete op;
+        return rc;
+    }
+    *out = op;
+    return DLRM_OK;
+}
+
+int dlrm_adagrad_destroy(dlrm_adagrad* op) {
+    if (!op) return DLRM_OK;
+    if (op->d_state) (void)hipFree(op->d_state);
+    delete op;
+    return DLRM_OK;
+}
+
+int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, unsigned flags,
+                        const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
+                        const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset, float lr, float eps) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_adagrad_update: null ctx/tables/optimizer/indexer");
+    int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, lookups);
+    if (rc) return rc;
+    CHECK_ARG(op->T == tb->T && op->D == tb->D, "dlrm_adagrad_update: the optimizer state was created for %d tables of dim %d",
+              op->T, op->D);
+    CHECK_ARG(grad_dtype == DLRM_F32 || grad_dtype == DLRM_BF16, "dlrm_adagrad_update: grad dtype %d", grad_dtype);
+    CHECK_ARG(grad_offset >= 0 && grad_ld >= grad_offset + (int64_t)tb->T * tb->D, "dlrm_adagrad_update: grad_ld too small");
+    CHECK_ARG(batch == 0 || tb->T == 0 || grad, "dlrm_adagrad_update: null grad");
+    if (flags & DLRM_UPDATE_ATOMIC)  // an atomic add never holds the row's whole sum, which the rule squares
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_adagrad_update: no atomic mode (the rule needs each row's complete sum)");
+    if (flags & DLRM_UPDATE_PREBUILT) {
+        if (!built_from(ix, indices, itype, table_stride, index_base, batch, lookups))
+            return ctx_fail(ctx, DLRM_E_STATE, "dlrm_adagrad_update: indexer was not built from these indices");
+        // a split backward stepped this build's once-hit rows with Descent and left their dt rows unwritten
+        if (ix->singles_done)
+            return ctx_fail(ctx, DLRM_E_STATE,
+                            "dlrm_adagrad_update: a split backward (dlrm_step_bwd) already stepped this build's "
+                            "once-hit rows with Descent");
+    } else {
+        rc = dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, lookups);
+        if (rc) return rc;
+    }
+    rc = ensure_partials(ctx, ix, tb->D);
+    if (rc) return rc;
+    // (a split indexer is taken whole: its once-hit positions as singles items)
+    const SinglesArgs sa{ix->split ? ix->dev.single : nullptr, indices, itype, table_stride, index_base,
+                         batch * lookups};
+    if (op->rowwise)
+        return launch_rowwise_adagrad_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, op->d_state, tb->T, tb->D, tb->dtype,
+                                            lookups, (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset,
+                                            lr, eps, sa);
+    return launch_adagrad_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_state, tb->T, tb->D,
+                                tb->dtype, lookups, (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr,
+                                eps, sa);
 }
 
 // ----------------------------------------------------------------------- training step

@@ -1,0 +1,19 @@
+// adagrad_rowwise.hip — the row-wise Adagrad embedding update on gfx950.
+//
+// The apply launch of update.hip (apply_kernel.hpp) with apply.hpp's RowwiseAdagrad rule at its
+// write sites: one fp32 word per table row,
+//   m[r] += (1/D) sum_c G[c]^2;  w[r][c] -= lr G[c] / (sqrt(m[r]) + eps)
+// The sum over c has a fixed order per site (apply.hpp), so the result is bitwise reproducible.
+#include "apply_kernel.hpp"
+
+namespace dlrm {
+
+int launch_rowwise_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16,
+                                 float* const* state, int T_, int D, int tdtype, int L, int64_t N, const void* grad,
+                                 int gdtype, int64_t grad_ld, int64_t grad_offset, float lr, float eps,
+                                 const SinglesArgs& sa) {
+    return launch_apply_rule(ctx, ix, tabs, aligned16, T_, D, tdtype, L, N, grad, gdtype, grad_ld, grad_offset,
+                             RowwiseAdagrad{lr, eps, state}, sa, nullptr);
+}
+
+}  // namespace dlrm

@@ -44,6 +44,15 @@ struct ApplyGeom {
     // once-hit positions per lane group (a grad and a table row in flight for each)
     static constexpr int SPPG = VPL * NE >= 16 ? 2 : (VPL * NE >= 8 ? 4 : 8);
 };
+// ... of a rule with state (kState != 0), a state row or word being in flight beside each table
+// row: half as many, a quarter for fp32 gradient rows (the row-wise rule: of one vector per lane).
+// The MODE 1 kernels sit at the 168-register limit of three workgroups per CU; at SPPG the Adagrad
+// instantiations spill up to 1300 registers to scratch, with these counts none does.
+template <typename G, int KSTATE>
+constexpr int singles_ppg() {
+    constexpr int DIV = G::NE == 4 && (KSTATE == 1 || G::VPL == 1) ? 4 : 2;
+    return KSTATE == 0 ? G::SPPG : (G::SPPG >= DIV ? G::SPPG / DIV : 1);
+}
 
 // Cross-workgroup hand-off of slice partials (cdna_hip_programming.md Guideline 16, R1/R2):
 // payload stored write-through (agent-scope atomic stores = sc1), the storing wave drains
@@ -80,11 +89,71 @@ __device__ __forceinline__ void add_vec(float* acc, const typename Vec<GT>::type
     for (int e = 0; e < Vec<GT>::N; ++e) acc[e] += f[e];
 }
 
+// ---- update rules: what a touched row's write does with its complete gradient sum G (fp32).
+//   Descent         w = fmaf(-lr, G, w)
+//   Adagrad         A += G^2 (element-wise, fp32 [nrows][D]);   w -= lr G / (sqrt(A) + eps)
+//   RowwiseAdagrad  m += (1/D) sum_c G[c]^2 (fp32 [nrows]);      w -= lr G / (sqrt(m) + eps)
+// kState: 0 none, 1 a state row per table row, 2 a state word per table row.  The state is loaded
+// where the table row is (beside the grad rows: these items are bound by dependent round trips)
+// and written once, with the row.  The row-wise sum of squares has a fixed order per site: a lane's
+// elements in element order, then an xor butterfly over the lanes holding the row (every level one
+// commutative add, so every lane ends with the same bits), then (slices of D > 256) the waves in
+// wave order.
+struct Descent {
+    float lr;
+    static constexpr int kState = 0;
+    __device__ __forceinline__ float* base(int) const { return nullptr; }
+};
+struct Adagrad {
+    float lr, eps;
+    float* const* state;  // [T] device pointers, fp32 [nrows][D]
+    static constexpr int kState = 1;
+    __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
+};
+struct RowwiseAdagrad {
+    float lr, eps;
+    float* const* state;  // [T] device pointers, fp32 [nrows]
+    static constexpr int kState = 2;
+    __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
+};
+
+// The element-wise rule's sqrt and reciprocal: the hardware's (v_sqrt_f32, v_rcp_f32: 1 ulp each)
+// instead of the correctly rounded expansions (~25 instructions and 6 live registers per element,
+// times up to 32 elements in flight per lane in a singles item).  Their operands are normal
+// numbers (A >= its initial eps > 0); the step stays within 4 ulp of the exact quotient.
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
+__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+#else  // host pass of the device code: never executed
+__device__ __forceinline__ float fast_sqrt(float x) { return __builtin_sqrtf(x); }
+__device__ __forceinline__ float fast_rcp(float x) { return 1.0f / x; }
+#endif
+
+// N elements of a row: a (the Adagrad accumulators) and w updated from the sums g
+template <int N>
+__device__ __forceinline__ void adagrad_step(float lr, float eps, const float* g, float* a, float* w) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+        a[e] = __builtin_fmaf(g[e], g[e], a[e]);
+        w[e] = __builtin_fmaf(-lr, g[e] * fast_rcp(fast_sqrt(a[e]) + eps), w[e]);
+    }
+}
+template <int N>
+__device__ __forceinline__ float sum_squares(const float* g, float ss) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) ss = __builtin_fmaf(g[e], g[e], ss);
+    return ss;
+}
+// the row-wise accumulator after a row whose squares sum to ss, and the row's step size
+__device__ __forceinline__ float rowwise_m(float m, float ss, int D) { return m + ss / (float)D; }
+__device__ __forceinline__ float rowwise_scale(float lr, float eps, float m) { return lr / (__builtin_sqrtf(m) + eps); }
+
 // ---- a chunk, by one lane group (lane v of LPR; gl0 = the group's first lane in the wave)
-template <typename TT, typename GT, int VPR>
+template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_chunk(const int32_t* __restrict__ perm, const int4& a, const int4& b,
-                                          TT* __restrict__ table, const GT* __restrict__ gbase, int64_t grad_ld,
-                                          const FastDiv& L, float lr, int v, int gl0) {
+                                          TT* __restrict__ table, float* __restrict__ st,
+                                          const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L,
+                                          const R& rule, int v, int gl0) {
     typedef ApplyGeom<GT, VPR> G;
     constexpr int NE = G::NE, D = G::D, LPR = G::LPR;
     constexpr int KX = (kChunk - kChunkInline + LPR - 1) / LPR;  // perm loads per lane (long chunks)
@@ -93,6 +162,13 @@ __device__ __forceinline__ void run_chunk(const int32_t* __restrict__ perm, cons
     float tv[G::VPL][NE];
 #pragma unroll
     for (int j = 0; j < G::VPL; ++j) load_row<TT, NE>(row, (v + j * 64) * NE, tv[j]);  // beside the grad rows
+    float sv[R::kState == 1 ? G::VPL : 1][NE];  // Adagrad: the state row
+    float m = 0.0f;                             // row-wise: the state word
+    if constexpr (R::kState == 1) {
+#pragma unroll
+        for (int j = 0; j < G::VPL; ++j) load_row<float, NE>(st + (int64_t)(uint32_t)a.z * D, (v + j * 64) * NE, sv[j]);
+    }
+    if constexpr (R::kState == 2) m = ldg<float>(st + (uint32_t)a.z);
     const int inl[kChunkInline] = {a.w, b.x, b.y, b.z, b.w};
     int px[KX];  // positions kChunkInline.. : position kChunkInline + k*LPR + lane
     if (len > kChunkInline) {
@@ -128,6 +204,26 @@ __device__ __forceinline__ void run_chunk(const int32_t* __restrict__ perm, cons
 #pragma unroll
                 for (int j = 0; j < G::VPL; ++j) add_vec<GT>(acc[j], gv[uu][j]);
     }
+    if constexpr (R::kState == 1) {
+#pragma unroll
+        for (int j = 0; j < G::VPL; ++j) {
+            adagrad_step<NE>(rule.lr, rule.eps, acc[j], sv[j], tv[j]);
+            store_row<float, NE>(st + (int64_t)(uint32_t)a.z * D, (v + j * 64) * NE, sv[j]);
+            store_row<TT, NE>(row, (v + j * 64) * NE, tv[j]);
+        }
+        return;
+    }
+    float lr = rule.lr;
+    if constexpr (R::kState == 2) {
+        float ss = 0.0f;
+#pragma unroll
+        for (int j = 0; j < G::VPL; ++j) ss = sum_squares<NE>(acc[j], ss);
+#pragma unroll
+        for (int o = 1; o < LPR; o <<= 1) ss += __shfl_xor(ss, o, 64);
+        m = rowwise_m(m, ss, D);
+        lr = rowwise_scale(rule.lr, rule.eps, m);
+        if (v == 0) stg<float>(st + (uint32_t)a.z, m);
+    }
 #pragma unroll
     for (int j = 0; j < G::VPL; ++j) {
 #pragma unroll
@@ -147,12 +243,13 @@ struct SinglesArgs {
     int base;
     int N;                  // positions per table
 };
-template <typename TT, typename GT, int VPR>
-__device__ __forceinline__ void run_singles(const SinglesArgs& sa, int64_t cap, TT* __restrict__ table, int64_t nrows,
-                                            int t, int p0, const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L,
-                                            float lr, int v, int gl0) {
+template <typename TT, typename GT, int VPR, typename R>
+__device__ __forceinline__ void run_singles(const SinglesArgs& sa, int64_t cap, TT* __restrict__ table,
+                                            float* __restrict__ st, int64_t nrows, int t, int p0,
+                                            const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L,
+                                            const R& rule, int v, int gl0) {
     typedef ApplyGeom<GT, VPR> G;
-    constexpr int NE = G::NE, D = G::D, LPR = G::LPR, PPG = G::SPPG;
+    constexpr int NE = G::NE, D = G::D, LPR = G::LPR, PPG = singles_ppg<G, R::kState>();
     constexpr int KX = (PPG + LPR - 1) / LPR;
     uint32_t pr[KX];  // the row of position p0 + k*LPR + v, ~0u when it is not a single
 #pragma unroll
@@ -166,6 +263,8 @@ __device__ __forceinline__ void run_singles(const SinglesArgs& sa, int64_t cap, 
     uint32_t ru[PPG];
     typename Vec<GT>::type gv[PPG][G::VPL];
     float tv[PPG][G::VPL][NE];
+    float sv[R::kState == 1 ? PPG : 1][R::kState == 1 ? G::VPL : 1][NE];  // Adagrad: the state rows
+    float m[PPG];                                                         // row-wise: the state words
 #pragma unroll
     for (int u = 0; u < PPG; ++u) {
         ru[u] = (uint32_t)__shfl((int)pr[u / LPR], gl0 + u % LPR, 64);
@@ -174,9 +273,48 @@ __device__ __forceinline__ void run_singles(const SinglesArgs& sa, int64_t cap, 
             for (int j = 0; j < G::VPL; ++j) {
                 gv[u][j] = grad_vec<GT>(gbase, grad_ld, L, p0 + u, v + j * 64);
                 load_row<TT, NE>(table + (int64_t)ru[u] * D, (v + j * 64) * NE, tv[u][j]);
+                if constexpr (R::kState == 1) load_row<float, NE>(st + (int64_t)ru[u] * D, (v + j * 64) * NE, sv[u][j]);
             }
+            if constexpr (R::kState == 2) m[u] = ldg<float>(st + ru[u]);
         }
     }
+    if constexpr (R::kState != 0) {
+#pragma unroll
+        for (int u = 0; u < PPG; ++u)
+            if (ru[u] != ~0u) {  // (uniform over the lane group)
+                float g[G::VPL][NE];
+#pragma unroll
+                for (int j = 0; j < G::VPL; ++j) {
+                    Vec<GT>::to_f32(gv[u][j], g[j]);
+#pragma unroll
+                    for (int e = 0; e < NE; ++e) g[j][e] = 0.0f + g[j][e];
+                }
+                float lr = rule.lr;
+                if constexpr (R::kState == 2) {
+                    float ss = 0.0f;
+#pragma unroll
+                    for (int j = 0; j < G::VPL; ++j) ss = sum_squares<NE>(g[j], ss);
+#pragma unroll
+                    for (int o = 1; o < LPR; o <<= 1) ss += __shfl_xor(ss, o, 64);
+                    m[u] = rowwise_m(m[u], ss, D);
+                    lr = rowwise_scale(rule.lr, rule.eps, m[u]);
+                    if (v == 0) stg<float>(st + ru[u], m[u]);
+                }
+#pragma unroll
+                for (int j = 0; j < G::VPL; ++j) {
+                    if constexpr (R::kState == 1) {
+                        adagrad_step<NE>(rule.lr, rule.eps, g[j], sv[u][j], tv[u][j]);
+                        store_row<float, NE>(st + (int64_t)ru[u] * D, (v + j * 64) * NE, sv[u][j]);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < NE; ++e) tv[u][j][e] = __builtin_fmaf(-lr, g[j][e], tv[u][j][e]);
+                    }
+                    store_row<TT, NE>(table + (int64_t)ru[u] * D, (v + j * 64) * NE, tv[u][j]);
+                }
+            }
+        return;
+    }
+    const float lr = rule.lr;
 #pragma unroll
     for (int u = 0; u < PPG; ++u)
         if (ru[u] != ~0u)
@@ -216,11 +354,53 @@ struct SliceLds {
 // len of them, `row` the table row, `ns` the slices of its segment, its partial row at
 // part_me, the segment's first at part_first (slot spacing pdim), `cnt` the segment's arrival
 // counter (zero at rest).
-template <typename TT, typename GT, int VPR>
-__device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int len, TT* __restrict__ row, int ns,
-                                           float* part_me, const float* part_first, int64_t pdim, int32_t* cnt_p,
-                                           const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L, float lr,
-                                           SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
+// The row's write by the first D/4 threads (G = the thread's four sums, rw its four weights, sw its
+// four accumulators or the row's word); every thread of the workgroup calls it.  wsum_read: other
+// waves may still be reading sm.wsum (the row-wise wave totals of D > 256 reuse it).
+template <typename TT, typename R, int D>
+__device__ __forceinline__ void slice_write(const R& rule, const f32x4& G, float* rw, float* sw, TT* __restrict__ row,
+                                            float* __restrict__ srow, SliceLds<D>& sm, bool wsum_read) {
+    const int tid = threadIdx.x;
+    const bool mine = tid < D / 4;
+    const float g[4] = {G[0], G[1], G[2], G[3]};
+    float lr = rule.lr;
+    if constexpr (R::kState == 1) {
+        if (mine) {
+            adagrad_step<4>(rule.lr, rule.eps, g, sw, rw);
+            store_row<float, 4>(srow, tid * 4, sw);
+            store_row<TT, 4>(row, tid * 4, rw);
+        }
+        return;
+    }
+    if constexpr (R::kState == 2) {
+        float ss = mine ? sum_squares<4>(g, 0.0f) : 0.0f;  // (lanes past the row add 0)
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) ss += __shfl_xor(ss, o, 64);
+        if constexpr (D / 4 > 64) {  // the wave totals, in wave order
+            if (wsum_read) __syncthreads();
+            float* wt = (float*)&sm.wsum[0][0];
+            if ((tid & 63) == 0) wt[tid >> 6] = ss;
+            __syncthreads();
+            ss = 0.0f;
+#pragma unroll
+            for (int ww = 0; ww < kApplyWaves; ++ww) ss += wt[ww];
+        }
+        const float m = rowwise_m(sw[0], ss, D);
+        lr = rowwise_scale(rule.lr, rule.eps, m);
+        if (tid == 0) stg<float>(srow, m);
+    }
+    if (mine) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rw[e] = __builtin_fmaf(-lr, g[e], rw[e]);
+        store_row<TT, 4>(row, tid * 4, rw);
+    }
+}
+
+template <typename TT, typename GT, int VPR, typename R>
+__device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int len, TT* __restrict__ row,
+                                           float* __restrict__ srow, int ns, float* part_me, const float* part_first,
+                                           int64_t pdim, int32_t* cnt_p, const GT* __restrict__ gbase, int64_t grad_ld,
+                                           const FastDiv& L, const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
     typedef ApplyGeom<GT, VPR> G;
     constexpr int NE = G::NE, D = G::D, LPR = G::LPR, NG = G::NG;
     constexpr int SPG = (kHotSlice + NG - 1) / NG;  // positions per lane group
@@ -229,6 +409,13 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
     // the table row, loaded now (needed only at the end; no other item writes it in this launch)
     float rw[4];
     if (tid < D / 4) load_row<TT, 4>(row, tid * 4, rw);
+    float sw[4] = {0.f, 0.f, 0.f, 0.f};  // the state, with the row (written by the segment's last slice only)
+    if constexpr (R::kState == 1) {
+        if (tid < D / 4) load_row<float, 4>(srow, tid * 4, sw);
+    }
+    if constexpr (R::kState == 2) {
+        if (tid < D / 4) sw[0] = ldg<float>(srow);
+    }
     // this group's consecutive share [g0, u1), in position order: lane v of the group loads
     // positions g0 + k LPR + v, and each row's position comes by a shuffle (no LDS staging and no
     // barrier before the grad rows)
@@ -285,10 +472,15 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
     }
     static_assert(D / 4 <= kApplyThreads, "a float4 of the row per thread");
     if (ns == 1) {
-        if (tid < D / 4) {
+        if constexpr (R::kState == 0) {
+            const float lr = rule.lr;
+            if (tid < D / 4) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) rw[e] = __builtin_fmaf(-lr, sum[e], rw[e]);
-            store_row<TT, 4>(row, tid * 4, rw);
+                for (int e = 0; e < 4; ++e) rw[e] = __builtin_fmaf(-lr, sum[e], rw[e]);
+                store_row<TT, 4>(row, tid * 4, rw);
+            }
+        } else {
+            slice_write<TT, R, D>(rule, sum, rw, sw, row, srow, sm, true);
         }
         __syncthreads();  // sm reused by this workgroup's next item
         return;
@@ -299,22 +491,41 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
     if (D / 4 > 64) __syncthreads();                   // (several storing waves)
     if (tid == 0) sm.last = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ns - 1;
     __syncthreads();
-    if (sm.last && tid < D / 4) {
-        float* f = rw;
-        const float* first = part_first + tid * 4;
-        f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
-        constexpr int PB = 16;  // partial rows in flight
-        for (int k0 = 0; k0 < ns; k0 += PB) {
-            f32x4 q[PB];
+    if constexpr (R::kState == 0) {
+        const float lr = rule.lr;
+        if (sm.last && tid < D / 4) {
+            float* f = rw;
+            const float* first = part_first + tid * 4;
+            f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
+            constexpr int PB = 16;  // partial rows in flight
+            for (int k0 = 0; k0 < ns; k0 += PB) {
+                f32x4 q[PB];
 #pragma unroll
-            for (int u = 0; u < PB; ++u) q[u] = load_sc1(first + (int64_t)(k0 + u < ns ? k0 + u : k0) * pdim);
+                for (int u = 0; u < PB; ++u) q[u] = load_sc1(first + (int64_t)(k0 + u < ns ? k0 + u : k0) * pdim);
 #pragma unroll
-            for (int u = 0; u < PB; ++u)
-                if (k0 + u < ns) s += q[u];
+                for (int u = 0; u < PB; ++u)
+                    if (k0 + u < ns) s += q[u];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) f[e] = __builtin_fmaf(-lr, s[e], f[e]);
+            store_row<TT, 4>(row, tid * 4, f);
+            if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+    } else if (sm.last) {  // (uniform over the workgroup: the row-wise reduction has barriers)
+        f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (tid < D / 4) {
+            const float* first = part_first + tid * 4;
+            constexpr int PB = 16;  // partial rows in flight
+            for (int k0 = 0; k0 < ns; k0 += PB) {
+                f32x4 q[PB];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) f[e] = __builtin_fmaf(-lr, s[e], f[e]);
-        store_row<TT, 4>(row, tid * 4, f);
+                for (int u = 0; u < PB; ++u) q[u] = load_sc1(first + (int64_t)(k0 + u < ns ? k0 + u : k0) * pdim);
+#pragma unroll
+                for (int u = 0; u < PB; ++u)
+                    if (k0 + u < ns) s += q[u];
+            }
+        }
+        slice_write<TT, R, D>(rule, s, rw, sw, row, srow, sm, false);  // (sm.wsum: read before the barriers above)
         if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();  // sm reused by this workgroup's next item
@@ -322,30 +533,38 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
 
 // ---- a slice of a hot segment located by (virtual table vt, local slice sl): sd = {p0, p1,
 // row, h}; the segment's descriptor ix.hot[vt][h] = {beg, end, row, first slice}
-template <typename TT, typename GT, int VPR>
+template <int KSTATE, int D>
+__device__ __forceinline__ float* state_row(float* st, uint32_t r) {
+    return KSTATE == 1 ? st + (int64_t)r * D : (KSTATE == 2 ? st + r : nullptr);
+}
+
+template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_slice(const IndexerDev& ix, int vt, int sl, const int4& sd, TT* __restrict__ table,
-                                          const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L, float lr,
-                                          SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
+                                          float* __restrict__ st, const GT* __restrict__ gbase, int64_t grad_ld,
+                                          const FastDiv& L, const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
     constexpr int D = ApplyGeom<GT, VPR>::D;
     const int64_t off = (int64_t)vt * ix.cap;
     const int4 hd = ix.hot[off + sd.w];
     const int ns = (hd.y - hd.x + kHotSlice - 1) / kHotSlice;
     float* pbase = ix.partial + (int64_t)vt * ix.pcap * ix.pdim;
-    slice_body<TT, GT, VPR>(ix.perm + off + sd.x, sd.y - sd.x, table + (int64_t)(uint32_t)sd.z * D, ns,
-                            pbase + (int64_t)sl * ix.pdim, pbase + (int64_t)hd.w * ix.pdim, ix.pdim,
-                            ix.hot_cnt + off + sd.w, gbase, grad_ld, L, lr, sm);
+    slice_body<TT, GT, VPR, R>(ix.perm + off + sd.x, sd.y - sd.x, table + (int64_t)(uint32_t)sd.z * D,
+                               state_row<R::kState, D>(st, (uint32_t)sd.z), ns, pbase + (int64_t)sl * ix.pdim,
+                               pbase + (int64_t)hd.w * ix.pdim, ix.pdim, ix.hot_cnt + off + sd.w, gbase, grad_ld, L,
+                               rule, sm);
 }
 
 // ---- hot slice k of the item map (one 32-B record: IndexerDev::slice_rec); k and its segment's
 // first slice `first` count over the sub-lists' slices in order (partial row and counter slots)
-template <typename TT, typename GT, int VPR>
+template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_slice_rec(const IndexerDev& ix, int k, int first, const int4& r0, const int4& r1,
-                                              TT* __restrict__ table, const GT* __restrict__ gbase, int64_t grad_ld,
-                                              const FastDiv& L, float lr, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
+                                              TT* __restrict__ table, float* __restrict__ st,
+                                              const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L,
+                                              const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
     constexpr int D = ApplyGeom<GT, VPR>::D;
-    slice_body<TT, GT, VPR>(ix.perm + r0.x, r0.y - r0.x, table + (int64_t)(uint32_t)r0.z * D, r1.x,
-                            ix.partial + (int64_t)k * ix.pdim, ix.partial + (int64_t)first * ix.pdim, ix.pdim,
-                            ix.hot_cnt + first, gbase, grad_ld, L, lr, sm);
+    slice_body<TT, GT, VPR, R>(ix.perm + r0.x, r0.y - r0.x, table + (int64_t)(uint32_t)r0.z * D,
+                               state_row<R::kState, D>(st, (uint32_t)r0.z), r1.x, ix.partial + (int64_t)k * ix.pdim,
+                               ix.partial + (int64_t)first * ix.pdim, ix.pdim, ix.hot_cnt + first, gbase, grad_ld, L,
+                               rule, sm);
 }
 
 }  // namespace dlrm

@@ -426,6 +426,16 @@ struct PrepArgs;
 int launch_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool tabs_aligned16, int T, int D,
                      int tdtype, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
                      float lr, const SinglesArgs& singles, const PrepArgs* prep = nullptr);
+// the same apply with an Adagrad rule (apply.hpp): state = the device array of per-table fp32 state
+// pointers ([nrows][D]; row-wise [nrows]).  aligned16: every table row (element-wise: and every
+// state row) is 16-B aligned.
+int launch_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, float* const* state,
+                         int T, int D, int tdtype, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
+                         int64_t grad_offset, float lr, float eps, const SinglesArgs& singles);
+int launch_rowwise_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16,
+                                 float* const* state, int T, int D, int tdtype, int L, int64_t N, const void* grad,
+                                 int gdtype, int64_t grad_ld, int64_t grad_offset, float lr, float eps,
+                                 const SinglesArgs& singles);
 int launch_triangular_slice(dlrm_ctx* ctx, int dtype, int sz, int B, const void* z, int64_t z_bs, void* out,
                             int64_t out_ld);
 int launch_triangular_slice_back(dlrm_ctx* ctx, int dtype, int sz, int B, const void* dy, int64_t dy_ld, void* a,

@@ -15,7 +15,8 @@
 //     positions.  The same workgroup then lists the segments (one per distinct row): those of
 //     <= kChunk positions as chunks, longer ones (hot rows of small tables: a 3-row table gets
 //     ~680 hits per row at B = 2048) as hot segments.
-//  2. sgd_apply: lane groups take one chunk each (grad rows summed in ascending position
+//  2. sgd_apply (apply_kernel.hpp; instantiated here for Descent, in adagrad.hip and
+//     adagrad_rowwise.hip for the Adagrad rules): lane groups take one chunk each (grad rows summed in ascending position
 //     order, 16-B lanes, 8 rows in flight, the table row prefetched meanwhile) and write the
 //     row once; each hot segment gets a whole workgroup whose lane groups sum fixed-size
 //     sub-chunks into LDS, combined in sub-chunk order before the row is written once.
@@ -79,7 +80,7 @@ extern "C" int dlrm_debug_items(unsigned long long* out, int reset) {
 #define APPLY_END() do {} while (0)
 #endif
 
-#include "apply.hpp"
+#include "apply_kernel.hpp"
 
 namespace dlrm {
 
@@ -347,210 +348,6 @@ __global__ __launch_bounds__(NT) void indexer_fast_kernel(IndexerDev ix, const T
 #endif
 }
 
-// ------------------------------------------------------------------------------ apply
-// Persistent launch, flat over tables (apply.hpp).  Work items: [0, S) = the S slices of every
-// table's hot segments (one workgroup each, handed out first: the longest chains), then
-// ceil(C / NG) items of NG chunks (one per lane group), then (singles: a split indexer whose
-// once-hit rows are this launch's too) T * ceil(N / (NG * SPPG)) items of once-hit
-// positions.  Workgroup b takes items b, b + grid, ...: every item is short, so static striding
-// balances, and no workgroup is launched past the work.
-// MODE 0: chunks + hot slices; 1: + once-hit (singles) items; 2: + the next batch's split indexer
-// in the first (pa.T << pa.ix.vshift) / 4 workgroups (PrepArgs); 3: the same for more than 2048
-// positions per table in rounds; 5: the same by the scan build.
-#ifndef DLRM_BUILD_PRIO
-#define DLRM_BUILD_PRIO 3
-#endif
-constexpr int kBuildPrio = DLRM_BUILD_PRIO;  // s_setprio of the in-apply build's waves (0..3)
-
-// The build of more than 2048 positions per table: 3 = the scan build (indexer.hpp
-// wave_build_group_scan; int32 indices, 16-B aligned per table, N % 4 == 0), the default; 1 = rounds
-// (wave_build_group<true>, any index type; DLRM_WAVE_ROUNDS=1 forces it).
-static int wave_big_kind(const PrepArgs& pa) {
-    if (knobs().wave_rounds) return 1;
-    const bool vec32 = pa.itype == DLRM_I32 && (uintptr_t)pa.idx % 16 == 0 && (pa.tstride * 4) % 16 == 0 &&
-                       pa.N % 4 == 0;
-    return vec32 ? 3 : 1;
-}
-// workgroups of a build (4 parts each)
-__host__ __device__ __forceinline__ int prep_groups(const PrepArgs& pa) { return (pa.T << pa.ix.vshift) / kWaveParts; }
-
-template <typename TT, typename GT, int VPR, int MODE>
-__global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev ix, TableDesc* __restrict__ tabs, int T_,
-                                                                  int L, const GT* __restrict__ grad, int64_t grad_ld,
-                                                                  int64_t grad_offset, float lr,
-                                                                  const unsigned* __restrict__ err, SinglesArgs sa,
-                                                                  PrepArgs pa) {
-    constexpr bool SG = MODE == 1;
-    int bid = blockIdx.x, nblk = gridDim.x;
-    if (MODE >= 2) {
-        extern __shared__ __attribute__((aligned(16))) unsigned char prep_lds[];
-        const int NI = prep_groups(pa);
-        if (bid < NI) {  // the next batch's split build: one wave per table part (indexer.hpp)
-            // the build's waves first at the issue arbiter: its chain of dependent LDS / VALU steps is
-            // the launch's longest, the apply waves beside it mostly wait on memory (A/B on one box:
-            // 54.72 / 54.77 -> 54.91 / 55.04 M samples/s, apply 10.58 -> 10.45 us)
-            __builtin_amdgcn_s_setprio(kBuildPrio);
-            ITEM_START(4, 0, bid);
-            // (MODE 3 / 5: the builds of more than 2048 positions per table, in their own
-            // instantiations, so the step's MODE 2 kernel keeps its registers)
-            if constexpr (MODE == 5)
-                wave_build_group_scan<kWaveParts>(pa.ix, bid, pa.T, pa.tabs, pa.idx, pa.tstride, pa.base, pa.N, pa.err,
-                                      *(WaveBuildLds*)prep_lds);
-            else
-                wave_build_group<MODE == 3>(pa.ix, bid, pa.T, pa.tabs, pa.idx, pa.itype, pa.tstride, pa.base,
-                                            pa.N, pa.err, *(WaveBuildLds*)prep_lds);
-            ITEM_END(0);
-            return;
-        }
-        bid -= NI;
-        nblk -= NI;
-#ifdef DLRM_PREP_ONLY  // (probe: the build alone in this launch)
-        return;
-#endif
-    }
-    // a bounds error raised since the last dlrm_check_bounds (the lookup or the indexer build of
-    // this step): the reference's gather throws before update!, so no table row is written.  (The
-    // error word is loaded with the item counts, one round trip for both.)
-    const FastDiv Ld(L);  // position -> bag
-    unsigned err0 = ldg<unsigned>(err);
-    if (ix.build_err) {  // a standalone prepared build's out-of-range indices (written by an earlier launch)
-        const unsigned be = ldg<unsigned>(ix.build_err);
-        if (be && !err0 && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) raise_index_error((unsigned*)err);
-        err0 |= be;
-    }
-    typedef ApplyGeom<GT, VPR> G;
-    constexpr int D = G::D, NG = G::NG;
-    __shared__ SliceLds<D> sm;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int g = lane / G::LPR, v = lane % G::LPR;
-    const int gid = w * G::RPW + g;
-    // where this launch's items are: the wave build's flat item map (one load per item), else a
-    // wave scan of every virtual table's counts (TableScan) and a lookup in it per item
-    const bool mp = ix.has_map != 0;
-    TableScan sS{}, sC{};
-    int Stot, Ctot;
-    // the item map's sub-list counts (indexer.hpp kResLists), kept in LDS: item_tot[0..8) slices,
-    // [8..16) chunks
-    __shared__ int lcnt[2 * kResLists];
-    const int* ls = lcnt;
-    const int* lc = lcnt + kResLists;
-    int lstride = 0;
-    if (mp) {
-        if (threadIdx.x < 2 * kResLists) lcnt[threadIdx.x] = ix.item_tot[threadIdx.x];
-        __syncthreads();
-        Stot = 0;
-        Ctot = 0;
-#pragma unroll
-        for (int j = 0; j < kResLists; ++j) {
-            Stot += ls[j];
-            Ctot += lc[j];
-        }
-        lstride = res_stride(T_ / kWaveParts, ix.cap, ix.vshift);
-    } else {
-        sS = scan_counts(ix, T_, CNT_S);
-        sC = scan_counts(ix, T_, CNT_C);
-        Stot = sS.total;
-        Ctot = sC.total;
-    }
-    if (err0) return;
-    const int citems = Stot + (Ctot + NG - 1) / NG;
-    constexpr int SP = NG * G::SPPG;                           // positions per singles item
-    const int per_t = SG ? (sa.N + SP - 1) / SP : 0;          // singles items per real table
-    const int items = citems + (T_ >> ix.vshift) * per_t;
-    // Pooled bags (L > 1): every position of a bag reads the bag's gradient row, so a table's
-    // gradient slice ([B][D]: 2 MB at B = 2048, D = 256 fp32) is read about L times.  Workgroups b
-    // and b + 8 share an XCD (and its L2): with the plain stride every XCD walks every table and
-    // fetches each slice for itself.  Instead each XCD takes one contiguous eighth of each item
-    // kind (hot slices, chunk items, once-hit items) -- about an eighth of the tables -- so a slice
-    // is fetched by one L2 and re-read there.  (One-hot: each gradient row is read once; plain.)
-    //   item = pos + (pos < e0 ? r0 : pos < e1 ? s1 : s2), pos = this workgroup's list position
-    int pos0 = bid, step = nblk, npos = items, r0 = 0, e0 = items, s1 = 0, e1 = items, s2 = 0;
-    if (L > 1 && (nblk & 7) == 0 && ((blockIdx.x - bid) & 7) == 0) {
-        const int x = bid & 7, c1 = citems - Stot, c2 = items - citems;
-        const int a0 = (int)((int64_t)Stot * x >> 3), b0 = (int)((int64_t)Stot * (x + 1) >> 3);
-        const int a1 = (int)((int64_t)c1 * x >> 3), b1 = (int)((int64_t)c1 * (x + 1) >> 3);
-        const int a2 = (int)((int64_t)c2 * x >> 3), b2 = (int)((int64_t)c2 * (x + 1) >> 3);
-        r0 = a0;
-        e0 = b0 - a0;
-        s1 = Stot + a1 - e0;
-        e1 = e0 + (b1 - a1);
-        s2 = citems + a2 - e1;
-        npos = e1 + (b2 - a2);
-        pos0 = bid >> 3;
-        step = nblk >> 3;
-    }
-#ifdef DLRM_PHASE
-    int kk_ = 0;
-#endif
-    for (int pos = pos0; pos < npos; pos += step) {
-        const int item = pos + (pos < e0 ? r0 : (pos < e1 ? s1 : s2));
-        APPLY_START(item >= citems ? 3 : (item >= Stot ? 1 : 2));
-#ifdef DLRM_PHASE
-        const int k_ = kk_++;
-        ITEM_START(item >= citems ? 3 : (item >= Stot ? 1 : 2), k_, item);
-#undef APPLY_END
-#define APPLY_END() do { ITEM_END(k_); } while (0)
-#endif
-        if (SG && item >= citems) {  // uniform: once-hit positions of one real table
-            const int t = (item - citems) / per_t;
-            const int p0 = ((item - citems) - t * per_t) * SP + gid * G::SPPG;
-            if (g >= G::RPW) continue;
-            const TableDesc td = load_table(tabs, t);
-            run_singles<TT, GT, VPR>(sa, ix.cap, (TT*)td.data, td.nrows, t, p0, grad + grad_offset + (int64_t)t * D,
-                                     grad_ld, Ld, lr, v, lane - v);
-            APPLY_END();
-            continue;
-        }
-        if (item >= Stot) {
-            const int fc = (item - Stot) * NG + gid;  // flat chunk of this lane group
-            const int32_t* pbase;
-            int4 ca, cb;
-            int t;
-            if (mp) {  // the flat chunk record: perm entries global, the virtual table = beg / cap
-                if (g >= G::RPW || fc >= Ctot) continue;
-                const int r = res_locate(lc, fc, lstride);
-                ca = ix.chunk_rec[2 * (int64_t)r];
-                cb = ix.chunk_rec[2 * (int64_t)r + 1];
-                pbase = ix.perm;
-                t = (int)(ca.x / ix.cap);  // (the compact layout: entries of table t at [t cap, (t + 1) cap))
-            } else {
-                int tc, cl;
-                locate(ix, T_, CNT_C, sC, fc, tc, cl);
-                if (g >= G::RPW || tc < 0) continue;
-                const int64_t co = 2 * ((int64_t)tc * ix.cap + cl);
-                ca = ix.chunks[co];
-                cb = ix.chunks[co + 1];
-                pbase = ix.perm + (int64_t)tc * ix.cap;
-                t = tc >> ix.vshift;
-            }
-            run_chunk<TT, GT, VPR>(pbase, ca, cb, (TT*)tabs[t].data, grad + grad_offset + (int64_t)t * D, grad_ld, Ld,
-                                   lr, v, lane - v);
-            APPLY_END();
-            continue;
-        }
-        if (mp) {  // (uniform: the slice's whole record in one 32-B load)
-            const int r = res_locate(ls, item, lstride);
-            const int4 r0 = ix.slice_rec[2 * (int64_t)r], r1 = ix.slice_rec[2 * (int64_t)r + 1];
-            const int t = r0.w >> ix.vshift;
-            run_slice_rec<TT, GT, VPR>(ix, item, item - (r - r1.y), r0, r1, (TT*)tabs[t].data, grad + grad_offset + (int64_t)t * D,
-                                       grad_ld, Ld, lr, sm);
-            APPLY_END();
-            continue;
-        }
-        int th, sl;
-        locate(ix, T_, CNT_S, sS, item, th, sl);  // item < S: found, the same for every lane
-        const int4 sd = ix.hot_slice[(int64_t)th * ix.cap + sl];
-        const int t = th >> ix.vshift;
-        run_slice<TT, GT, VPR>(ix, th, sl, sd, (TT*)tabs[t].data, grad + grad_offset + (int64_t)t * D, grad_ld, Ld, lr,
-                               sm);
-        APPLY_END();
-    }
-#ifdef DLRM_PHASE
-#undef APPLY_END
-#define APPLY_END() do {} while (0)
-#endif
-}
-
 // The step indexer's workgroups alone (PrepArgs), where the apply has no vector kernel to host them.
 // KIND 0: one round (N <= 2048); 1: rounds (the scan build has its own kernel below).
 template <int KIND>
@@ -601,7 +398,7 @@ static void launch_step_index_kind(hipStream_t s, const PrepArgs& pa) {
 }
 
 // step_index_kernel's own launch (the next batch's split build when the apply launch cannot carry it)
-static void launch_step_index(hipStream_t s, const PrepArgs& pa) {
+void launch_step_index(hipStream_t s, const PrepArgs& pa) {
     const int kind = pa.N <= kStepIndexMaxN ? 0 : wave_big_kind(pa);
     if (kind == 0) launch_step_index_kind<0>(s, pa);
     else if (kind == 1) launch_step_index_kind<1>(s, pa);
@@ -953,73 +750,6 @@ int launch_step_prepare(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* ta
     return ctx_hip(ctx, hipGetLastError(), "step_index launch");
 }
 
-// Generic (any D) versions: one thread per element column.
-template <typename TT, typename GT>
-__global__ __launch_bounds__(256) void sgd_chunks_scalar(IndexerDev ix, TableDesc* __restrict__ tabs, int D, int L,
-                                                         const GT* __restrict__ grad, int64_t grad_ld,
-                                                         int64_t grad_offset, float lr, const unsigned* __restrict__ err) {
-    if (ix.build_err && *ix.build_err) {  // (a prepared build's bounds error: raised here, before hot / singles)
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) raise_index_error((unsigned*)err);
-        return;
-    }
-    if (*err) return;
-    const int t = blockIdx.y;
-    const int nchunks = ix.counts[(int64_t)t * 8 + CNT_C];
-    const int64_t off = ix.part_off(t);
-    const int64_t total = (int64_t)nchunks * D;
-    TT* table = (TT*)tabs[t >> ix.vshift].data;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const int cid = (int)(e / D), c = (int)(e % D);
-        const int4 cd = ix.chunks[2 * (off + cid)];
-        float acc = 0.0f;
-        for (int i = cd.x; i < cd.y; ++i)
-            acc += to_f32(grad[(int64_t)(ix.perm[off + i] / L) * grad_ld + grad_offset + (int64_t)(t >> ix.vshift) * D + c]);
-        TT* row = table + (int64_t)(uint32_t)cd.z * D;
-        row[c] = from_f32<TT>(__builtin_fmaf(-lr, acc, to_f32(row[c])));
-    }
-}
-
-template <typename TT, typename GT>
-__global__ __launch_bounds__(256) void sgd_hot_scalar(IndexerDev ix, TableDesc* __restrict__ tabs, int D, int L,
-                                                      const GT* __restrict__ grad, int64_t grad_ld,
-                                                      int64_t grad_offset, float lr, const unsigned* __restrict__ err) {
-    if (*err) return;
-    const int t = blockIdx.y;
-    const int nhot = ix.counts[(int64_t)t * 8 + CNT_H];
-    const int64_t off = ix.part_off(t);
-    const int64_t total = (int64_t)nhot * D;
-    TT* table = (TT*)tabs[t >> ix.vshift].data;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const int h = (int)(e / D), c = (int)(e % D);
-        const int4 hd = ix.hot[off + h];
-        float acc = 0.0f;
-        for (int i = hd.x; i < hd.y; ++i)
-            acc += to_f32(grad[(int64_t)(ix.perm[off + i] / L) * grad_ld + grad_offset + (int64_t)(t >> ix.vshift) * D + c]);
-        TT* row = table + (int64_t)(uint32_t)hd.z * D;
-        row[c] = from_f32<TT>(__builtin_fmaf(-lr, acc, to_f32(row[c])));
-    }
-}
-
-template <typename TT, typename GT>
-__global__ __launch_bounds__(256) void sgd_singles_scalar(SinglesArgs sa, int64_t cap, TableDesc* __restrict__ tabs,
-                                                          int D, int L, const GT* __restrict__ grad, int64_t grad_ld,
-                                                          int64_t grad_offset, float lr,
-                                                          const unsigned* __restrict__ err) {
-    if (*err) return;
-    const int t = blockIdx.y;
-    const int64_t total = (int64_t)sa.N * D;
-    TT* table = (TT*)tabs[t].data;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const int p = (int)(e / D), c = (int)(e % D);
-        if (!sa.single[(int64_t)t * cap + p]) continue;
-        const int64_t r = load_index(sa.idx, sa.itype, (int64_t)t * sa.tstride + p) - sa.base;
-        if (r < 0 || r >= tabs[t].nrows) continue;
-        const float g = to_f32(grad[(int64_t)(p / L) * grad_ld + grad_offset + (int64_t)t * D + c]);
-        TT* row = table + r * D;
-        row[c] = from_f32<TT>(__builtin_fmaf(-lr, 0.0f + g, to_f32(row[c])));
-    }
-}
-
 // Non-deterministic: every lookup adds -lr * grad straight into its row (fp32 tables).
 template <typename GT>
 __global__ __launch_bounds__(256) void sgd_atomic_kernel(TableDesc* __restrict__ tabs, int ntab, int D,
@@ -1102,120 +832,11 @@ int launch_indexer_build(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* t
     return ctx_hip(ctx, hipGetLastError(), "indexer_build launch");
 }
 
-// the apply launch that also carries the next batch's build (MODE >= 2): build workgroups first
-template <typename TT, typename GT, int VPR, int MODE>
-static void launch_apply_build(hipStream_t s, unsigned grid, const IndexerDev& ix, TableDesc* tabs, int T_, int L,
-                               const void* grad, int64_t grad_ld, int64_t grad_offset, float lr, const unsigned* err,
-                               const SinglesArgs& sa, const PrepArgs& pa) {
-    static const hipError_t attr = hipFuncSetAttribute((const void*)sgd_apply_kernel<TT, GT, VPR, MODE>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)sizeof(WaveBuildLds));
-    (void)attr;
-    hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, MODE>), dim3(grid), dim3(kApplyThreads), sizeof(WaveBuildLds), s,
-                       ix, tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, lr, err, sa, pa);
-}
-
-template <typename TT, typename GT, int VPR>
-static void launch_apply_vec(hipStream_t s, const IndexerDev& ix, TableDesc* tabs, int T_, int L, const void* grad,
-                             int64_t grad_ld, int64_t grad_offset, float lr, int64_t N, const unsigned* err,
-                             const SinglesArgs& sa, const PrepArgs* pa) {
-    typedef ApplyGeom<GT, VPR> G;
-    // persistent grid: resident workgroups only (never more than the worst-case item count per
-    // table: N / kHotSlice + N / (kChunk + 1) + 1 hot slices, N / NG chunk items, singles items)
-    const int64_t SP = G::NG * G::SPPG;
-    const int64_t ib = (int64_t)T_ * (N / kHotSlice + N / (kMinChunk + 1) + 1 + (N + G::NG - 1) / G::NG) +
-                       (sa.single ? (int64_t)(T_ >> ix.vshift) * ((N + SP - 1) / SP) : 0);
-    static int per_cu = 0;
-    if (!per_cu) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sgd_apply_kernel<TT, GT, VPR, 0>, kApplyThreads,
-                                                         0) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-    }
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    int64_t grid = (int64_t)per_cu * (cus > 0 ? cus : 256);
-    if (grid > ib) grid = ib;
-    if (grid < 1) grid = 1;
-    // (the once-hit items and the next batch's indexer are separate instantiations: the step's
-    // apply stays lean)
-    if (pa && !sa.single) {
-        // MODE 2: <= 2048 positions per table; above, 2 + wave_big_kind (3 rounds, 5 scan)
-        const int mode = pa->N <= kStepIndexMaxN ? 2 : 2 + wave_big_kind(*pa);
-        const unsigned g2 = (unsigned)(grid + prep_groups(*pa));
-        if (mode == 2) launch_apply_build<TT, GT, VPR, 2>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, err, sa, *pa);
-        else if (mode == 5) launch_apply_build<TT, GT, VPR, 5>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, err, sa, *pa);
-        else launch_apply_build<TT, GT, VPR, 3>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, err, sa, *pa);
-    } else if (sa.single) {
-        hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, 1>), dim3((unsigned)grid), dim3(kApplyThreads), 0, s, ix,
-                           tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, lr, err, sa, PrepArgs{});
-        // MODE 2 has no once-hit items: the next batch's build (if any) gets its own launch
-        if (pa) launch_step_index(s, *pa);
-    } else {
-        hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, 0>), dim3((unsigned)grid), dim3(kApplyThreads), 0, s, ix,
-                           tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, lr, err, sa, PrepArgs{});
-    }
-}
-
-template <typename TT, typename GT>
-static bool dispatch_apply(int vpr, hipStream_t s, const IndexerDev& ix, TableDesc* tabs, int T_, int L,
-                           const void* grad, int64_t grad_ld, int64_t grad_offset, float lr, int64_t N,
-                           const unsigned* err, const SinglesArgs& sa, const PrepArgs* pa) {
-#define DLRM_CASE(V) \
-    case V: launch_apply_vec<TT, GT, V>(s, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, N, err, sa, pa); return true;
-    switch (vpr) {
-        DLRM_CASE(1) DLRM_CASE(2) DLRM_CASE(4) DLRM_CASE(8) DLRM_CASE(16) DLRM_CASE(32) DLRM_CASE(64) DLRM_CASE(128)
-        default: return false;
-    }
-#undef DLRM_CASE
-}
-
 int launch_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool tabs_aligned16, int T_, int D,
                      int tdtype, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
                      float lr, const SinglesArgs& sa, const PrepArgs* pa) {
-    if (T_ == 0 || N == 0) return DLRM_OK;
-    T_ <<= ix.vshift;  // virtual tables (row-parity halves) of a forward-launch build
-    hipStream_t s = ctx_stream(ctx);
-    const unsigned* err = ctx_error_word(ctx);
-    const int gesz = gdtype == DLRM_F32 ? 4 : 2;
-    const int tesz = tdtype == DLRM_F32 ? 4 : 2;
-    const bool aligned = tabs_aligned16 && (uintptr_t)grad % 16 == 0 && (grad_ld * gesz) % 16 == 0 &&
-                         (grad_offset * gesz) % 16 == 0 && (D * gesz) % 16 == 0 && (D * tesz) % 16 == 0 && D % 4 == 0;
-    bool done = false;
-    const int64_t slots = (int64_t)T_ * (N + 1);  // (item counts stay in int)
-    if (aligned && slots < (1ll << 31)) {
-        const int vpr = D * gesz / 16;
-        if (tdtype == DLRM_F32 && gdtype == DLRM_F32)
-            done = dispatch_apply<float, float>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, N, err, sa, pa);
-        else if (tdtype == DLRM_BF16 && gdtype == DLRM_F32)
-            done = dispatch_apply<uint16_t, float>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, N, err, sa, pa);
-        else if (tdtype == DLRM_F32 && gdtype == DLRM_BF16)
-            done = dispatch_apply<float, uint16_t>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, N, err, sa, pa);
-        else
-            done = dispatch_apply<uint16_t, uint16_t>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, N,
-                                                      err, sa, pa);
-    }
-    if (!done && pa) launch_step_index(s, *pa);
-    if (!done) {
-        const int64_t gx0 = (N * D + 255) / 256;
-        const unsigned gx = (unsigned)(gx0 < 1 ? 1 : (gx0 > 4096 ? 4096 : gx0));
-        const int64_t hx0 = ((N / (kChunk + 1)) * D + 255) / 256;
-        const unsigned hx = (unsigned)(hx0 < 1 ? 1 : (hx0 > 1024 ? 1024 : hx0));
-#define DLRM_SCALAR(TT, GT)                                                                                         \
-    hipLaunchKernelGGL((sgd_chunks_scalar<TT, GT>), dim3(gx, T_), dim3(256), 0, s, ix, tabs, D, L, (const GT*)grad, \
-                       grad_ld, grad_offset, lr, err);                                                              \
-    hipLaunchKernelGGL((sgd_hot_scalar<TT, GT>), dim3(hx, T_), dim3(256), 0, s, ix, tabs, D, L, (const GT*)grad,    \
-                       grad_ld, grad_offset, lr, err);                                                              \
-    if (sa.single)                                                                                                  \
-        hipLaunchKernelGGL((sgd_singles_scalar<TT, GT>), dim3(gx, T_ >> ix.vshift), dim3(256), 0, s, sa, ix.cap,    \
-                           tabs, D, L, (const GT*)grad, grad_ld, grad_offset, lr, err);
-        if (tdtype == DLRM_F32 && gdtype == DLRM_F32) { DLRM_SCALAR(float, float) }
-        else if (tdtype == DLRM_BF16 && gdtype == DLRM_F32) { DLRM_SCALAR(uint16_t, float) }
-        else if (tdtype == DLRM_F32 && gdtype == DLRM_BF16) { DLRM_SCALAR(float, uint16_t) }
-        else { DLRM_SCALAR(uint16_t, uint16_t) }
-#undef DLRM_SCALAR
-    }
-    return ctx_hip(ctx, hipGetLastError(), "sgd_apply launch");
+    return launch_apply_rule(ctx, ix, tabs, tabs_aligned16, T_, D, tdtype, L, N, grad, gdtype, grad_ld, grad_offset,
+                             Descent{lr}, sa, pa);
 }
 
 int launch_sgd_atomic(dlrm_ctx* ctx, TableDesc* tabs, int T_, int D, const void* idx, int itype, int64_t tstride,

@@ -24,6 +24,11 @@ forward writes only `out` and the backward rebuilds T from x and the gathered ta
 (dlrm_interact_bwd_gather) -- the same values, bit for bit, since the tables change only in
 the update that follows -- which saves ys's write and keeps the step's HBM traffic at what
 the math needs.  Turn it on to read `ys` (e.g. for parity checks against maplookup).
+
+`opt` (an `ADAGrad` or `RowwiseADAGrad`; default None = `Descent(lr)`): the tables are stepped with
+that optimizer.  The fused step pair is Descent-only, so this selects the operator path: the fused
+forward, the gather backward (which writes every dt row and builds the indexer in its launch),
+then dlrm_adagrad_update(PREBUILT) -- three launches, no host synchronisation, graph-capturable.
 """
 import torch
 
@@ -32,13 +37,18 @@ from .embedding import EmbeddingTableSet, PackedIndices
 from .interact import interaction_sizes
 from .runtime import dtype_code, ptr, require_device
 from .shapes import APPLY_MAX_N
-from .update import SparseIndexer
+from .update import SparseIndexer, _AdagradBase
 
 
 class HotPath:
     def __init__(self, tables, batch, lookups=1, *, lr=0.1, index_base=0, deterministic=True,
                  overlap_indexer=None, pad_to=1, fused=True, materialize_ys=None, pipeline=False, chunk=None,
-                 parts=None):
+                 parts=None, opt=None):
+        if opt is not None and not isinstance(opt, _AdagradBase):
+            raise TypeError("HotPath: opt is an ADAGrad or RowwiseADAGrad (None: Descent(lr))")
+        if opt is not None and not deterministic:
+            raise ValueError("HotPath: an Adagrad optimizer needs the deterministic update")
+        self.opt = opt
         self.ts = tables if isinstance(tables, EmbeddingTableSet) else EmbeddingTableSet(tables)
         self.B, self.L = int(batch), int(lookups)
         self.T, self.D = len(self.ts), self.ts.D
@@ -83,7 +93,8 @@ class HotPath:
         self._indexer_done = None
         # the training-step pair (dlrm_step_fwd / dlrm_step_bwd): indexer built inside the forward's
         # launch, once-hit rows updated inside the backward's, the rest by the apply launch
-        self.step_api = (not self.materialize_ys) and self.indexer is not None and not self.overlap_indexer
+        self.step_api = ((not self.materialize_ys) and self.indexer is not None and not self.overlap_indexer and
+                         opt is None)  # (dlrm_step_bwd steps with Descent)
         # pipelined steps: the NEXT batch's split indexer is built during this step, so the
         # step's forward launch only gathers; two indexers alternate.
         #   "apply" (`step_prep`): by extra workgroups of this step's apply launch
@@ -94,6 +105,10 @@ class HotPath:
         mode = {False: None, 0: None, None: None, True: "side", 1: "side", 2: "apply"}.get(pipeline, pipeline)
         if mode not in (None, "side", "apply"):
             raise ValueError(f"pipeline must be None, 'side' or 'apply', not {pipeline!r}")
+        if opt is not None:
+            if mode is not None:
+                raise ValueError("HotPath: the pipelined steps are Descent-only (pipeline must be None with opt)")
+            opt.handle_of(self.ts)  # the state, allocated before any graph capture
         # (pooled bags: "side" only -- the next batch's build beside this step's apply, `step_next`)
         self.pipeline = mode if (mode and ((self.step_api and self.L == 1) or (mode == "side" and self.L > 1))) else None
         self._prepare_ok = None  # build_split: None untried, False the wave build does not take it
@@ -168,6 +183,16 @@ class HotPath:
         self._check(self.lib.dlrm_sgd_update(h, self.ts.handle, self.indexer.handle if self.indexer else None, flags,
                                              ptr(idx.data), idx.itype, idx.stride, self.index_base, self.B, self.L,
                                              ptr(self.dt), _lib.F32, self.dt.stride(0), self.d, self.lr))
+
+    def adagrad_update(self, idx, prebuilt, opt=None):
+        """dlrm_adagrad_update of dt with `opt` (default: the engine's optimizer)."""
+        h = self.ctx.bind()
+        opt = self.opt if opt is None else opt
+        flags = _lib.UPDATE_PREBUILT if prebuilt else 0
+        self._check(self.lib.dlrm_adagrad_update(h, self.ts.handle, opt.handle_of(self.ts), self.indexer.handle,
+                                                 flags, ptr(idx.data), idx.itype, idx.stride, self.index_base, self.B,
+                                                 self.L, ptr(self.dt), _lib.F32, self.dt.stride(0), self.d, opt.eta,
+                                                 opt.eps))
 
     def step_fwd(self, x, idx):
         """dlrm_step_fwd: lookup + interaction (no ys) + the split indexer, one launch."""
@@ -339,7 +364,10 @@ class HotPath:
         if self.overlap_indexer and self._indexer_done is not None:
             torch.cuda.current_stream(self.ts.device).wait_event(self._indexer_done)
             prebuilt = True
-        self.sgd_update(idx, prebuilt)
+        if self.opt is not None:
+            self.adagrad_update(idx, prebuilt)
+        else:
+            self.sgd_update(idx, prebuilt)
         return self.dx
 
     def step(self, x, idx, dout):

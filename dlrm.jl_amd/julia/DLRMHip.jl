@@ -404,6 +404,97 @@ function EmbeddingTables.update!(
 end
 
 #####
+##### Sparse Adagrad on the tables: HipADAGrad (Flux.ADAGrad, element-wise) and HipRowwiseADAGrad
+##### (one fp32 accumulator per table row).  The dense MLP parameters keep their own optimiser.
+#####
+
+abstract type AbstractHipADAGrad end
+
+"""
+    HipADAGrad(η = 0.1, ϵ = 1e-8)
+
+`Flux.ADAGrad(η, ϵ)` for `HipEmbedding` tables: `A .+= G.^2; w .-= η .* G ./ (sqrt.(A) .+ ϵ)` on the
+rows a batch touches (an untouched row has `G = 0`, so dense and sparse agree).  The fp32 state
+(`D × N` per table, filled with `ϵ` as Flux does) is created on the device at the first `update!` of
+a table vector and kept per table vector, as Flux keys its `IdDict` by parameter;
+`adagrad_state(opt, tables)` returns it.
+"""
+mutable struct HipADAGrad <: AbstractHipADAGrad
+    eta::Float32
+    epsilon::Float32
+    state::IdDict{Any,Any}     # tables => (state matrices, dlrm_adagrad handle)
+end
+HipADAGrad(η = 0.1, ϵ = 1e-8) = HipADAGrad(Float32(η), Float32(ϵ), IdDict{Any,Any}())
+
+"""
+    HipRowwiseADAGrad(η = 0.1, ϵ = 1e-8)
+
+Row-wise Adagrad: `m[r] += mean(G[:, r].^2); w[:, r] .-= η .* G[:, r] ./ (sqrt(m[r]) + ϵ)`, one fp32
+word per table row (`1 × N` per table, zero at the start): 3.5 GB for the Terabyte set's 882.8 M rows.
+"""
+mutable struct HipRowwiseADAGrad <: AbstractHipADAGrad
+    eta::Float32
+    epsilon::Float32
+    state::IdDict{Any,Any}
+end
+HipRowwiseADAGrad(η = 0.1, ϵ = 1e-8) = HipRowwiseADAGrad(Float32(η), Float32(ϵ), IdDict{Any,Any}())
+
+rowwise(::HipADAGrad) = false
+rowwise(::HipRowwiseADAGrad) = true
+function init_state(opt::HipADAGrad, t::HipEmbedding)
+    D, N = size(t)
+    return upload!(DeviceMatrix{Float32}(t.data.ctx, D, N), fill(opt.epsilon, D, N))
+end
+function init_state(::HipRowwiseADAGrad, t::HipEmbedding)
+    N = size(t, 2)
+    return upload!(DeviceMatrix{Float32}(t.data.ctx, 1, N), zeros(Float32, 1, N))
+end
+
+"The optimizer state of `tables` (one `DeviceMatrix{Float32}` per table) and its dlrm_adagrad handle."
+function adagrad_state(opt::AbstractHipADAGrad, tables::AbstractVector{<:HipEmbedding})
+    get!(opt.state, tables) do
+        ctx = first(tables).data.ctx
+        state = [init_state(opt, t) for t in tables]
+        ptrs = [m.ptr for m in state]
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ctx, ccall((:dlrm_adagrad_create, libdlrm), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                         ctx.ptr, tableset(tables), Cint(rowwise(opt)), ptrs, out))
+        (state, out[])
+    end
+end
+
+# update!(HipADAGrad / HipRowwiseADAGrad, tables, grads, indexers): the unfused path builds the
+# indexer in the call; after a fused step's pullback that wrote every dt row (a fused context without a
+# learning rate) the forward's split indexer is reused (_fused_update!).
+function EmbeddingTables.update!(
+    opt::AbstractHipADAGrad, tables::AbstractVector{<:HipEmbedding{Static{D}}},
+    grads::AbstractVector{<:SparseEmbeddingUpdate}, indexers; num_splits = 8, nthreads = Threads.nthreads()
+) where {D}
+    length(grads) == length(tables) || throw(ArgumentError("one SparseEmbeddingUpdate per table"))
+    δ1, ix1 = hip_delta(first(grads)), hip_indices(first(grads))
+    for (t, g) in enumerate(grads)
+        δ, ix = hip_delta(g), hip_indices(g)
+        (δ.dt === δ1.dt && δ.offset == δ1.offset + (t - 1) * D && ix.idx === ix1.idx && ix.table == t) ||
+            throw(ArgumentError("update! expects the per-table views of one maplookup pullback"))
+    end
+    ctx, idx = δ1.dt.ctx, ix1.idx
+    if ctx.fused && haskey(CHAIN_STEPS, tables) && haskey(CHAIN_STEPS[tables], idx.batch)
+        st = CHAIN_STEPS[tables][idx.batch]
+        st.dt === δ1.dt && return _fused_update!(opt, st, tables)
+    end
+    ix = get!(() -> HipIndexer(ctx, length(tables), idx.batch * idx.lookups), INDEXERS, indexers)
+    _, h = adagrad_state(opt, tables)
+    check(ctx, ccall((:dlrm_adagrad_update, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cuint, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint,
+                      Ptr{Cvoid}, Cint, Int64, Int64, Cfloat, Cfloat),
+                     ctx.ptr, tableset(tables), h, ix.ptr, Cuint(0), idx.data.ptr, DLRM_I32, idx.batch * idx.lookups, 1,
+                     idx.batch, idx.lookups, δ1.dt.ptr, DLRM_F32, size(δ1.dt, 1), δ1.offset, opt.eta, opt.epsilon))
+    check_bounds(ctx)     # BoundsError, as the reference's gather throws (no row or state was written)
+    return nothing
+end
+
+#####
 ##### Optional fast path: the sparse half of one train! iteration as the training-step pair
 ##### (dlrm_step_fwd / dlrm_step_bwd): identical results to maplookup -> interaction ->
 ##### dot_back -> update!, three launches instead of five.
@@ -688,6 +779,22 @@ end
 function _fused_update!(opt, st, tables)
     ctx = st.ctx
     d, B = size(st.x)
+    if opt isa AbstractHipADAGrad
+        # every dt row is needed: the forward's split indexer, the once-hit rows as singles items
+        st.bwd === :once_hit_applied &&
+            throw(ArgumentError("the pullback already stepped the once-hit rows with Descent (η = $(ctx.lr)) and left " *
+                                "their gradient rows unwritten; use a context without a learning rate to update with Adagrad"))
+        st.bwd === :all_dt || throw(ArgumentError("update! before the interaction's pullback ran"))
+        _, h = adagrad_state(opt, tables)
+        check(ctx, ccall((:dlrm_adagrad_update, libdlrm), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cuint, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint,
+                          Ptr{Cvoid}, Cint, Int64, Int64, Cfloat, Cfloat),
+                         ctx.ptr, tableset(st.tables), h, st.ix.ptr, UPDATE_PREBUILT, st.idx.data.ptr, DLRM_I32,
+                         st.idx.batch, 1, st.idx.batch, 1, st.dt.ptr, DLRM_F32, size(st.dt, 1), d, opt.eta, opt.epsilon))
+        st.bwd = :done
+        check_bounds(ctx)
+        return nothing
+    end
     if st.bwd === :once_hit_applied && ctx.defer
         opt.eta == ctx.lr || throw(ArgumentError("the pullback stepped the once-hit rows with η = $(ctx.lr), update! got $(opt.eta)"))
         # the apply launch runs in the next maplookup (flush!); bounds surface there (poll_bounds!)

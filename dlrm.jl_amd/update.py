@@ -28,6 +28,70 @@ class Descent:
         return f"Descent({self.eta})"
 
 
+class _AdagradBase:
+    """Sparse Adagrad over embedding tables.  The state is kept per table set (as Flux keys its
+    IdDict by parameter): allocated on the tables' device at first use, and exposed by
+    `state_of(tables)` so a caller can read, save or preset it."""
+    rowwise = False
+
+    def __init__(self, eta=0.1, eps=1e-8):
+        self.eta = float(eta)
+        self.eps = float(eps)
+        self._state = {}  # the tables' data pointers -> (table set, [state tensors], dlrm_adagrad handle)
+
+    def _init_state(self, table):
+        raise NotImplementedError
+
+    def _entry(self, tables):
+        ts = as_table_set(tables)
+        key = tuple(t.data.data_ptr() for t in ts)  # (the parameters themselves: any table set over them)
+        ent = self._state.get(key)
+        if ent is None:
+            state = [self._init_state(t.data) for t in ts]
+            T = len(ts)
+            ptrs = (ctypes.c_void_p * T)(*[s.data_ptr() for s in state])
+            h = ctypes.c_void_p()
+            ts.ctx.check(ts.ctx.lib.dlrm_adagrad_create(ts.ctx.bind(), ts.handle, int(self.rowwise), ptrs,
+                                                        ctypes.byref(h)))
+            ent = self._state[key] = (ts, state, h)
+        return ent
+
+    def state_of(self, tables):
+        """The fp32 state tensors of `tables` (a table set), one per table: [nrows][D] accumulators
+        (ADAGrad) or [nrows] row accumulators (RowwiseADAGrad).  Write into them to preset the state."""
+        return self._entry(tables)[1]
+
+    def handle_of(self, tables):
+        return self._entry(tables)[2]
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.eta}, {self.eps})"
+
+    def __del__(self):
+        try:
+            for ts, _, h in self._state.values():
+                ts.ctx.lib.dlrm_adagrad_destroy(h)
+        except Exception:
+            pass
+
+
+class ADAGrad(_AdagradBase):
+    """Flux.ADAGrad(η, ϵ): A .+= g.^2; w .-= η .* g ./ (sqrt.(A) .+ ϵ), A starting at ϵ.  On
+    embedding tables only the rows a batch touches change (an untouched row has g = 0)."""
+
+    def _init_state(self, table):
+        return torch.full(table.shape, self.eps, dtype=torch.float32, device=table.device)
+
+
+class RowwiseADAGrad(_AdagradBase):
+    """Row-wise Adagrad: one fp32 accumulator per table row, m[r] += mean_c(g[r][c]^2);
+    w[r] .-= η .* g[r] ./ (sqrt(m[r]) + ϵ), m starting at 0."""
+    rowwise = True
+
+    def _init_state(self, table):
+        return torch.zeros((table.shape[0],), dtype=torch.float32, device=table.device)
+
+
 class SparseEmbeddingUpdate:
     """SparseEmbeddingUpdate{Static{D}}(delta, indices): the gradient of one table.
 
@@ -213,8 +277,13 @@ def update_(opt, tables, grads, indexers=None, *, num_splits=8, nthreads=12, ind
     index_base = 1 if index_base is None else int(index_base)
     if isinstance(tables, HipTables):
         tables = tables.ts
-    if not isinstance(opt, Descent):
-        raise TypeError("update_ implements Descent (plain SGD), the optimizer DLRM.jl trains with")
+    if not isinstance(opt, (Descent, _AdagradBase)):
+        raise TypeError("update_ implements Descent (plain SGD, the optimizer DLRM.jl trains with), ADAGrad and "
+                        "RowwiseADAGrad")
+    adagrad = isinstance(opt, _AdagradBase)
+    if adagrad and not deterministic:
+        raise ValueError("update_ with an Adagrad optimizer is deterministic only: an atomic add never holds the "
+                         "row's whole gradient sum, which the rule squares")
     ts = as_table_set(tables)
     if len(grads) != len(ts):
         raise ValueError(f"{len(grads)} gradients for {len(ts)} tables")
@@ -243,9 +312,15 @@ def update_(opt, tables, grads, indexers=None, *, num_splits=8, nthreads=12, ind
     else:
         flags |= _lib.UPDATE_ATOMIC
     ctx = ts.ctx
-    ctx.check(ctx.lib.dlrm_sgd_update(ctx.bind(), ts.handle, ix.handle if ix is not None else None, flags,
-                                      ptr(idx.data), idx.itype, idx.stride, index_base, idx.B, idx.L, ptr(grad),
-                                      dtype_code(grad.dtype), grad.stride(0), g0.grad_offset, opt.eta))
+    if adagrad:
+        ctx.check(ctx.lib.dlrm_adagrad_update(ctx.bind(), ts.handle, opt.handle_of(ts), ix.handle, flags, ptr(idx.data),
+                                              idx.itype, idx.stride, index_base, idx.B, idx.L, ptr(grad),
+                                              dtype_code(grad.dtype), grad.stride(0), g0.grad_offset, opt.eta,
+                                              opt.eps))
+    else:
+        ctx.check(ctx.lib.dlrm_sgd_update(ctx.bind(), ts.handle, ix.handle if ix is not None else None, flags,
+                                          ptr(idx.data), idx.itype, idx.stride, index_base, idx.B, idx.L, ptr(grad),
+                                          dtype_code(grad.dtype), grad.stride(0), g0.grad_offset, opt.eta))
     if check_bounds or check_bounds is None:
         ctx.check_bounds()
     return tables

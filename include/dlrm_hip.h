@@ -316,6 +316,50 @@ int dlrm_sgd_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_indexer* indexer, u
                     const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset,
                     float lr);
 
+/* ---- sparse Adagrad: update!(ADAGrad(lr, eps), tables, grads, indexers) and its row-wise form.
+ * No reference counterpart in DLRM.jl's own training loop (it trains with Descent); the
+ * reference's update! is generic over the Flux optimiser (src/model/embedding_update.jl:136).
+ *
+ * For a table row r touched by the batch, G[c] = sum of grad[b][grad_offset + t*dim + c] over the
+ * positions that hit r, summed in fp32 in exactly the order dlrm_sgd_update uses for the same
+ * indexer.  Then
+ *   element-wise (rowwise = 0; Flux.ADAGrad(lr, eps); dense and sparse agree: an untouched row
+ *   has G = 0):
+ *       A[r][c] += G[c]^2
+ *       w[r][c] -= lr * G[c] / (sqrt(A[r][c]) + eps)
+ *     state: fp32 [nrows][dim] per table, caller-owned device memory; Flux initialises it to eps
+ *     and so do the Python and Julia wrappers.
+ *   row-wise (rowwise = 1):
+ *       m[r]    += (1/dim) * sum_c G[c]^2
+ *       w[r][c] -= lr * G[c] / (sqrt(m[r]) + eps)
+ *     state: fp32 [nrows] per table, initialised to 0.  The sum over c runs in a fixed order per
+ *     kernel path (a lane's elements in element order, then an xor butterfly over the lanes that
+ *     hold the row, then the waves in wave order), so it is reproducible.
+ * All arithmetic is fp32; bf16 tables are read and stored through the same conversions as
+ * dlrm_sgd_update's; the state is always fp32.  Each touched row's weights and state are written
+ * exactly once, untouched rows keep their bits (weights and state), and the result is bitwise
+ * reproducible from run to run.  When the context's bounds flag (or a prepared build's) is set,
+ * neither tables nor state are written, as in dlrm_sgd_update.
+ *
+ * dlrm_adagrad_create uploads the per-table state pointers once (state[t] non-NULL for every
+ * table with rows; 16-B aligned pointers let the element-wise rule use the vector kernels).
+ * dlrm_adagrad_update: DLRM_UPDATE_PREBUILT is honoured; DLRM_UPDATE_ATOMIC returns
+ * DLRM_E_UNSUPPORTED (an atomic add cannot square a sum it never holds).  An indexer in state
+ * DLRM_IX_SINGLES_DONE returns DLRM_E_STATE: a split backward has already stepped the once-hit
+ * rows with Descent and its dt lacks their rows.  A split indexer whose singles are not done is
+ * taken whole, once-hit rows included.  Launches neither allocate nor synchronise beyond what
+ * dlrm_sgd_update does (partial rows for dim > 256 on first use), so the call is graph-capturable.
+ * dlrm_adagrad_destroy of NULL returns 0. */
+typedef struct dlrm_adagrad dlrm_adagrad; /* per-table state pointers on the device + kind */
+int dlrm_adagrad_create(dlrm_ctx* ctx, const dlrm_tables* tables, int rowwise,
+                        float* const* state, dlrm_adagrad** out);
+int dlrm_adagrad_destroy(dlrm_adagrad* opt);
+int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagrad* opt, dlrm_indexer* indexer,
+                        unsigned flags, const void* indices, int itype, int64_t table_stride,
+                        int index_base, int batch, int lookups,
+                        const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset,
+                        float lr, float eps);
+
 /* ---- training step: fused forms of the four operators --------------------------------
  * One train! iteration of the sparse half of the model (src/train/train.jl:215-227 and
  * custom_update! :283-290) on one-hot lookups, as two launching calls with the tables
