@@ -152,7 +152,15 @@ int dlrm_scatter_rows(dlrm_ctx* ctx, int esize, int num_tables, int batch, int d
 /* (dot::DotInteraction)(x, ys): copies x[b][0:d] into ys[b][0:d] (fast_vcat), views
  * ys[b][0:F*d] as T_b = [F][d], and writes
  *   out[b] = [ x_b | Z[i][j] for i = 1..F-1, j = 0..i-1 | 0 * padding ],  Z = T_b T_b^T
- * dtype applies to x, ys and out (bf16 in, fp32 accumulate, bf16 out). */
+ * dtype applies to x, ys and out (bf16 in, fp32 accumulate, bf16 out).
+ * Padding: the `padding` columns after the pairs are written as zeros (all-zero bits) by every
+ * forward (this one, dlrm_lookup_interact_fwd, dlrm_step_fwd), and a row is written in columns
+ * [0, d + F(F-1)/2 + padding) only: out_ld may be larger and the rest of the row keeps its bytes.
+ * ys is written in columns [0, d) only.  The backwards read dout[b][0 : d + F(F-1)/2] and never its
+ * padding columns.  Leading dimensions and base pointers need no alignment (rows that are not 16-B
+ * aligned take slower kernels with the same results) except where an entry point says otherwise; a
+ * leading dimension smaller than its row, or a negative padding, is DLRM_E_ARG and nothing is
+ * launched. */
 int dlrm_interact_fwd(dlrm_ctx* ctx, int dtype, int d, int num_features, int batch,
                       const void* x, int64_t x_ld, void* ys, int64_t ys_ld,
                       void* out, int64_t out_ld, int padding);
@@ -378,7 +386,8 @@ int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagrad* opt, d
  *   bit-identical to dlrm_sgd_update's result: a once-hit row gets w = fmaf(-lr, g, w) inside
  *   the backward (no other sample reads it), so its dt row is never written or read back;
  *   dt holds only the rows the apply launch reads (x rows and rows of repeated table rows).
- *   dx and dt must be 16-B aligned with leading dimensions divisible by 4.
+ *   dx and dt must be 16-B aligned with leading dimensions divisible by 4 (DLRM_E_ARG otherwise,
+ *   with no table row, dx or dt written; the indexer stays valid for an aligned call).
  *   flags: 0 runs both launches; DLRM_STEP_BWD_ONLY then DLRM_STEP_APPLY_ONLY run them one at a
  *   time (e.g. the apply on another stream, or timed alone). */
 #define DLRM_STEP_BWD_ONLY 1u   /* the backward launch only (dx, dt, once-hit rows)       */

@@ -16,6 +16,11 @@ Bounds (derived, not measured; u = 2^-24):
   bf16 tables:        the weight bounds plus 2^-8 |w_ref| (one bf16 rounding); state bounds as is.
 Each step is checked on its own: the reference of the second step starts from the first step's
 GPU result (weights and state), so the one-step bounds hold for it too.
+
+bf16 gradients are k/64 with |k| <= 256 (exact in bf16's 8 significant bits), so G stays exact and
+the same bounds apply unchanged.  A displaced gradient (grad_offset = 13 in a buffer whose base is
+one element past a 16-B boundary: the scalar apply kernels) lives in a guard band of NaNs, which
+must neither be read nor written.
 """
 import ctypes
 
@@ -23,7 +28,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import rand_indices, rand_tables
+from helpers import banded, rand_indices, rand_tables
 
 pytestmark = pytest.mark.gpu
 
@@ -38,8 +43,8 @@ def _tables(rng, rows, D, gpu, dtype=torch.float32):
     return [t.to(gpu) for t in tabs]
 
 
-def _exact_grad(rng, B, width):
-    return (rng.integers(-512, 513, size=(B, width)) / 64.0).astype(np.float32)
+def _exact_grad(rng, B, width, kmax=512):
+    return (rng.integers(-kmax, kmax + 1, size=(B, width)) / 64.0).astype(np.float32)
 
 
 def _dense_G(idx_t, grad_t, nrows, L):
@@ -58,12 +63,26 @@ def _bits(t):
     return t.view(torch.int16).numpy() if t.dtype == torch.bfloat16 else t.view(torch.int32).numpy()
 
 
-def _update(pkg, opt, ts, idx_np, grad_np, gpu, B, L, indexer=None, prebuilt=False):
+DISPLACED_OFFSET = 13
+
+
+def _update(pkg, opt, ts, idx_np, grad_np, gpu, B, L, indexer=None, prebuilt=False, grad_dtype=torch.float32,
+            displaced=False):
     p = pkg.PackedIndices(torch.from_numpy(idx_np).to(torch.int32).to(gpu).reshape(len(idx_np), B, L))
-    g = torch.from_numpy(grad_np).to(gpu)
+    g = torch.from_numpy(grad_np).to(gpu).to(grad_dtype)
+    assert np.array_equal(_f32(g), grad_np)  # (exact in grad_dtype)
+    off, band = 0, None
+    if displaced:  # columns [0, 13) and everything around the rows: NaN
+        off = DISPLACED_OFFSET
+        band = banded((B, off + g.shape[1]), grad_dtype, off + g.shape[1], 1, gpu)
+        band.view[:, off:].copy_(g)
+        band.snapshot()
+        g = band.view
     if indexer is not None and prebuilt:
         assert indexer.prepare(ts, p, index_base=0)
-    pkg.update_(opt, ts, pkg.maplookup_pullback(0, ts, p, g), indexer, index_base=0, prebuilt=prebuilt)
+    pkg.update_(opt, ts, pkg.maplookup_pullback(off, ts, p, g), indexer, index_base=0, prebuilt=prebuilt)
+    if band is not None:
+        band.check(0, what="grad")
     return p
 
 
@@ -98,7 +117,8 @@ def _check_step(rowwise, D, before_w, before_s, after_w, after_s, G, touched, bf
     assert t.any()
 
 
-def _run_and_check(pkg, gpu, rowwise, D, dtype=torch.float32, rows=ROWS, B=B0, L=1, steps=2, seed=0, prepare=False):
+def _run_and_check(pkg, gpu, rowwise, D, dtype=torch.float32, rows=ROWS, B=B0, L=1, steps=2, seed=0, prepare=False,
+                   grad_dtype=torch.float32, displaced=False):
     rng = np.random.default_rng(1000 * D + seed + (7 if rowwise else 0))
     T = len(rows)
     ts = pkg.EmbeddingTableSet(_tables(rng, rows, D, gpu, dtype))
@@ -107,10 +127,10 @@ def _run_and_check(pkg, gpu, rowwise, D, dtype=torch.float32, rows=ROWS, B=B0, L
     ix = pkg.SparseIndexer(T, B * L, gpu) if prepare else None
     for _ in range(steps):
         idx = rand_indices(rng, rows, B, L)
-        grad = _exact_grad(rng, B, T * D)
+        grad = _exact_grad(rng, B, T * D, 256 if grad_dtype == torch.bfloat16 else 512)
         w0 = [t.data.clone() for t in ts]
         s0 = [s.clone() for s in state]
-        _update(pkg, opt, ts, idx, grad, gpu, B, L, ix, prebuilt=prepare)
+        _update(pkg, opt, ts, idx, grad, gpu, B, L, ix, prebuilt=prepare, grad_dtype=grad_dtype, displaced=displaced)
         for t in range(T):
             G = _dense_G(idx[t], grad[:, t * D:(t + 1) * D], rows[t], L)
             touched = np.zeros(rows[t], dtype=bool)
@@ -137,6 +157,26 @@ def test_rowwise_against_float64_formula(pkg, gpu, D):
 @pytest.mark.parametrize("rowwise", [False, True])
 def test_bf16_tables_fp32_gradients(pkg, gpu, rowwise):
     _run_and_check(pkg, gpu, rowwise, 128, dtype=torch.bfloat16)
+
+
+@pytest.mark.parametrize("D", [16, 128])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["tf32", "tbf16"])
+@pytest.mark.parametrize("rowwise", [False, True])
+def test_bf16_gradients(pkg, gpu, rowwise, dtype, D):
+    """grad_dtype = bf16 into fp32 and bf16 tables: the GT = bf16 instantiations of the vector apply
+    (chunks, hot slices) for both rules."""
+    _run_and_check(pkg, gpu, rowwise, D, dtype=dtype, seed=4, grad_dtype=torch.bfloat16)
+
+
+@pytest.mark.parametrize("grad_dtype", [torch.float32, torch.bfloat16], ids=["gf32", "gbf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["tf32", "tbf16"])
+@pytest.mark.parametrize("prepare", [False, True], ids=["built", "prepared"])
+@pytest.mark.parametrize("rowwise", [False, True])
+def test_displaced_unaligned_gradient(pkg, gpu, rowwise, prepare, dtype, grad_dtype):
+    """grad_offset = 13 from a base one element past a 16-B boundary: the scalar apply kernels
+    (chunks, hot; with a prepared build also the once-hit singles), which must read nothing before
+    grad_offset or outside the rows."""
+    _run_and_check(pkg, gpu, rowwise, 16, dtype=dtype, seed=5, prepare=prepare, grad_dtype=grad_dtype, displaced=True)
 
 
 @pytest.mark.parametrize("rowwise", [False, True])

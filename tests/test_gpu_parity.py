@@ -9,28 +9,10 @@ import pytest
 import torch
 
 import oracle
-from helpers import assert_close, julia_isapprox, rand_indices, rand_tables
+from helpers import (_assert_segments, _dt_written_mask, assert_close, dev_tables, julia_isapprox, rand_indices,
+                     rand_tables, to_np_bits, to_np_f32)
 
 pytestmark = pytest.mark.gpu
-
-
-def dev_tables(tables, device, dtype=torch.float32):
-    if dtype == torch.bfloat16:
-        return [torch.from_numpy(oracle.bf16_to_f32(oracle.f32_to_bf16(t))).to(device).to(torch.bfloat16)
-                for t in tables]
-    return [torch.from_numpy(t).to(device) for t in tables]
-
-
-def to_np_bits(t):
-    """device tensor -> numpy (bf16 as uint16 bit patterns, fp32 as float32)"""
-    t = t.detach().cpu()
-    if t.dtype == torch.bfloat16:
-        return t.view(torch.int16).numpy().view(np.uint16)
-    return t.numpy()
-
-
-def to_np_f32(t):
-    return t.detach().float().cpu().numpy()
 
 
 # ------------------------------------------------------------------ golden (HDF5) vectors
@@ -501,22 +483,6 @@ def test_indexer_footprint_compact(pkg, gpu):
     _assert_segments(ix, idx, N)
 
 
-def _assert_segments(ix, idx, N):
-    """One segment per distinct row (segment order unspecified), holding exactly that row's
-    positions in ascending order (vectorised: large-N builds have ~N segments per table)."""
-    for t in range(idx.shape[0]):
-        got_rows, pos, seg = ix.segments(t)
-        got_rows, pos, seg = np.asarray(got_rows, dtype=np.int64), np.asarray(pos), np.asarray(seg)
-        order = np.argsort(idx[t], kind="stable")
-        urows, starts, counts = np.unique(idx[t][order], return_index=True, return_counts=True)
-        assert len(got_rows) == len(urows) and seg[-1] == N and len(seg) == len(urows) + 1
-        assert np.array_equal(np.sort(got_rows), urows)
-        k = np.searchsorted(urows, got_rows)
-        assert np.array_equal(np.diff(seg), counts[k])
-        want = order[np.repeat(starts[k] - seg[:-1], counts[k]) + np.arange(N)]
-        assert np.array_equal(pos, want)
-
-
 @pytest.mark.parametrize("rows,B,zipf", [([3, 4, 10, 1000, 5_000_000], 2048, None), ([300, 100000, 5_000_000], 2048, 1.1),
                                          ([256, 257, 70000], 2048, None), ([0x10000, 0x1000000], 1500, None),
                                          ([2], 1, None), ("kaggle", 2048, None), ([100000, 3], 5000, None),
@@ -734,19 +700,6 @@ def test_hotpath_step_matches_operator_sequence(pkg, gpu, overlap, materialize):
     assert np.array_equal(to_np_f32(hp.dt)[m], to_np_f32(dy)[m])
     for a, b in zip(hp.ts, ts2):
         assert np.array_equal(to_np_f32(a.data), to_np_f32(b.data))
-
-
-def _dt_written_mask(idx, D):
-    """[B][F*D] bool: the dt entries dlrm_step_bwd must write -- the rows of positions whose table
-    row is hit more than once (once-hit rows are updated in place; the x rows' gradient is dx, and
-    the split step backward leaves dt's x rows unwritten)."""
-    T, B = idx.shape
-    keep = np.ones((B, T + 1), dtype=bool)
-    keep[:, 0] = False
-    for t in range(T):
-        _, inv, cnt = np.unique(idx[t], return_inverse=True, return_counts=True)
-        keep[:, t + 1] = cnt[inv] > 1
-    return np.repeat(keep, D, axis=1)
 
 
 @pytest.mark.parametrize("rows,D,B,zipf,dtype", [
