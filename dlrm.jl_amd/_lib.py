@@ -95,6 +95,10 @@ SIGNATURES = {
     "dlrm_adagrad_destroy": (_i32, [_vp]),
     "dlrm_adagrad_update": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _i64, _i64,
                                    _f32, _f32]),
+    "dlrm_split_sgd_create": (_i32, [_vp, _vp, _pp, _pp]),
+    "dlrm_split_sgd_destroy": (_i32, [_vp]),
+    "dlrm_split_sgd_update": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _i64, _i64,
+                                     _f32]),
     "dlrm_bce_head":(_i32, [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dlrm_relu_bwd_bias_workspace": (_i32, [_i32, _i32, _pi64, _pi64]),
     "dlrm_relu_bwd_bias": (_i32, [_vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),

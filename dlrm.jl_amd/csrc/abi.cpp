@@ -54,6 +54,14 @@ struct dlrm_adagrad {
     std::vector<float*> h_state;
 };
 
+// Low halves of one split-bf16 table set: the caller's per-table uint16 pointers, uploaded once
+struct dlrm_split_sgd {
+    int T = 0, D = 0;
+    bool aligned16 = true;    // every low-half pointer is 16-B aligned
+    uint16_t** d_lo = nullptr;
+    std::vector<uint16_t*> h_lo;
+};
+
 struct dlrm_indexer {
     dlrm_ctx* ctx = nullptr;
     int T = 0;
@@ -1069,6 +1077,80 @@ int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_i
     return launch_adagrad_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_state, tb->T, tb->D,
                                 tb->dtype, lookups, (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr,
                                 eps, sa);
+}
+
+// ------------------------------------------------------------------ split-bf16 tables
+int dlrm_split_sgd_create(dlrm_ctx* ctx, const dlrm_tables* tb, uint16_t* const* lo, dlrm_split_sgd** out) {
+    CHECK_ARG(ctx && tb && out, "dlrm_split_sgd_create: null argument");
+    *out = nullptr;
+    CHECK_ARG(tb->dtype == DLRM_BF16, "dlrm_split_sgd_create: split tables are bf16 (the high halves)");
+    CHECK_ARG(tb->T == 0 || lo, "dlrm_split_sgd_create: null low halves");
+    for (int t = 0; t < tb->T; ++t)
+        CHECK_ARG(lo[t] || tb->h_desc[t].nrows == 0, "dlrm_split_sgd_create: table %d has no low half", t);
+    dlrm_split_sgd* op = new (std::nothrow) dlrm_split_sgd();
+    if (!op) return DLRM_E_NOMEM;
+    op->T = tb->T;
+    op->D = tb->D;
+    op->h_lo.assign(lo, lo + tb->T);
+    // (rows of D uint16 from a 16-B aligned base: aligned when D % 8 == 0, which the vector kernels need anyway)
+    for (int t = 0; t < tb->T; ++t)
+        if ((uintptr_t)lo[t] % 16) op->aligned16 = false;
+    int rc = hip_set(ctx);
+    if (rc == DLRM_OK && tb->T > 0) {
+        rc = ctx_hip(ctx, hipMalloc((void**)&op->d_lo, sizeof(uint16_t*) * tb->T), "hipMalloc(split low halves)");
+        if (rc == DLRM_OK)
+            rc = ctx_hip(ctx, hipMemcpy(op->d_lo, op->h_lo.data(), sizeof(uint16_t*) * tb->T, hipMemcpyHostToDevice),
+                         "hipMemcpy(split low halves)");
+    }
+    if (rc != DLRM_OK) {
+        if (op->d_lo) (void)hipFree(op->d_lo);
+        delete op;
+        return rc;
+    }
+    *out = op;
+    return DLRM_OK;
+}
+
+int dlrm_split_sgd_destroy(dlrm_split_sgd* op) {
+    if (!op) return DLRM_OK;
+    if (op->d_lo) (void)hipFree(op->d_lo);
+    delete op;
+    return DLRM_OK;
+}
+
+int dlrm_split_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dlrm_indexer* ix, unsigned flags,
+                          const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
+                          const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset, float lr) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_split_sgd_update: null ctx/tables/optimizer/indexer");
+    int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, lookups);
+    if (rc) return rc;
+    CHECK_ARG(tb->dtype == DLRM_BF16, "dlrm_split_sgd_update: split tables are bf16 (the high halves)");
+    CHECK_ARG(op->T == tb->T && op->D == tb->D, "dlrm_split_sgd_update: the low halves were created for %d tables of dim %d",
+              op->T, op->D);
+    CHECK_ARG(grad_dtype == DLRM_F32 || grad_dtype == DLRM_BF16, "dlrm_split_sgd_update: grad dtype %d", grad_dtype);
+    CHECK_ARG(grad_offset >= 0 && grad_ld >= grad_offset + (int64_t)tb->T * tb->D, "dlrm_split_sgd_update: grad_ld too small");
+    CHECK_ARG(batch == 0 || tb->T == 0 || grad, "dlrm_split_sgd_update: null grad");
+    if (flags & DLRM_UPDATE_ATOMIC)  // an atomic add on one half cannot carry into the other
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_split_sgd_update: no atomic mode (a row's two halves are stepped together)");
+    if (flags & DLRM_UPDATE_PREBUILT) {
+        if (!built_from(ix, indices, itype, table_stride, index_base, batch, lookups))
+            return ctx_fail(ctx, DLRM_E_STATE, "dlrm_split_sgd_update: indexer was not built from these indices");
+        // a split backward wrote those rows' high halves with a rounded bf16 step and left their dt rows unwritten
+        if (ix->singles_done)
+            return ctx_fail(ctx, DLRM_E_STATE,
+                            "dlrm_split_sgd_update: a split backward (dlrm_step_bwd) already stepped this build's "
+                            "once-hit rows with a rounded bf16 Descent");
+    } else {
+        rc = dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, lookups);
+        if (rc) return rc;
+    }
+    rc = ensure_partials(ctx, ix, tb->D);
+    if (rc) return rc;
+    // (a split indexer is taken whole: its once-hit positions as singles items)
+    const SinglesArgs sa{ix->split ? ix->dev.single : nullptr, indices, itype, table_stride, index_base,
+                         batch * lookups};
+    return launch_split_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_lo, tb->T, tb->D, lookups,
+                                  (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr, sa);
 }
 
 // ----------------------------------------------------------------------- training step

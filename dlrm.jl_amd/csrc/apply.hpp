@@ -51,6 +51,10 @@ struct ApplyGeom {
 template <typename G, int KSTATE>
 constexpr int singles_ppg() {
     constexpr int DIV = G::NE == 4 && (KSTATE == 1 || G::VPL == 1) ? 4 : 2;
+    // The split rule's halves wait as bits, a row's two halves in the registers of Descent's fp32 row, so
+    // it keeps SPPG -- but for fp32 gradient rows of 16 vectors (D = 64), whose MODE 1 kernel spilt 4
+    // registers at SPPG = 8: half as many there.
+    if (KSTATE == 3) return G::NE == 4 && G::LPR == 16 ? G::SPPG / 2 : G::SPPG;
     return KSTATE == 0 ? G::SPPG : (G::SPPG >= DIV ? G::SPPG / DIV : 1);
 }
 
@@ -93,29 +97,82 @@ __device__ __forceinline__ void add_vec(float* acc, const typename Vec<GT>::type
 //   Descent         w = fmaf(-lr, G, w)
 //   Adagrad         A += G^2 (element-wise, fp32 [nrows][D]);   w -= lr G / (sqrt(A) + eps)
 //   RowwiseAdagrad  m += (1/D) sum_c G[c]^2 (fp32 [nrows]);      w -= lr G / (sqrt(m) + eps)
-// kState: 0 none, 1 a state row per table row, 2 a state word per table row.  The state is loaded
+// kState: 0 none, 1 a state row per table row, 2 a state word per table row, 3 a row of low halves per
+// table row.  The state is loaded
 // where the table row is (beside the grad rows: these items are bound by dependent round trips)
 // and written once, with the row.  The row-wise sum of squares has a fixed order per site: a lane's
 // elements in element order, then an xor butterfly over the lanes holding the row (every level one
 // commutative add, so every lane ends with the same bits), then (slices of D > 256) the waves in
 // wave order.
+//   SplitDescent    W = bits(hi << 16 | lo);  W' = fmaf(-lr, G, W);  hi' = bits(W') >> 16, lo' = bits(W') & 0xffff
+//                   (kState 3: hi = the bf16 table's element, lo = a uint16 [nrows][D] state row: the table
+//                   holds the truncated high half of an fp32 master weight, the step is Descent's on fp32)
 struct Descent {
     float lr;
+    typedef float State;
     static constexpr int kState = 0;
     __device__ __forceinline__ float* base(int) const { return nullptr; }
 };
 struct Adagrad {
     float lr, eps;
     float* const* state;  // [T] device pointers, fp32 [nrows][D]
+    typedef float State;
     static constexpr int kState = 1;
     __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
 };
 struct RowwiseAdagrad {
     float lr, eps;
     float* const* state;  // [T] device pointers, fp32 [nrows]
+    typedef float State;
     static constexpr int kState = 2;
     __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
 };
+struct SplitDescent {
+    float lr;
+    uint16_t* const* lo;  // [T] device pointers, uint16 [nrows][D]: the low halves
+    typedef uint16_t State;
+    static constexpr int kState = 3;
+    __device__ __forceinline__ uint16_t* base(int t) const { return ldg<uint16_t*>(lo + t); }
+};
+
+// N (4 or 8) consecutive 16-bit halves of a split row, kept as raw bits in one 8-B or 16-B vector (half
+// the registers of their fp32 values while they wait beside the grad rows).
+typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
+template <int N> struct Halves;
+template <> struct Halves<4> { typedef u16x4 type; };
+template <> struct Halves<8> { typedef u16x8 type; };
+template <int N>
+__device__ __forceinline__ typename Halves<N>::type load_halves(const uint16_t* p) {
+    return ldg<typename Halves<N>::type>(p);
+}
+// the split step on N elements: the fp32 master weight from its halves, Descent's fma, the halves of
+// the result by truncation.  A NaN result also sets the high half's quiet bit (as f32_to_bf16 does), so
+// the bf16 table alone still reads NaN when the payload sits in the low half.
+__device__ __forceinline__ void split_step1(float lr, float g, uint16_t& hi, uint16_t& lo) {
+    const float w = __builtin_fmaf(-lr, g, __uint_as_float(((uint32_t)hi << 16) | (uint32_t)lo));
+    const uint32_t u = __float_as_uint(w);
+    hi = (uint16_t)((u >> 16) | (w != w ? 0x40u : 0u));
+    lo = (uint16_t)(u & 0xffffu);
+}
+template <int N>
+__device__ __forceinline__ void split_step(float lr, const float* g, typename Halves<N>::type& hi,
+                                           typename Halves<N>::type& lo) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+        uint16_t h = hi[e], l = lo[e];
+        split_step1(lr, g[e], h, l);
+        hi[e] = h;
+        lo[e] = l;
+    }
+}
+// ... and its write: both halves of the N elements at `hrow` / `lrow`, one vector store each
+template <int N>
+__device__ __forceinline__ void split_write(float lr, const float* g, typename Halves<N>::type& hi,
+                                            typename Halves<N>::type& lo, uint16_t* hrow, uint16_t* lrow) {
+    split_step<N>(lr, g, hi, lo);
+    stg<typename Halves<N>::type>(hrow, hi);
+    stg<typename Halves<N>::type>(lrow, lo);
+}
 
 // The element-wise rule's sqrt and reciprocal: the hardware's (v_sqrt_f32, v_rcp_f32: 1 ulp each)
 // instead of the correctly rounded expansions (~25 instructions and 6 live registers per element,
@@ -151,7 +208,7 @@ __device__ __forceinline__ float rowwise_scale(float lr, float eps, float m) { r
 // ---- a chunk, by one lane group (lane v of LPR; gl0 = the group's first lane in the wave)
 template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_chunk(const int32_t* __restrict__ perm, const int4& a, const int4& b,
-                                          TT* __restrict__ table, float* __restrict__ st,
+                                          TT* __restrict__ table, typename R::State* __restrict__ st,
                                           const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L,
                                           const R& rule, int v, int gl0) {
     typedef ApplyGeom<GT, VPR> G;
@@ -160,8 +217,18 @@ __device__ __forceinline__ void run_chunk(const int32_t* __restrict__ perm, cons
     const int beg = a.x, len = a.y - a.x;
     TT* row = table + (int64_t)(uint32_t)a.z * D;
     float tv[G::VPL][NE];
+    typename Halves<NE>::type hv[G::VPL], lv[G::VPL];  // split: the row's halves, as bits
+    if constexpr (R::kState == 3) {
+        static_assert(sizeof(TT) == 2, "split rows live in bf16 tables");
 #pragma unroll
-    for (int j = 0; j < G::VPL; ++j) load_row<TT, NE>(row, (v + j * 64) * NE, tv[j]);  // beside the grad rows
+        for (int j = 0; j < G::VPL; ++j) {
+            hv[j] = load_halves<NE>((const uint16_t*)row + (v + j * 64) * NE);
+            lv[j] = load_halves<NE>(st + (int64_t)(uint32_t)a.z * D + (v + j * 64) * NE);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < G::VPL; ++j) load_row<TT, NE>(row, (v + j * 64) * NE, tv[j]);  // beside the grad rows
+    }
     float sv[R::kState == 1 ? G::VPL : 1][NE];  // Adagrad: the state row
     float m = 0.0f;                             // row-wise: the state word
     if constexpr (R::kState == 1) {
@@ -213,6 +280,13 @@ __device__ __forceinline__ void run_chunk(const int32_t* __restrict__ perm, cons
         }
         return;
     }
+    if constexpr (R::kState == 3) {
+#pragma unroll
+        for (int j = 0; j < G::VPL; ++j)
+            split_write<NE>(rule.lr, acc[j], hv[j], lv[j], (uint16_t*)row + (v + j * 64) * NE,
+                            st + (int64_t)(uint32_t)a.z * D + (v + j * 64) * NE);
+        return;
+    }
     float lr = rule.lr;
     if constexpr (R::kState == 2) {
         float ss = 0.0f;
@@ -245,7 +319,7 @@ struct SinglesArgs {
 };
 template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_singles(const SinglesArgs& sa, int64_t cap, TT* __restrict__ table,
-                                            float* __restrict__ st, int64_t nrows, int t, int p0,
+                                            typename R::State* __restrict__ st, int64_t nrows, int t, int p0,
                                             const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L,
                                             const R& rule, int v, int gl0) {
     typedef ApplyGeom<GT, VPR> G;
@@ -265,6 +339,7 @@ __device__ __forceinline__ void run_singles(const SinglesArgs& sa, int64_t cap, 
     float tv[PPG][G::VPL][NE];
     float sv[R::kState == 1 ? PPG : 1][R::kState == 1 ? G::VPL : 1][NE];  // Adagrad: the state rows
     float m[PPG];                                                         // row-wise: the state words
+    typename Halves<NE>::type hv[PPG][G::VPL], lv[PPG][G::VPL];           // split: the rows' halves, as bits
 #pragma unroll
     for (int u = 0; u < PPG; ++u) {
         ru[u] = (uint32_t)__shfl((int)pr[u / LPR], gl0 + u % LPR, 64);
@@ -272,7 +347,12 @@ __device__ __forceinline__ void run_singles(const SinglesArgs& sa, int64_t cap, 
 #pragma unroll
             for (int j = 0; j < G::VPL; ++j) {
                 gv[u][j] = grad_vec<GT>(gbase, grad_ld, L, p0 + u, v + j * 64);
-                load_row<TT, NE>(table + (int64_t)ru[u] * D, (v + j * 64) * NE, tv[u][j]);
+                if constexpr (R::kState == 3) {
+                    hv[u][j] = load_halves<NE>((const uint16_t*)table + (int64_t)ru[u] * D + (v + j * 64) * NE);
+                    lv[u][j] = load_halves<NE>(st + (int64_t)ru[u] * D + (v + j * 64) * NE);
+                } else {
+                    load_row<TT, NE>(table + (int64_t)ru[u] * D, (v + j * 64) * NE, tv[u][j]);
+                }
                 if constexpr (R::kState == 1) load_row<float, NE>(st + (int64_t)ru[u] * D, (v + j * 64) * NE, sv[u][j]);
             }
             if constexpr (R::kState == 2) m[u] = ldg<float>(st + ru[u]);
@@ -302,14 +382,20 @@ __device__ __forceinline__ void run_singles(const SinglesArgs& sa, int64_t cap, 
                 }
 #pragma unroll
                 for (int j = 0; j < G::VPL; ++j) {
-                    if constexpr (R::kState == 1) {
-                        adagrad_step<NE>(rule.lr, rule.eps, g[j], sv[u][j], tv[u][j]);
-                        store_row<float, NE>(st + (int64_t)ru[u] * D, (v + j * 64) * NE, sv[u][j]);
+                    if constexpr (R::kState == 3) {
+                        split_write<NE>(rule.lr, g[j], hv[u][j], lv[u][j],
+                                        (uint16_t*)table + (int64_t)ru[u] * D + (v + j * 64) * NE,
+                                        st + (int64_t)ru[u] * D + (v + j * 64) * NE);
                     } else {
+                        if constexpr (R::kState == 1) {
+                            adagrad_step<NE>(rule.lr, rule.eps, g[j], sv[u][j], tv[u][j]);
+                            store_row<float, NE>(st + (int64_t)ru[u] * D, (v + j * 64) * NE, sv[u][j]);
+                        } else {
 #pragma unroll
-                        for (int e = 0; e < NE; ++e) tv[u][j][e] = __builtin_fmaf(-lr, g[j][e], tv[u][j][e]);
+                            for (int e = 0; e < NE; ++e) tv[u][j][e] = __builtin_fmaf(-lr, g[j][e], tv[u][j][e]);
+                        }
+                        store_row<TT, NE>(table + (int64_t)ru[u] * D, (v + j * 64) * NE, tv[u][j]);
                     }
-                    store_row<TT, NE>(table + (int64_t)ru[u] * D, (v + j * 64) * NE, tv[u][j]);
                 }
             }
         return;
@@ -357,13 +443,19 @@ struct SliceLds {
 // The row's write by the first D/4 threads (G = the thread's four sums, rw its four weights, sw its
 // four accumulators or the row's word); every thread of the workgroup calls it.  wsum_read: other
 // waves may still be reading sm.wsum (the row-wise wave totals of D > 256 reuse it).
+// (The split rule: rh / rl = the thread's four high and low halves, as bits, in place of rw / sw.)
 template <typename TT, typename R, int D>
-__device__ __forceinline__ void slice_write(const R& rule, const f32x4& G, float* rw, float* sw, TT* __restrict__ row,
-                                            float* __restrict__ srow, SliceLds<D>& sm, bool wsum_read) {
+__device__ __forceinline__ void slice_write(const R& rule, const f32x4& G, float* rw, float* sw, u16x4& rh, u16x4& rl,
+                                            TT* __restrict__ row, typename R::State* __restrict__ srow, SliceLds<D>& sm,
+                                            bool wsum_read) {
     const int tid = threadIdx.x;
     const bool mine = tid < D / 4;
     const float g[4] = {G[0], G[1], G[2], G[3]};
     float lr = rule.lr;
+    if constexpr (R::kState == 3) {
+        if (mine) split_write<4>(rule.lr, g, rh, rl, (uint16_t*)row + tid * 4, srow + tid * 4);
+        return;
+    }
     if constexpr (R::kState == 1) {
         if (mine) {
             adagrad_step<4>(rule.lr, rule.eps, g, sw, rw);
@@ -398,7 +490,7 @@ __device__ __forceinline__ void slice_write(const R& rule, const f32x4& G, float
 
 template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int len, TT* __restrict__ row,
-                                           float* __restrict__ srow, int ns, float* part_me, const float* part_first,
+                                           typename R::State* __restrict__ srow, int ns, float* part_me, const float* part_first,
                                            int64_t pdim, int32_t* cnt_p, const GT* __restrict__ gbase, int64_t grad_ld,
                                            const FastDiv& L, const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
     typedef ApplyGeom<GT, VPR> G;
@@ -408,7 +500,16 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
     const int g = lane / LPR, v = lane % LPR, gid = w * G::RPW + g;
     // the table row, loaded now (needed only at the end; no other item writes it in this launch)
     float rw[4];
-    if (tid < D / 4) load_row<TT, 4>(row, tid * 4, rw);
+    u16x4 rh = u16x4{0, 0, 0, 0}, rl = u16x4{0, 0, 0, 0};  // split: the row's halves, as bits
+    if constexpr (R::kState == 3) {
+        static_assert(sizeof(TT) == 2, "split rows live in bf16 tables");
+        if (tid < D / 4) {
+            rh = load_halves<4>((const uint16_t*)row + tid * 4);
+            rl = load_halves<4>(srow + tid * 4);
+        }
+    } else {
+        if (tid < D / 4) load_row<TT, 4>(row, tid * 4, rw);
+    }
     float sw[4] = {0.f, 0.f, 0.f, 0.f};  // the state, with the row (written by the segment's last slice only)
     if constexpr (R::kState == 1) {
         if (tid < D / 4) load_row<float, 4>(srow, tid * 4, sw);
@@ -480,7 +581,7 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
                 store_row<TT, 4>(row, tid * 4, rw);
             }
         } else {
-            slice_write<TT, R, D>(rule, sum, rw, sw, row, srow, sm, true);
+            slice_write<TT, R, D>(rule, sum, rw, sw, rh, rl, row, srow, sm, true);
         }
         __syncthreads();  // sm reused by this workgroup's next item
         return;
@@ -525,7 +626,7 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
                     if (k0 + u < ns) s += q[u];
             }
         }
-        slice_write<TT, R, D>(rule, s, rw, sw, row, srow, sm, false);  // (sm.wsum: read before the barriers above)
+        slice_write<TT, R, D>(rule, s, rw, sw, rh, rl, row, srow, sm, false);  // (sm.wsum: read before the barriers above)
         if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();  // sm reused by this workgroup's next item
@@ -533,14 +634,14 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
 
 // ---- a slice of a hot segment located by (virtual table vt, local slice sl): sd = {p0, p1,
 // row, h}; the segment's descriptor ix.hot[vt][h] = {beg, end, row, first slice}
-template <int KSTATE, int D>
-__device__ __forceinline__ float* state_row(float* st, uint32_t r) {
-    return KSTATE == 1 ? st + (int64_t)r * D : (KSTATE == 2 ? st + r : nullptr);
+template <int KSTATE, int D, typename S>
+__device__ __forceinline__ S* state_row(S* st, uint32_t r) {
+    return KSTATE == 1 || KSTATE == 3 ? st + (int64_t)r * D : (KSTATE == 2 ? st + r : nullptr);
 }
 
 template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_slice(const IndexerDev& ix, int vt, int sl, const int4& sd, TT* __restrict__ table,
-                                          float* __restrict__ st, const GT* __restrict__ gbase, int64_t grad_ld,
+                                          typename R::State* __restrict__ st, const GT* __restrict__ gbase, int64_t grad_ld,
                                           const FastDiv& L, const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
     constexpr int D = ApplyGeom<GT, VPR>::D;
     const int64_t off = (int64_t)vt * ix.cap;
@@ -557,7 +658,7 @@ __device__ __forceinline__ void run_slice(const IndexerDev& ix, int vt, int sl, 
 // first slice `first` count over the sub-lists' slices in order (partial row and counter slots)
 template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_slice_rec(const IndexerDev& ix, int k, int first, const int4& r0, const int4& r1,
-                                              TT* __restrict__ table, float* __restrict__ st,
+                                              TT* __restrict__ table, typename R::State* __restrict__ st,
                                               const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L,
                                               const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
     constexpr int D = ApplyGeom<GT, VPR>::D;

@@ -1,7 +1,7 @@
 // apply_kernel.hpp -- the apply launch of update! (sgd_apply_kernel over apply.hpp's work items), its
 // any-D fallback kernels and their launchers, by update rule.  update.hip instantiates Descent
-// (every MODE), adagrad.hip and adagrad_rowwise.hip the Adagrad rules (MODE 0 and 1): one translation
-// unit per rule, so they compile side by side.
+// (every MODE), adagrad.hip and adagrad_rowwise.hip the Adagrad rules, split_sgd.hip the split rule (MODE 0
+// and 1): one translation unit per rule, so they compile side by side.
 #pragma once
 #include "apply.hpp"
 
@@ -45,7 +45,8 @@ static inline int wave_big_kind(const PrepArgs& pa) {
 // workgroups of a build (4 parts each)
 __host__ __device__ __forceinline__ int prep_groups(const PrepArgs& pa) { return (pa.T << pa.ix.vshift) / kWaveParts; }
 
-// R: the update rule (apply.hpp: Descent, Adagrad, RowwiseAdagrad -- the last two in MODE 0 and 1 only).
+// R: the update rule (apply.hpp: Descent, Adagrad, RowwiseAdagrad, SplitDescent -- all but the first in MODE 0
+// and 1 only).
 template <typename TT, typename GT, int VPR, int MODE, typename R = Descent>
 __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev ix, TableDesc* __restrict__ tabs, int T_,
                                                                   int L, const GT* __restrict__ grad, int64_t grad_ld,
@@ -230,10 +231,17 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
 // (two passes over the row's sums: the squares in column order, then the step).
 // The write of column c of row r (kState 2: of the whole row), colsum(c) = the column's gradient sum.
 template <typename TT, typename R, typename F>
-__device__ __forceinline__ void scalar_write(const R& rule, TT* __restrict__ row, float* __restrict__ st, int64_t r, int D,
-                                             int c, F&& colsum) {
+__device__ __forceinline__ void scalar_write(const R& rule, TT* __restrict__ row, typename R::State* __restrict__ st,
+                                             int64_t r, int D, int c, F&& colsum) {
     if constexpr (R::kState == 0) {
         row[c] = from_f32<TT>(__builtin_fmaf(-rule.lr, colsum(c), to_f32(row[c])));
+    } else if constexpr (R::kState == 3) {
+        static_assert(sizeof(TT) == 2, "split rows live in bf16 tables");
+        const float g = colsum(c);
+        uint16_t hi = ldg<uint16_t>(row + c), lo = ldg<uint16_t>(st + r * D + c);
+        split_step1(rule.lr, g, hi, lo);
+        stg<uint16_t>(row + c, hi);
+        stg<uint16_t>(st + r * D + c, lo);
     } else if constexpr (R::kState == 1) {
         const float g = colsum(c);
         float a = st[r * D + c], w = to_f32(row[c]);
@@ -268,7 +276,7 @@ __global__ __launch_bounds__(256) void sgd_chunks_scalar(IndexerDev ix, TableDes
     const int W = R::kState == 2 ? 1 : D;  // threads per row
     const int64_t total = (int64_t)nchunks * W;
     TT* table = (TT*)tabs[t >> ix.vshift].data;
-    float* st = rule.base(t >> ix.vshift);
+    typename R::State* st = rule.base(t >> ix.vshift);
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int cid = (int)(e / W);
         const int4 cd = ix.chunks[2 * (off + cid)];
@@ -292,7 +300,7 @@ __global__ __launch_bounds__(256) void sgd_hot_scalar(IndexerDev ix, TableDesc* 
     const int W = R::kState == 2 ? 1 : D;  // threads per row
     const int64_t total = (int64_t)nhot * W;
     TT* table = (TT*)tabs[t >> ix.vshift].data;
-    float* st = rule.base(t >> ix.vshift);
+    typename R::State* st = rule.base(t >> ix.vshift);
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int h = (int)(e / W);
         const int4 hd = ix.hot[off + h];
@@ -315,7 +323,7 @@ __global__ __launch_bounds__(256) void sgd_singles_scalar(SinglesArgs sa, int64_
     const int W = R::kState == 2 ? 1 : D;  // threads per position
     const int64_t total = (int64_t)sa.N * W;
     TT* table = (TT*)tabs[t].data;
-    float* st = rule.base(t);
+    typename R::State* st = rule.base(t);
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int p = (int)(e / W);
         if (!sa.single[(int64_t)t * cap + p]) continue;
@@ -406,7 +414,8 @@ static bool dispatch_apply(int vpr, hipStream_t s, const IndexerDev& ix, TableDe
 #undef DLRM_CASE
 }
 
-// tabs_aligned16: every table row (and, for the element-wise Adagrad rule, every state row) is 16-B aligned
+// tabs_aligned16: every table row (and, for the element-wise Adagrad and the split rule, every state row) is
+// 16-B aligned
 template <typename R>
 static int launch_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool tabs_aligned16, int T_, int D,
                              int tdtype, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
@@ -423,7 +432,13 @@ static int launch_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tab
     const int64_t slots = (int64_t)T_ * (N + 1);  // (item counts stay in int)
     if (aligned && slots < (1ll << 31)) {
         const int vpr = D * gesz / 16;
-        if (tdtype == DLRM_F32 && gdtype == DLRM_F32)
+        if constexpr (R::kState == 3) {  // (bf16 tables only: the caller checked)
+            if (gdtype == DLRM_F32)
+                done = dispatch_apply<uint16_t, float, R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N, err, sa, pa);
+            else
+                done = dispatch_apply<uint16_t, uint16_t, R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N,
+                                                             err, sa, pa);
+        } else if (tdtype == DLRM_F32 && gdtype == DLRM_F32)
             done = dispatch_apply<float, float, R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N, err, sa, pa);
         else if (tdtype == DLRM_BF16 && gdtype == DLRM_F32)
             done = dispatch_apply<uint16_t, float, R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N, err, sa, pa);
@@ -447,7 +462,10 @@ static int launch_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tab
     if (sa.single)                                                                                                  \
         hipLaunchKernelGGL((sgd_singles_scalar<TT, GT, R>), dim3(gx, T_ >> ix.vshift), dim3(256), 0, s, sa, ix.cap, \
                            tabs, D, L, (const GT*)grad, grad_ld, grad_offset, rule, err);
-        if (tdtype == DLRM_F32 && gdtype == DLRM_F32) { DLRM_SCALAR(float, float) }
+        if constexpr (R::kState == 3) {
+            if (gdtype == DLRM_F32) { DLRM_SCALAR(uint16_t, float) }
+            else { DLRM_SCALAR(uint16_t, uint16_t) }
+        } else if (tdtype == DLRM_F32 && gdtype == DLRM_F32) { DLRM_SCALAR(float, float) }
         else if (tdtype == DLRM_BF16 && gdtype == DLRM_F32) { DLRM_SCALAR(uint16_t, float) }
         else if (tdtype == DLRM_F32 && gdtype == DLRM_BF16) { DLRM_SCALAR(float, uint16_t) }
         else { DLRM_SCALAR(uint16_t, uint16_t) }

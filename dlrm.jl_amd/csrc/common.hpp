@@ -436,6 +436,12 @@ int launch_rowwise_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc*
                                  float* const* state, int T, int D, int tdtype, int L, int64_t N, const void* grad,
                                  int gdtype, int64_t grad_ld, int64_t grad_offset, float lr, float eps,
                                  const SinglesArgs& singles);
+// the same apply with the split rule (apply.hpp SplitDescent) on bf16 tables: lo = the device array of
+// per-table uint16 [nrows][D] low-half pointers.  aligned16: every table row and every low-half row is
+// 16-B aligned.
+int launch_split_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint16_t* const* lo,
+                           int T, int D, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
+                           int64_t grad_offset, float lr, const SinglesArgs& singles);
 int launch_triangular_slice(dlrm_ctx* ctx, int dtype, int sz, int B, const void* z, int64_t z_bs, void* out,
                             int64_t out_ld);
 int launch_triangular_slice_back(dlrm_ctx* ctx, int dtype, int sz, int B, const void* dy, int64_t dy_ld, void* a,

@@ -25,10 +25,11 @@ forward writes only `out` and the backward rebuilds T from x and the gathered ta
 the update that follows -- which saves ys's write and keeps the step's HBM traffic at what
 the math needs.  Turn it on to read `ys` (e.g. for parity checks against maplookup).
 
-`opt` (an `ADAGrad` or `RowwiseADAGrad`; default None = `Descent(lr)`): the tables are stepped with
-that optimizer.  The fused step pair is Descent-only, so this selects the operator path: the fused
-forward, the gather backward (which writes every dt row and builds the indexer in its launch),
-then dlrm_adagrad_update(PREBUILT) -- three launches, no host synchronisation, graph-capturable.
+`opt` (an `ADAGrad`, `RowwiseADAGrad` or `SplitDescent`; default None = `Descent(lr)`): the tables are
+stepped with that optimizer.  The fused step pair is Descent-only (on split-bf16 tables it would round
+the high halves), so this selects the operator path: the fused forward, the gather backward (which
+writes every dt row and builds the indexer in its launch), then dlrm_adagrad_update(PREBUILT) or
+dlrm_split_sgd_update(PREBUILT) -- three launches, no host synchronisation, graph-capturable.
 """
 import torch
 
@@ -37,17 +38,17 @@ from .embedding import EmbeddingTableSet, PackedIndices
 from .interact import interaction_sizes
 from .runtime import dtype_code, ptr, require_device
 from .shapes import APPLY_MAX_N
-from .update import SparseIndexer, _AdagradBase
+from .update import SparseIndexer, _StatefulOpt
 
 
 class HotPath:
     def __init__(self, tables, batch, lookups=1, *, lr=0.1, index_base=0, deterministic=True,
                  overlap_indexer=None, pad_to=1, fused=True, materialize_ys=None, pipeline=False, chunk=None,
                  parts=None, opt=None):
-        if opt is not None and not isinstance(opt, _AdagradBase):
-            raise TypeError("HotPath: opt is an ADAGrad or RowwiseADAGrad (None: Descent(lr))")
+        if opt is not None and not isinstance(opt, _StatefulOpt):
+            raise TypeError("HotPath: opt is an ADAGrad, RowwiseADAGrad or SplitDescent (None: Descent(lr))")
         if opt is not None and not deterministic:
-            raise ValueError("HotPath: an Adagrad optimizer needs the deterministic update")
+            raise ValueError(f"HotPath: {type(opt).__name__} needs the deterministic update")
         self.opt = opt
         self.ts = tables if isinstance(tables, EmbeddingTableSet) else EmbeddingTableSet(tables)
         self.B, self.L = int(batch), int(lookups)
@@ -184,15 +185,13 @@ class HotPath:
                                              ptr(idx.data), idx.itype, idx.stride, self.index_base, self.B, self.L,
                                              ptr(self.dt), _lib.F32, self.dt.stride(0), self.d, self.lr))
 
-    def adagrad_update(self, idx, prebuilt, opt=None):
-        """dlrm_adagrad_update of dt with `opt` (default: the engine's optimizer)."""
-        h = self.ctx.bind()
+    def opt_update(self, idx, prebuilt, opt=None):
+        """dlrm_adagrad_update / dlrm_split_sgd_update of dt with `opt` (default: the engine's optimizer)."""
         opt = self.opt if opt is None else opt
         flags = _lib.UPDATE_PREBUILT if prebuilt else 0
-        self._check(self.lib.dlrm_adagrad_update(h, self.ts.handle, opt.handle_of(self.ts), self.indexer.handle,
-                                                 flags, ptr(idx.data), idx.itype, idx.stride, self.index_base, self.B,
-                                                 self.L, ptr(self.dt), _lib.F32, self.dt.stride(0), self.d, opt.eta,
-                                                 opt.eps))
+        self._check(opt.launch(self.ts, self.indexer, flags, idx, self.index_base, self.dt, self.d))
+
+    adagrad_update = opt_update
 
     def step_fwd(self, x, idx):
         """dlrm_step_fwd: lookup + interaction (no ys) + the split indexer, one launch."""
@@ -365,7 +364,7 @@ class HotPath:
             torch.cuda.current_stream(self.ts.device).wait_event(self._indexer_done)
             prebuilt = True
         if self.opt is not None:
-            self.adagrad_update(idx, prebuilt)
+            self.opt_update(idx, prebuilt)
         else:
             self.sgd_update(idx, prebuilt)
         return self.dx

@@ -464,11 +464,67 @@ function adagrad_state(opt::AbstractHipADAGrad, tables::AbstractVector{<:HipEmbe
     end
 end
 
-# update!(HipADAGrad / HipRowwiseADAGrad, tables, grads, indexers): the unfused path builds the
-# indexer in the call; after a fused step's pullback that wrote every dt row (a fused context without a
-# learning rate) the forward's split indexer is reused (_fused_update!).
+#####
+##### Split-bf16 tables: HipSplitDescent (Flux.Descent as an exact fp32 step on bf16 rows).
+#####
+
+"""
+    HipSplitDescent(η = 0.1)
+
+`Flux.Descent(η)` for 2-byte (bf16) `HipEmbedding` tables kept in the split layout: each weight has an
+fp32 master value whose high 16 bits are the table element and whose low 16 bits live in a `UInt16`
+state matrix of the table's shape (`D × N`, zeros at the first `update!` of a table vector: right for
+tables that were bf16 all along).  `update!` steps the master value, `w .-= η .* G`, exactly, and
+writes both halves back; lookups and the interaction keep reading the bf16 table (the master value
+truncated).  `split_state(opt, tables)` returns the low halves.  Do not also step such tables with
+`Descent` or an Adagrad optimizer: those round the high half and leave the low one behind.
+"""
+mutable struct HipSplitDescent
+    eta::Float32
+    state::IdDict{Any,Any}     # tables => (low-half matrices, dlrm_split_sgd handle)
+end
+HipSplitDescent(η = 0.1) = HipSplitDescent(Float32(η), IdDict{Any,Any}())
+
+"The low halves of `tables` (one `DeviceMatrix{UInt16}` per table) and their dlrm_split_sgd handle."
+function split_state(opt::HipSplitDescent, tables::AbstractVector{<:HipEmbedding})
+    get!(opt.state, tables) do
+        ctx = first(tables).data.ctx
+        state = map(tables) do t
+            D, N = size(t)
+            upload!(DeviceMatrix{UInt16}(ctx, D, N), zeros(UInt16, D, N))
+        end
+        ptrs = [m.ptr for m in state]
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ctx, ccall((:dlrm_split_sgd_create, libdlrm), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                         ctx.ptr, tableset(tables), ptrs, out))
+        (state, out[])
+    end
+end
+
+# The C update of a rule with state: (ctx, tables, optimizer handle, indexer, flags, indices, gradient).
+function _rule_update(opt::AbstractHipADAGrad, ctx, tables, ixptr, flags, idxptr, stride, batch, lookups, dtptr, ld, off)
+    _, h = adagrad_state(opt, tables)
+    ccall((:dlrm_adagrad_update, libdlrm), Cint,
+          (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cuint, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint,
+           Ptr{Cvoid}, Cint, Int64, Int64, Cfloat, Cfloat),
+          ctx.ptr, tableset(tables), h, ixptr, flags, idxptr, DLRM_I32, stride, 1,
+          batch, lookups, dtptr, DLRM_F32, ld, off, opt.eta, opt.epsilon)
+end
+function _rule_update(opt::HipSplitDescent, ctx, tables, ixptr, flags, idxptr, stride, batch, lookups, dtptr, ld, off)
+    _, h = split_state(opt, tables)
+    ccall((:dlrm_split_sgd_update, libdlrm), Cint,
+          (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cuint, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint,
+           Ptr{Cvoid}, Cint, Int64, Int64, Cfloat),
+          ctx.ptr, tableset(tables), h, ixptr, flags, idxptr, DLRM_I32, stride, 1,
+          batch, lookups, dtptr, DLRM_F32, ld, off, opt.eta)
+end
+
+# update!(HipADAGrad / HipRowwiseADAGrad / HipSplitDescent, tables, grads, indexers): the unfused path
+# builds the indexer in the call; after a fused step's pullback that wrote every dt row (a fused context
+# without a learning rate) the forward's split indexer is reused (_fused_update!).
 function EmbeddingTables.update!(
-    opt::AbstractHipADAGrad, tables::AbstractVector{<:HipEmbedding{Static{D}}},
+    opt::Union{AbstractHipADAGrad,HipSplitDescent}, tables::AbstractVector{<:HipEmbedding{Static{D}}},
     grads::AbstractVector{<:SparseEmbeddingUpdate}, indexers; num_splits = 8, nthreads = Threads.nthreads()
 ) where {D}
     length(grads) == length(tables) || throw(ArgumentError("one SparseEmbeddingUpdate per table"))
@@ -484,12 +540,8 @@ function EmbeddingTables.update!(
         st.dt === δ1.dt && return _fused_update!(opt, st, tables)
     end
     ix = get!(() -> HipIndexer(ctx, length(tables), idx.batch * idx.lookups), INDEXERS, indexers)
-    _, h = adagrad_state(opt, tables)
-    check(ctx, ccall((:dlrm_adagrad_update, libdlrm), Cint,
-                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cuint, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint,
-                      Ptr{Cvoid}, Cint, Int64, Int64, Cfloat, Cfloat),
-                     ctx.ptr, tableset(tables), h, ix.ptr, Cuint(0), idx.data.ptr, DLRM_I32, idx.batch * idx.lookups, 1,
-                     idx.batch, idx.lookups, δ1.dt.ptr, DLRM_F32, size(δ1.dt, 1), δ1.offset, opt.eta, opt.epsilon))
+    check(ctx, _rule_update(opt, ctx, tables, ix.ptr, Cuint(0), idx.data.ptr, idx.batch * idx.lookups, idx.batch,
+                            idx.lookups, δ1.dt.ptr, size(δ1.dt, 1), δ1.offset))
     check_bounds(ctx)     # BoundsError, as the reference's gather throws (no row or state was written)
     return nothing
 end
@@ -779,18 +831,15 @@ end
 function _fused_update!(opt, st, tables)
     ctx = st.ctx
     d, B = size(st.x)
-    if opt isa AbstractHipADAGrad
+    if opt isa Union{AbstractHipADAGrad,HipSplitDescent}
         # every dt row is needed: the forward's split indexer, the once-hit rows as singles items
         st.bwd === :once_hit_applied &&
             throw(ArgumentError("the pullback already stepped the once-hit rows with Descent (η = $(ctx.lr)) and left " *
-                                "their gradient rows unwritten; use a context without a learning rate to update with Adagrad"))
+                                "their gradient rows unwritten; use a context without a learning rate to update with " *
+                                "$(nameof(typeof(opt)))"))
         st.bwd === :all_dt || throw(ArgumentError("update! before the interaction's pullback ran"))
-        _, h = adagrad_state(opt, tables)
-        check(ctx, ccall((:dlrm_adagrad_update, libdlrm), Cint,
-                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cuint, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint,
-                          Ptr{Cvoid}, Cint, Int64, Int64, Cfloat, Cfloat),
-                         ctx.ptr, tableset(st.tables), h, st.ix.ptr, UPDATE_PREBUILT, st.idx.data.ptr, DLRM_I32,
-                         st.idx.batch, 1, st.idx.batch, 1, st.dt.ptr, DLRM_F32, size(st.dt, 1), d, opt.eta, opt.epsilon))
+        check(ctx, _rule_update(opt, ctx, tables, st.ix.ptr, UPDATE_PREBUILT, st.idx.data.ptr, st.idx.batch,
+                                st.idx.batch, 1, st.dt.ptr, size(st.dt, 1), d))
         st.bwd = :done
         check_bounds(ctx)
         return nothing

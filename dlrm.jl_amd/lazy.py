@@ -38,9 +38,11 @@ Anything else that reads ys gets it materialized (`LazyLookup.materialize`).  `o
 gradient live in per-batch-size buffers reused by the next step, as the reference's own
 preallocated scratch (`DotInteraction`'s per-thread scratchpads) is.
 """
+import torch
+
 from . import _lib
 from .embedding import EmbeddingTableSet, PackedIndices, PreallocationStrategy, as_table_set
-from .update import Descent, SparseEmbeddingUpdate, _AdagradBase
+from .update import Descent, SparseEmbeddingUpdate, SplitDescent, _StatefulOpt
 
 
 class HipTables:
@@ -244,21 +246,23 @@ def update_lazy(opt, tables, grads, *, check_bounds=None):
     """update!(Descent(η), ::HipTables, grads): the apply launch of the step.  check_bounds: None
     (the reference's call): the tables' policy -- deferred apply + flag snapshot when they defer,
     else the launch and a synchronising check; True: run it now and check; False: no check."""
-    if not isinstance(opt, (Descent, _AdagradBase)):
-        raise TypeError("update_ implements Descent (plain SGD, the optimizer DLRM.jl trains with), ADAGrad and "
-                        "RowwiseADAGrad")
+    if not isinstance(opt, (Descent, _StatefulOpt)):
+        raise TypeError("update_ implements Descent (plain SGD, the optimizer DLRM.jl trains with), ADAGrad, "
+                        "RowwiseADAGrad and SplitDescent")
+    if isinstance(opt, SplitDescent) and tables._ts.dtype != torch.bfloat16:
+        raise ValueError(f"SplitDescent needs bfloat16 tables (the high halves), not {tables._ts.dtype}")
     lz = grads[0].lazy
     if len(grads) != len(tables) or any(g.lazy is not lz or g.table_index != t for t, g in enumerate(grads)):
         raise ValueError("update_ expects the per-table views of one maplookup pullback")
     hp = lz.hp
     tables.flush()
-    if isinstance(opt, _AdagradBase):
+    if isinstance(opt, _StatefulOpt):
         # every dt row is needed: the forward's split indexer, the once-hit rows as singles items
         if lz.applied:
             raise ValueError(f"the pullback already stepped the once-hit rows with Descent (HipTables(lr={tables.lr})) "
                              "and left their gradient rows unwritten; build HipTables with lr=None to update with "
                              f"{type(opt).__name__}")
-        hp.adagrad_update(lz.idx, prebuilt=True, opt=opt)
+        hp.opt_update(lz.idx, prebuilt=True, opt=opt)
     elif lz.applied:
         if opt.eta != tables.lr:
             raise ValueError(f"the pullback stepped the once-hit rows with η = {tables.lr}; update! got {opt.eta}")

@@ -28,18 +28,26 @@ class Descent:
         return f"Descent({self.eta})"
 
 
-class _AdagradBase:
-    """Sparse Adagrad over embedding tables.  The state is kept per table set (as Flux keys its
-    IdDict by parameter): allocated on the tables' device at first use, and exposed by
+class _StatefulOpt:
+    """An optimizer with device state per table row.  The state is kept per table set (as Flux keys
+    its IdDict by parameter): allocated on the tables' device at first use, and exposed by
     `state_of(tables)` so a caller can read, save or preset it."""
-    rowwise = False
 
-    def __init__(self, eta=0.1, eps=1e-8):
-        self.eta = float(eta)
-        self.eps = float(eps)
-        self._state = {}  # the tables' data pointers -> (table set, [state tensors], dlrm_adagrad handle)
+    def __init__(self):
+        self._state = {}  # the tables' data pointers -> (table set, [state tensors], the C handle)
 
     def _init_state(self, table):
+        raise NotImplementedError
+
+    def _create(self, ts, ptrs, out):
+        """The C constructor's return code (handle into `out`)."""
+        raise NotImplementedError
+
+    def _destroy(self, lib, handle):
+        raise NotImplementedError
+
+    def launch(self, ts, indexer, flags, idx, index_base, grad, grad_offset):
+        """The C update's return code: `grad` columns from `grad_offset`, indices `idx` (PackedIndices)."""
         raise NotImplementedError
 
     def _entry(self, tables):
@@ -51,28 +59,50 @@ class _AdagradBase:
             T = len(ts)
             ptrs = (ctypes.c_void_p * T)(*[s.data_ptr() for s in state])
             h = ctypes.c_void_p()
-            ts.ctx.check(ts.ctx.lib.dlrm_adagrad_create(ts.ctx.bind(), ts.handle, int(self.rowwise), ptrs,
-                                                        ctypes.byref(h)))
+            ts.ctx.check(self._create(ts, ptrs, ctypes.byref(h)))
             ent = self._state[key] = (ts, state, h)
         return ent
 
     def state_of(self, tables):
-        """The fp32 state tensors of `tables` (a table set), one per table: [nrows][D] accumulators
-        (ADAGrad) or [nrows] row accumulators (RowwiseADAGrad).  Write into them to preset the state."""
+        """The state tensors of `tables` (a table set), one per table: fp32 [nrows][D] accumulators
+        (ADAGrad), fp32 [nrows] row accumulators (RowwiseADAGrad) or int16 [nrows][D] low halves
+        (SplitDescent).  Write into them to preset the state."""
         return self._entry(tables)[1]
 
     def handle_of(self, tables):
         return self._entry(tables)[2]
 
-    def __repr__(self):
-        return f"{type(self).__name__}({self.eta}, {self.eps})"
-
     def __del__(self):
         try:
             for ts, _, h in self._state.values():
-                ts.ctx.lib.dlrm_adagrad_destroy(h)
+                self._destroy(ts.ctx.lib, h)
         except Exception:
             pass
+
+
+class _AdagradBase(_StatefulOpt):
+    """Sparse Adagrad over embedding tables (dlrm_adagrad_*)."""
+    rowwise = False
+
+    def __init__(self, eta=0.1, eps=1e-8):
+        super().__init__()
+        self.eta = float(eta)
+        self.eps = float(eps)
+
+    def _create(self, ts, ptrs, out):
+        return ts.ctx.lib.dlrm_adagrad_create(ts.ctx.bind(), ts.handle, int(self.rowwise), ptrs, out)
+
+    def _destroy(self, lib, handle):
+        lib.dlrm_adagrad_destroy(handle)
+
+    def launch(self, ts, indexer, flags, idx, index_base, grad, grad_offset):
+        ctx = ts.ctx
+        return ctx.lib.dlrm_adagrad_update(ctx.bind(), ts.handle, self.handle_of(ts), indexer.handle, flags,
+                                           ptr(idx.data), idx.itype, idx.stride, index_base, idx.B, idx.L, ptr(grad),
+                                           dtype_code(grad.dtype), grad.stride(0), grad_offset, self.eta, self.eps)
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.eta}, {self.eps})"
 
 
 class ADAGrad(_AdagradBase):
@@ -90,6 +120,73 @@ class RowwiseADAGrad(_AdagradBase):
 
     def _init_state(self, table):
         return torch.zeros((table.shape[0],), dtype=torch.float32, device=table.device)
+
+
+def split_f32(w):
+    """(hi, lo) of an fp32 tensor: hi = the top 16 bits of every element as bfloat16 (the
+    truncation of w, not `w.to(bfloat16)`, which rounds), lo = the bottom 16 bits as int16.  Pure
+    bit operations, any device; `merge_split(hi, lo)` has exactly the bits of `w`."""
+    if w.dtype != torch.float32:
+        raise TypeError("split_f32 expects a float32 tensor")
+    u = w.view(torch.int32)
+    hi = (u >> 16).to(torch.int16).view(torch.bfloat16)  # (arithmetic shifts: both halves fit int16 as they are)
+    lo = ((u << 16) >> 16).to(torch.int16)
+    return hi, lo
+
+
+def merge_split(hi, lo):
+    """The fp32 tensor whose top 16 bits are `hi` (bfloat16) and bottom 16 bits `lo` (int16)."""
+    if hi.dtype != torch.bfloat16 or lo.dtype != torch.int16 or hi.shape != lo.shape:
+        raise TypeError("merge_split expects a bfloat16 tensor and an int16 tensor of the same shape")
+    u = (hi.view(torch.int16).to(torch.int32) << 16) | (lo.to(torch.int32) & 0xFFFF)
+    return u.view(torch.float32)
+
+
+class SplitDescent(_StatefulOpt):
+    """Flux.Descent(η) on split-bf16 tables (dlrm_split_sgd_*): every weight has an fp32 master value
+    whose high 16 bits are the bf16 table element and whose low 16 bits live in an int16 state array
+    of the same shape.  The step is Descent's on the fp32 value, exactly; the lookup, the
+    interaction and its backward keep reading the bf16 table (the master value truncated).
+
+    `state_of(tables)` returns the low halves, zeros at first use (right for tables that were bf16
+    all along); write `split_f32(w)[1]` into them to start from fp32 weights `w`.  Do not step such
+    tables with Descent, an Adagrad optimizer or a `HotPath` without `opt=`: those round the high
+    half and leave the low one behind."""
+
+    def __init__(self, eta=0.1):
+        super().__init__()
+        self.eta = float(eta)
+
+    def _init_state(self, table):
+        if table.dtype != torch.bfloat16:
+            raise ValueError(f"SplitDescent needs bfloat16 tables (the high halves), not {table.dtype}")
+        return torch.zeros(table.shape, dtype=torch.int16, device=table.device)
+
+    def _create(self, ts, ptrs, out):
+        return ts.ctx.lib.dlrm_split_sgd_create(ts.ctx.bind(), ts.handle, ptrs, out)
+
+    def _destroy(self, lib, handle):
+        lib.dlrm_split_sgd_destroy(handle)
+
+    def launch(self, ts, indexer, flags, idx, index_base, grad, grad_offset):
+        ctx = ts.ctx
+        return ctx.lib.dlrm_split_sgd_update(ctx.bind(), ts.handle, self.handle_of(ts), indexer.handle, flags,
+                                             ptr(idx.data), idx.itype, idx.stride, index_base, idx.B, idx.L, ptr(grad),
+                                             dtype_code(grad.dtype), grad.stride(0), grad_offset, self.eta)
+
+    def master_of(self, tables):
+        """The fp32 master weights of `tables`, one new tensor per table (checkpoints, tests)."""
+        ts, lo, _ = self._entry(tables)
+        return [merge_split(t.data, s) for t, s in zip(ts, lo)]
+
+    def __repr__(self):
+        return f"SplitDescent({self.eta})"
+
+
+def _tables_dtype(tables):
+    """The element type of `tables` (a table set, HipTables, or a list of tables / tensors)."""
+    first = next(iter(getattr(tables, "_ts", tables)))  # (HipTables: its table set, without a bounds check)
+    return getattr(first, "data", first).dtype
 
 
 class SparseEmbeddingUpdate:
@@ -277,13 +374,19 @@ def update_(opt, tables, grads, indexers=None, *, num_splits=8, nthreads=12, ind
     index_base = 1 if index_base is None else int(index_base)
     if isinstance(tables, HipTables):
         tables = tables.ts
-    if not isinstance(opt, (Descent, _AdagradBase)):
-        raise TypeError("update_ implements Descent (plain SGD, the optimizer DLRM.jl trains with), ADAGrad and "
-                        "RowwiseADAGrad")
-    adagrad = isinstance(opt, _AdagradBase)
-    if adagrad and not deterministic:
+    if not isinstance(opt, (Descent, _StatefulOpt)):
+        raise TypeError("update_ implements Descent (plain SGD, the optimizer DLRM.jl trains with), ADAGrad, "
+                        "RowwiseADAGrad and SplitDescent")
+    stateful = isinstance(opt, _StatefulOpt)
+    if isinstance(opt, _AdagradBase) and not deterministic:
         raise ValueError("update_ with an Adagrad optimizer is deterministic only: an atomic add never holds the "
                          "row's whole gradient sum, which the rule squares")
+    if isinstance(opt, SplitDescent):
+        if not deterministic:
+            raise ValueError("update_ with SplitDescent is deterministic only: an atomic add on one half of a "
+                             "weight cannot carry into the other")
+        if _tables_dtype(tables) != torch.bfloat16:
+            raise ValueError(f"SplitDescent needs bfloat16 tables (the high halves), not {_tables_dtype(tables)}")
     ts = as_table_set(tables)
     if len(grads) != len(ts):
         raise ValueError(f"{len(grads)} gradients for {len(ts)} tables")
@@ -312,11 +415,8 @@ def update_(opt, tables, grads, indexers=None, *, num_splits=8, nthreads=12, ind
     else:
         flags |= _lib.UPDATE_ATOMIC
     ctx = ts.ctx
-    if adagrad:
-        ctx.check(ctx.lib.dlrm_adagrad_update(ctx.bind(), ts.handle, opt.handle_of(ts), ix.handle, flags, ptr(idx.data),
-                                              idx.itype, idx.stride, index_base, idx.B, idx.L, ptr(grad),
-                                              dtype_code(grad.dtype), grad.stride(0), g0.grad_offset, opt.eta,
-                                              opt.eps))
+    if stateful:
+        ctx.check(opt.launch(ts, ix, flags, idx, index_base, grad, g0.grad_offset))
     else:
         ctx.check(ctx.lib.dlrm_sgd_update(ctx.bind(), ts.handle, ix.handle if ix is not None else None, flags,
                                           ptr(idx.data), idx.itype, idx.stride, index_base, idx.B, idx.L, ptr(grad),

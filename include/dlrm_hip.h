@@ -368,6 +368,52 @@ int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagrad* opt, d
                         const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset,
                         float lr, float eps);
 
+/* ---- split-bf16 tables: update!(Descent(lr), ...) as an exact fp32 step on bf16 rows.
+ * The reference names the layout (src/train/train.jl:117, `mantissa_trick`) and never builds it.
+ *
+ * Layout: every weight has an fp32 master value W.  The bf16 table every other entry point reads
+ * (dlrm_maplookup, dlrm_step_fwd, dlrm_interact_bwd_gather, the exchange) holds the HIGH 16 bits of
+ * W; a second caller-owned uint16 array per table, lo[t] of shape [nrows][dim], holds the LOW 16
+ * bits.  The high half is the truncation of W, not its rounding: the forward sees W moved toward
+ * zero by less than one bf16 ulp, and (hi << 16) | lo is W exactly.  A table that was bf16 all
+ * along starts with zero low halves.
+ *
+ * For a table row r touched by the batch, G[c] is dlrm_sgd_update's fp32 gradient sum (same indexer
+ * form, same order).  Then
+ *     W  = bits((hi[r][c] << 16) | lo[r][c])
+ *     W' = fmaf(-lr, G[c], W)
+ *     hi[r][c] = bits(W') >> 16,  lo[r][c] = bits(W') & 0xffff
+ * so the merged values follow dlrm_sgd_update's trajectory on fp32 tables bit for bit.  When W' is a
+ * NaN the high half also gets the quiet bit (0x40), so the bf16 table alone still reads NaN.  Each
+ * touched row's two halves are written exactly once, untouched rows keep their bits in both arrays,
+ * the result is bitwise reproducible, and a set bounds flag (the context's, or a prepared build's)
+ * leaves both arrays unwritten, as in dlrm_sgd_update.  The update moves the bytes per row of an
+ * fp32 table's; the two arrays together take 4 bytes per element.
+ *
+ * Do not mix: dlrm_sgd_update, dlrm_adagrad_update or dlrm_step_bwd on such tables write a ROUNDED
+ * bf16 step into the high half and leave the low half as it was, after which the pair no longer
+ * holds the master weight.
+ *
+ * dlrm_split_sgd_create uploads the per-table low-half pointers once: tables that are not
+ * DLRM_BF16, or a table with rows and lo[t] == NULL, return DLRM_E_ARG.  16-B aligned lo[t] (and
+ * dim * 2 % 16 == 0) let the vector kernels run; anything else takes the any-dim kernels with the
+ * same results.  dlrm_split_sgd_update: tables that are not DLRM_BF16, or an optimizer created for
+ * another table count / dim, return DLRM_E_ARG; DLRM_UPDATE_ATOMIC returns DLRM_E_UNSUPPORTED;
+ * DLRM_UPDATE_PREBUILT is honoured; an indexer in state DLRM_IX_SINGLES_DONE returns DLRM_E_STATE
+ * (a split backward has already written those rows' high halves with a rounded bf16 step); a
+ * split indexer whose singles are not done is taken whole, once-hit rows included.  Launches
+ * neither allocate nor synchronise beyond what dlrm_sgd_update does, so the call is
+ * graph-capturable.  dlrm_split_sgd_destroy of NULL returns 0. */
+typedef struct dlrm_split_sgd dlrm_split_sgd; /* per-table low-half pointers on the device */
+int dlrm_split_sgd_create(dlrm_ctx* ctx, const dlrm_tables* tables, uint16_t* const* lo,
+                          dlrm_split_sgd** out);
+int dlrm_split_sgd_destroy(dlrm_split_sgd* opt);
+int dlrm_split_sgd_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_split_sgd* opt, dlrm_indexer* indexer,
+                          unsigned flags, const void* indices, int itype, int64_t table_stride,
+                          int index_base, int batch, int lookups,
+                          const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset,
+                          float lr);
+
 /* ---- training step: fused forms of the four operators --------------------------------
  * One train! iteration of the sparse half of the model (src/train/train.jl:215-227 and
  * custom_update! :283-290) on one-hot lookups, as two launching calls with the tables

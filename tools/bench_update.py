@@ -1,10 +1,13 @@
 """The embedding update alone, by optimizer: Descent (dlrm_sgd_update), ADAGrad and RowwiseADAGrad
-(dlrm_adagrad_update), each with DLRM_UPDATE_PREBUILT on one indexer built once, over a full dt.
+(dlrm_adagrad_update) and SplitDescent (dlrm_split_sgd_update), each with DLRM_UPDATE_PREBUILT on one
+indexer built once, over a full dt.  SplitDescent runs on a bf16 copy of the tables (the truncated high
+halves, the low halves beside them); on an fp32 workload a Descent-bf16 leg steps a second bf16 copy, so
+the split rule is timed against Descent on fp32 tables and on bf16 tables in the same run.
 
 Each leg is a captured graph of 200 launches, replayed until the timed window exceeds 0.5 s; the
 legs alternate, five repeats.  One JSON line per run: per shape and leg the median / min / max us
 per launch, the leg's algorithmic bytes (gradient rows + twice the touched table rows + twice the
-touched state rows or words, from the shapes and the unique-row counts), and each Adagrad leg's
+touched state rows or words, from the shapes and the unique-row counts), and each other leg's
 time and byte ratios to the Descent leg of the same run.
 
     python tools/bench_update.py [--workloads kaggle-d128-b2048,kaggle-d16-b2048]
@@ -38,12 +41,19 @@ def bench_shape(pkg, dev, name):
     dt = torch.randn((B, (T + 1) * D), device=dev, generator=g) * 1e-3  # x rows first, as dot_back writes it
     ix = pkg.SparseIndexer(T, B * L, dev).build(ts, p, index_base=0)  # once: every leg passes PREBUILT
     grads = pkg.maplookup_pullback(D, ts, p, dt)
-    opts = {"Descent": pkg.Descent(1e-6), "ADAGrad": pkg.ADAGrad(1e-6), "RowwiseADAGrad": pkg.RowwiseADAGrad(1e-6)}
+    # leg -> (optimizer, tables, their gradient views); the indexer depends on the indices and row counts only
+    opts = {"Descent": (pkg.Descent(1e-6), ts, grads), "ADAGrad": (pkg.ADAGrad(1e-6), ts, grads),
+            "RowwiseADAGrad": (pkg.RowwiseADAGrad(1e-6), ts, grads)}
+    hi = pkg.EmbeddingTableSet([pkg.split_f32(t.data.float())[0] for t in ts])
+    opts["SplitDescent"] = (pkg.SplitDescent(1e-6), hi, pkg.maplookup_pullback(D, hi, p, dt))
+    if dtype == torch.float32:
+        b16 = pkg.EmbeddingTableSet([t.data.clone() for t in hi])
+        opts["Descent-bf16"] = (pkg.Descent(1e-6), b16, pkg.maplookup_pullback(D, b16, p, dt))
     graphs = {}
     s = torch.cuda.Stream()
-    for leg, opt in opts.items():
-        def launch(opt=opt):
-            pkg.update_(opt, ts, grads, ix, index_base=0, prebuilt=True, check_bounds=False)
+    for leg, (opt, tabs, gr_views) in opts.items():
+        def launch(opt=opt, tabs=tabs, gr_views=gr_views):
+            pkg.update_(opt, tabs, gr_views, ix, index_base=0, prebuilt=True, check_bounds=False)
         launch()  # the state and every first-use allocation, before the capture
         torch.cuda.synchronize()
         s.wait_stream(torch.cuda.current_stream())
@@ -73,16 +83,20 @@ def bench_shape(pkg, dev, name):
             us[leg].append(ms * 1e3 / (n * LAUNCHES))
     ts.ctx.check_bounds()
     grad_bytes = T * B * L * D * 4 if L == 1 else T * B * D * 4
-    state_bytes = {"Descent": 0, "ADAGrad": 2 * unique * D * 4, "RowwiseADAGrad": 2 * unique * 4}
+    state_bytes = {"Descent": 0, "ADAGrad": 2 * unique * D * 4, "RowwiseADAGrad": 2 * unique * 4,
+                   "SplitDescent": 2 * unique * D * 2, "Descent-bf16": 0}
+    table_esize = {"SplitDescent": 2, "Descent-bf16": 2}
     out = {"unique_rows": unique, "legs": {}}
     for leg in opts:
         v = us[leg]
         out["legs"][leg] = {"us_median": round(statistics.median(v), 3), "us_min": round(min(v), 3),
                             "us_max": round(max(v), 3),
-                            "bytes": grad_bytes + 2 * unique * D * esize + state_bytes[leg]}
+                            "bytes": grad_bytes + 2 * unique * D * table_esize.get(leg, esize) + state_bytes[leg]}
     base = out["legs"]["Descent"]
     out["descent_spread"] = round((base["us_max"] - base["us_min"]) / base["us_median"], 4)
-    for leg in ("ADAGrad", "RowwiseADAGrad"):
+    for leg in opts:
+        if leg == "Descent":
+            continue
         out["legs"][leg]["time_ratio"] = round(out["legs"][leg]["us_median"] / base["us_median"], 4)
         out["legs"][leg]["byte_ratio"] = round(out["legs"][leg]["bytes"] / base["bytes"], 4)
     return out
