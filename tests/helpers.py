@@ -8,6 +8,8 @@ Tolerances (stated here once, used by every parity test):
     norm(a - b) <= sqrt(eps(Float32)) * max(norm(a), norm(b)) (the reference's own criterion,
     test/integration.jl, src/validation.jl).
   * bf16 outputs: one bf16 rounding (2^-8 relative) of the fp32 result.
+  * interaction on exactly summable inputs: bit-exact, bf16 rounded once to nearest even
+    (tests/test_interaction_exact.py).
 """
 import numpy as np
 
