@@ -45,22 +45,22 @@ struct dlrm_tables {
     bool aligned16 = true;
 };
 
-// Sparse Adagrad state of one table set: the caller's per-table fp32 state pointers, uploaded once
-struct dlrm_adagrad {
-    int T = 0, D = 0;
-    bool rowwise = false;     // one word per table row instead of one row
-    bool aligned16 = true;    // every state pointer is 16-B aligned
-    float** d_state = nullptr;
-    std::vector<float*> h_state;
+// An optimizer's state of one table set: the caller's per-table pointers, uploaded once
+struct StateDims {
+    int T = 0, D = 0;  // what the handle was created for
 };
-
-// Low halves of one split-bf16 table set: the caller's per-table uint16 pointers, uploaded once
-struct dlrm_split_sgd {
-    int T = 0, D = 0;
-    bool aligned16 = true;    // every low-half pointer is 16-B aligned
-    uint16_t** d_lo = nullptr;
-    std::vector<uint16_t*> h_lo;
+template <typename E>
+struct StatePtrs : StateDims {
+    bool aligned16 = true;  // every pointer is 16-B aligned
+    E** d_ptr = nullptr;
+    std::vector<E*> h_ptr;
 };
+// Sparse Adagrad: fp32 state
+struct dlrm_adagrad : StatePtrs<float> {
+    bool rowwise = false;  // one word per table row instead of one row
+};
+// The low halves of split-bf16 tables
+struct dlrm_split_sgd : StatePtrs<uint16_t> {};
 
 struct dlrm_indexer {
     dlrm_ctx* ctx = nullptr;
@@ -178,6 +178,54 @@ static int ensure_side(dlrm_ctx* ctx) {
     if (rc == DLRM_OK) rc = ctx_hip(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming), "hipEventCreate");
     if (rc == DLRM_OK) rc = ctx_hip(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming), "hipEventCreate");
     return rc;
+}
+
+// The words of a create's messages: "FN: null WHAT", "FN: table %d has no ONE", "hipMalloc(HIP)".
+struct StateWords { const char *fn, *what, *one, *hip; };
+
+// The checks of a state handle's create, the upload of its per-table pointers and the unwinding.
+// (Rows of D elements from a 16-B aligned base are aligned when the row's bytes % 16 == 0, which the vector
+// kernels need anyway.)
+template <typename OP, typename E>
+static int state_create(dlrm_ctx* ctx, const dlrm_tables* tb, bool bf16_only, E* const* ptrs, OP** out,
+                        const StateWords& w) {
+    CHECK_ARG(ctx && tb && out, "%s: null argument", w.fn);
+    *out = nullptr;
+    CHECK_ARG(!bf16_only || tb->dtype == DLRM_BF16, "%s: split tables are bf16 (the high halves)", w.fn);
+    CHECK_ARG(tb->T == 0 || ptrs, "%s: null %s", w.fn, w.what);
+    for (int t = 0; t < tb->T; ++t)
+        CHECK_ARG(ptrs[t] || tb->h_desc[t].nrows == 0, "%s: table %d has no %s", w.fn, t, w.one);
+    OP* op = new (std::nothrow) OP();
+    if (!op) return DLRM_E_NOMEM;
+    op->T = tb->T;
+    op->D = tb->D;
+    op->h_ptr.assign(ptrs, ptrs + tb->T);
+    for (int t = 0; t < tb->T; ++t)
+        if ((uintptr_t)ptrs[t] % 16) op->aligned16 = false;
+    char what[2][48];
+    snprintf(what[0], sizeof(what[0]), "hipMalloc(%s)", w.hip);
+    snprintf(what[1], sizeof(what[1]), "hipMemcpy(%s)", w.hip);
+    int rc = hip_set(ctx);
+    if (rc == DLRM_OK && tb->T > 0) {
+        rc = ctx_hip(ctx, hipMalloc((void**)&op->d_ptr, sizeof(E*) * tb->T), what[0]);
+        if (rc == DLRM_OK)
+            rc = ctx_hip(ctx, hipMemcpy(op->d_ptr, op->h_ptr.data(), sizeof(E*) * tb->T, hipMemcpyHostToDevice), what[1]);
+    }
+    if (rc != DLRM_OK) {
+        if (op->d_ptr) (void)hipFree(op->d_ptr);
+        delete op;
+        return rc;
+    }
+    *out = op;
+    return DLRM_OK;
+}
+
+template <typename OP>
+static int state_destroy(OP* op) {
+    if (!op) return DLRM_OK;
+    if (op->d_ptr) (void)hipFree(op->d_ptr);
+    delete op;
+    return DLRM_OK;
 }
 
 extern "C" {
@@ -967,25 +1015,53 @@ static int ensure_partials(dlrm_ctx* ctx, dlrm_indexer* ix, int D) {
     return DLRM_OK;
 }
 
-int dlrm_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, unsigned flags, const void* indices, int itype,
-                    int64_t table_stride, int index_base, int batch, int lookups, const void* grad, int grad_dtype,
-                    int64_t grad_ld, int64_t grad_offset, float lr) {
-    CHECK_ARG(ctx && tb, "dlrm_sgd_update: null ctx/tables");
+// What the update entry points differ in before their launch.
+struct UpdateRule {
+    const char* fn;            // the entry point, for the messages
+    bool bf16_only;            // split tables
+    const char* made;          // its state handle in words; NULL: none
+    const char* no_atomic;     // why the rule has no atomic mode; NULL: it has one
+    const char* singles_done;  // how a split backward stepped the once-hit rows, which the rule cannot take over;
+                               // NULL: it skips them (their dt rows are all the backward left unwritten)
+};
+static const UpdateRule kSgdUpdate = {"dlrm_sgd_update", false, nullptr, nullptr, nullptr};
+// (an atomic add never holds the row's whole sum, which the rule squares; a split backward stepped its once-hit
+// rows with Descent and left their dt rows unwritten)
+static const UpdateRule kAdagradUpdate = {"dlrm_adagrad_update", false, "the optimizer state was",
+                                          "the rule needs each row's complete sum", "Descent"};
+// (an atomic add on one half cannot carry into the other; a split backward wrote its once-hit rows' high halves
+// with a rounded bf16 step and left their dt rows unwritten)
+static const UpdateRule kSplitUpdate = {"dlrm_split_sgd_update", true, "the low halves were",
+                                        "a row's two halves are stepped together", "a rounded bf16 Descent"};
+
+// The common part of the update entry points, from the index checks to the indexer's build: sa = the
+// launch's once-hit items.  *atomic: DLRM_UPDATE_ATOMIC of a rule that has the mode (nothing is built).
+static int update_prologue(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const UpdateRule& r, const StateDims* op,
+                           unsigned flags,
+                           const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
+                           const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset, SinglesArgs* sa,
+                           bool* atomic) {
+    *atomic = false;
     int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, lookups);
     if (rc) return rc;
-    CHECK_ARG(grad_dtype == DLRM_F32 || grad_dtype == DLRM_BF16, "dlrm_sgd_update: grad dtype %d", grad_dtype);
-    CHECK_ARG(grad_offset >= 0 && grad_ld >= grad_offset + (int64_t)tb->T * tb->D, "dlrm_sgd_update: grad_ld too small");
-    CHECK_ARG(batch == 0 || tb->T == 0 || grad, "dlrm_sgd_update: null grad");
+    CHECK_ARG(!r.bf16_only || tb->dtype == DLRM_BF16, "%s: split tables are bf16 (the high halves)", r.fn);
+    CHECK_ARG(!op || (op->T == tb->T && op->D == tb->D), "%s: %s created for %d tables of dim %d", r.fn, r.made,
+              op ? op->T : 0, op ? op->D : 0);
+    CHECK_ARG(grad_dtype == DLRM_F32 || grad_dtype == DLRM_BF16, "%s: grad dtype %d", r.fn, grad_dtype);
+    CHECK_ARG(grad_offset >= 0 && grad_ld >= grad_offset + (int64_t)tb->T * tb->D, "%s: grad_ld too small", r.fn);
+    CHECK_ARG(batch == 0 || tb->T == 0 || grad, "%s: null grad", r.fn);
     if (flags & DLRM_UPDATE_ATOMIC) {
-        if (tb->dtype != DLRM_F32)
-            return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_sgd_update: atomic mode needs fp32 tables");
-        return launch_sgd_atomic(ctx, tb->d_desc, tb->T, tb->D, indices, itype, table_stride, index_base, batch,
-                                 lookups, grad, grad_dtype, grad_ld, grad_offset, lr);
+        if (r.no_atomic) return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no atomic mode (%s)", r.fn, r.no_atomic);
+        *atomic = true;
+        return DLRM_OK;
     }
-    CHECK_ARG(ix, "dlrm_sgd_update: deterministic mode needs an indexer");
+    CHECK_ARG(ix, "%s: deterministic mode needs an indexer", r.fn);
     if (flags & DLRM_UPDATE_PREBUILT) {
         if (!built_from(ix, indices, itype, table_stride, index_base, batch, lookups))
-            return ctx_fail(ctx, DLRM_E_STATE, "dlrm_sgd_update: indexer was not built from these indices");
+            return ctx_fail(ctx, DLRM_E_STATE, "%s: indexer was not built from these indices", r.fn);
+        if (ix->singles_done && r.singles_done)
+            return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_step_bwd) already stepped this build's "
+                            "once-hit rows with %s", r.fn, r.singles_done);
     } else {
         rc = dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, lookups);
         if (rc) return rc;
@@ -994,162 +1070,74 @@ int dlrm_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, unsigned f
     if (rc) return rc;
     // a split indexer (dlrm_indexer_build's default form, or dlrm_step_fwd's): its once-hit
     // positions are this launch's too -- unless a split backward (dlrm_step_bwd) has updated them
-    // already, in which case only the repeated rows are left (their dt rows are all it wrote)
-    const SinglesArgs sa{(ix->split && !ix->singles_done) ? ix->dev.single : nullptr, indices, itype, table_stride,
-                         index_base, batch * lookups};
+    // already, in which case only the repeated rows are left
+    *sa = SinglesArgs{(ix->split && !ix->singles_done) ? ix->dev.single : nullptr, indices, itype, table_stride,
+                      index_base, batch * lookups};
+    return DLRM_OK;
+}
+
+int dlrm_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, unsigned flags, const void* indices, int itype,
+                    int64_t table_stride, int index_base, int batch, int lookups, const void* grad, int grad_dtype,
+                    int64_t grad_ld, int64_t grad_offset, float lr) {
+    CHECK_ARG(ctx && tb, "dlrm_sgd_update: null ctx/tables");
+    SinglesArgs sa;
+    bool atomic;
+    const int rc = update_prologue(ctx, tb, ix, kSgdUpdate, nullptr, flags, indices, itype, table_stride, index_base, batch,
+                                   lookups, grad, grad_dtype, grad_ld, grad_offset, &sa, &atomic);
+    if (rc) return rc;
+    if (atomic) {
+        if (tb->dtype != DLRM_F32)
+            return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_sgd_update: atomic mode needs fp32 tables");
+        return launch_sgd_atomic(ctx, tb->d_desc, tb->T, tb->D, indices, itype, table_stride, index_base, batch,
+                                 lookups, grad, grad_dtype, grad_ld, grad_offset, lr);
+    }
     return launch_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, tb->T, tb->D, tb->dtype, lookups,
                             (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr, sa);
 }
 
-// ------------------------------------------------------------------------- sparse Adagrad
+// ------------------------------------------------- optimizers with state: sparse Adagrad, split-bf16 tables
 int dlrm_adagrad_create(dlrm_ctx* ctx, const dlrm_tables* tb, int rowwise, float* const* state, dlrm_adagrad** out) {
-    CHECK_ARG(ctx && tb && out, "dlrm_adagrad_create: null argument");
-    *out = nullptr;
-    CHECK_ARG(tb->T == 0 || state, "dlrm_adagrad_create: null state");
-    for (int t = 0; t < tb->T; ++t)
-        CHECK_ARG(state[t] || tb->h_desc[t].nrows == 0, "dlrm_adagrad_create: table %d has no state", t);
-    dlrm_adagrad* op = new (std::nothrow) dlrm_adagrad();
-    if (!op) return DLRM_E_NOMEM;
-    op->T = tb->T;
-    op->D = tb->D;
-    op->rowwise = rowwise != 0;
-    op->h_state.assign(state, state + tb->T);
-    // (rows of D floats from a 16-B aligned base: aligned when D % 4 == 0, which the vector kernels need anyway)
-    for (int t = 0; t < tb->T; ++t)
-        if ((uintptr_t)state[t] % 16) op->aligned16 = false;
-    int rc = hip_set(ctx);
-    if (rc == DLRM_OK && tb->T > 0) {
-        rc = ctx_hip(ctx, hipMalloc((void**)&op->d_state, sizeof(float*) * tb->T), "hipMalloc(adagrad state)");
-        if (rc == DLRM_OK)
-            rc = ctx_hip(ctx, hipMemcpy(op->d_state, op->h_state.data(), sizeof(float*) * tb->T, hipMemcpyHostToDevice),
-                         "hipMemcpy(adagrad state)");
-    }
-    if (rc != DLRM_OK) {
-        if (op->d_state) (void)hipFree(op->d_state);
-        delete op;
-        return rc;
-    }
-    *out = op;
-    return DLRM_OK;
+    const int rc = state_create(ctx, tb, false, state, out, {"dlrm_adagrad_create", "state", "state", "adagrad state"});
+    if (rc == DLRM_OK) (*out)->rowwise = rowwise != 0;
+    return rc;
 }
 
-int dlrm_adagrad_destroy(dlrm_adagrad* op) {
-    if (!op) return DLRM_OK;
-    if (op->d_state) (void)hipFree(op->d_state);
-    delete op;
-    return DLRM_OK;
-}
+int dlrm_adagrad_destroy(dlrm_adagrad* op) { return state_destroy(op); }
 
 int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, unsigned flags,
                         const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
                         const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset, float lr, float eps) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_adagrad_update: null ctx/tables/optimizer/indexer");
-    int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, lookups);
+    SinglesArgs sa;
+    bool atomic;
+    const int rc = update_prologue(ctx, tb, ix, kAdagradUpdate, op, flags, indices, itype, table_stride, index_base, batch,
+                                   lookups, grad, grad_dtype, grad_ld, grad_offset, &sa, &atomic);
     if (rc) return rc;
-    CHECK_ARG(op->T == tb->T && op->D == tb->D, "dlrm_adagrad_update: the optimizer state was created for %d tables of dim %d",
-              op->T, op->D);
-    CHECK_ARG(grad_dtype == DLRM_F32 || grad_dtype == DLRM_BF16, "dlrm_adagrad_update: grad dtype %d", grad_dtype);
-    CHECK_ARG(grad_offset >= 0 && grad_ld >= grad_offset + (int64_t)tb->T * tb->D, "dlrm_adagrad_update: grad_ld too small");
-    CHECK_ARG(batch == 0 || tb->T == 0 || grad, "dlrm_adagrad_update: null grad");
-    if (flags & DLRM_UPDATE_ATOMIC)  // an atomic add never holds the row's whole sum, which the rule squares
-        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_adagrad_update: no atomic mode (the rule needs each row's complete sum)");
-    if (flags & DLRM_UPDATE_PREBUILT) {
-        if (!built_from(ix, indices, itype, table_stride, index_base, batch, lookups))
-            return ctx_fail(ctx, DLRM_E_STATE, "dlrm_adagrad_update: indexer was not built from these indices");
-        // a split backward stepped this build's once-hit rows with Descent and left their dt rows unwritten
-        if (ix->singles_done)
-            return ctx_fail(ctx, DLRM_E_STATE,
-                            "dlrm_adagrad_update: a split backward (dlrm_step_bwd) already stepped this build's "
-                            "once-hit rows with Descent");
-    } else {
-        rc = dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, lookups);
-        if (rc) return rc;
-    }
-    rc = ensure_partials(ctx, ix, tb->D);
-    if (rc) return rc;
-    // (a split indexer is taken whole: its once-hit positions as singles items)
-    const SinglesArgs sa{ix->split ? ix->dev.single : nullptr, indices, itype, table_stride, index_base,
-                         batch * lookups};
     if (op->rowwise)
-        return launch_rowwise_adagrad_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, op->d_state, tb->T, tb->D, tb->dtype,
+        return launch_rowwise_adagrad_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, op->d_ptr, tb->T, tb->D, tb->dtype,
                                             lookups, (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset,
                                             lr, eps, sa);
-    return launch_adagrad_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_state, tb->T, tb->D,
+    return launch_adagrad_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_ptr, tb->T, tb->D,
                                 tb->dtype, lookups, (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr,
                                 eps, sa);
 }
 
-// ------------------------------------------------------------------ split-bf16 tables
 int dlrm_split_sgd_create(dlrm_ctx* ctx, const dlrm_tables* tb, uint16_t* const* lo, dlrm_split_sgd** out) {
-    CHECK_ARG(ctx && tb && out, "dlrm_split_sgd_create: null argument");
-    *out = nullptr;
-    CHECK_ARG(tb->dtype == DLRM_BF16, "dlrm_split_sgd_create: split tables are bf16 (the high halves)");
-    CHECK_ARG(tb->T == 0 || lo, "dlrm_split_sgd_create: null low halves");
-    for (int t = 0; t < tb->T; ++t)
-        CHECK_ARG(lo[t] || tb->h_desc[t].nrows == 0, "dlrm_split_sgd_create: table %d has no low half", t);
-    dlrm_split_sgd* op = new (std::nothrow) dlrm_split_sgd();
-    if (!op) return DLRM_E_NOMEM;
-    op->T = tb->T;
-    op->D = tb->D;
-    op->h_lo.assign(lo, lo + tb->T);
-    // (rows of D uint16 from a 16-B aligned base: aligned when D % 8 == 0, which the vector kernels need anyway)
-    for (int t = 0; t < tb->T; ++t)
-        if ((uintptr_t)lo[t] % 16) op->aligned16 = false;
-    int rc = hip_set(ctx);
-    if (rc == DLRM_OK && tb->T > 0) {
-        rc = ctx_hip(ctx, hipMalloc((void**)&op->d_lo, sizeof(uint16_t*) * tb->T), "hipMalloc(split low halves)");
-        if (rc == DLRM_OK)
-            rc = ctx_hip(ctx, hipMemcpy(op->d_lo, op->h_lo.data(), sizeof(uint16_t*) * tb->T, hipMemcpyHostToDevice),
-                         "hipMemcpy(split low halves)");
-    }
-    if (rc != DLRM_OK) {
-        if (op->d_lo) (void)hipFree(op->d_lo);
-        delete op;
-        return rc;
-    }
-    *out = op;
-    return DLRM_OK;
+    return state_create(ctx, tb, true, lo, out, {"dlrm_split_sgd_create", "low halves", "low half", "split low halves"});
 }
 
-int dlrm_split_sgd_destroy(dlrm_split_sgd* op) {
-    if (!op) return DLRM_OK;
-    if (op->d_lo) (void)hipFree(op->d_lo);
-    delete op;
-    return DLRM_OK;
-}
+int dlrm_split_sgd_destroy(dlrm_split_sgd* op) { return state_destroy(op); }
 
 int dlrm_split_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dlrm_indexer* ix, unsigned flags,
                           const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
                           const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset, float lr) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_split_sgd_update: null ctx/tables/optimizer/indexer");
-    int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, lookups);
+    SinglesArgs sa;
+    bool atomic;
+    const int rc = update_prologue(ctx, tb, ix, kSplitUpdate, op, flags, indices, itype, table_stride, index_base, batch,
+                                   lookups, grad, grad_dtype, grad_ld, grad_offset, &sa, &atomic);
     if (rc) return rc;
-    CHECK_ARG(tb->dtype == DLRM_BF16, "dlrm_split_sgd_update: split tables are bf16 (the high halves)");
-    CHECK_ARG(op->T == tb->T && op->D == tb->D, "dlrm_split_sgd_update: the low halves were created for %d tables of dim %d",
-              op->T, op->D);
-    CHECK_ARG(grad_dtype == DLRM_F32 || grad_dtype == DLRM_BF16, "dlrm_split_sgd_update: grad dtype %d", grad_dtype);
-    CHECK_ARG(grad_offset >= 0 && grad_ld >= grad_offset + (int64_t)tb->T * tb->D, "dlrm_split_sgd_update: grad_ld too small");
-    CHECK_ARG(batch == 0 || tb->T == 0 || grad, "dlrm_split_sgd_update: null grad");
-    if (flags & DLRM_UPDATE_ATOMIC)  // an atomic add on one half cannot carry into the other
-        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_split_sgd_update: no atomic mode (a row's two halves are stepped together)");
-    if (flags & DLRM_UPDATE_PREBUILT) {
-        if (!built_from(ix, indices, itype, table_stride, index_base, batch, lookups))
-            return ctx_fail(ctx, DLRM_E_STATE, "dlrm_split_sgd_update: indexer was not built from these indices");
-        // a split backward wrote those rows' high halves with a rounded bf16 step and left their dt rows unwritten
-        if (ix->singles_done)
-            return ctx_fail(ctx, DLRM_E_STATE,
-                            "dlrm_split_sgd_update: a split backward (dlrm_step_bwd) already stepped this build's "
-                            "once-hit rows with a rounded bf16 Descent");
-    } else {
-        rc = dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, lookups);
-        if (rc) return rc;
-    }
-    rc = ensure_partials(ctx, ix, tb->D);
-    if (rc) return rc;
-    // (a split indexer is taken whole: its once-hit positions as singles items)
-    const SinglesArgs sa{ix->split ? ix->dev.single : nullptr, indices, itype, table_stride, index_base,
-                         batch * lookups};
-    return launch_split_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_lo, tb->T, tb->D, lookups,
+    return launch_split_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_ptr, tb->T, tb->D, lookups,
                                   (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr, sa);
 }
 

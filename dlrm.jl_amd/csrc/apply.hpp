@@ -41,22 +41,10 @@ struct ApplyGeom {
     static constexpr int NG = kApplyWaves * RPW;        // lane groups per workgroup
     static constexpr int SIF = NE == 8 ? kSliceIF / 2 : kSliceIF;  // hot slice rows in flight (bf16: 8 per 16 B)
     static constexpr int IF = VPL >= 4 ? 4 : (NE == 8 ? 8 : 16) / VPL;  // grad rows in flight per lane
-    // once-hit positions per lane group (a grad and a table row in flight for each)
+    // once-hit positions per lane group (a grad and a table row in flight for each; a rule with
+    // state in flight beside the table row takes fewer: its singles_ppg)
     static constexpr int SPPG = VPL * NE >= 16 ? 2 : (VPL * NE >= 8 ? 4 : 8);
 };
-// ... of a rule with state (kState != 0), a state row or word being in flight beside each table
-// row: half as many, a quarter for fp32 gradient rows (the row-wise rule: of one vector per lane).
-// The MODE 1 kernels sit at the 168-register limit of three workgroups per CU; at SPPG the Adagrad
-// instantiations spill up to 1300 registers to scratch, with these counts none does.
-template <typename G, int KSTATE>
-constexpr int singles_ppg() {
-    constexpr int DIV = G::NE == 4 && (KSTATE == 1 || G::VPL == 1) ? 4 : 2;
-    // The split rule's halves wait as bits, a row's two halves in the registers of Descent's fp32 row, so
-    // it keeps SPPG -- but for fp32 gradient rows of 16 vectors (D = 64), whose MODE 1 kernel spilt 4
-    // registers at SPPG = 8: half as many there.
-    if (KSTATE == 3) return G::NE == 4 && G::LPR == 16 ? G::SPPG / 2 : G::SPPG;
-    return KSTATE == 0 ? G::SPPG : (G::SPPG >= DIV ? G::SPPG / DIV : 1);
-}
 
 // Cross-workgroup hand-off of slice partials (cdna_hip_programming.md Guideline 16, R1/R2):
 // payload stored write-through (agent-scope atomic stores = sc1), the storing wave drains
@@ -97,43 +85,15 @@ __device__ __forceinline__ void add_vec(float* acc, const typename Vec<GT>::type
 //   Descent         w = fmaf(-lr, G, w)
 //   Adagrad         A += G^2 (element-wise, fp32 [nrows][D]);   w -= lr G / (sqrt(A) + eps)
 //   RowwiseAdagrad  m += (1/D) sum_c G[c]^2 (fp32 [nrows]);      w -= lr G / (sqrt(m) + eps)
-// kState: 0 none, 1 a state row per table row, 2 a state word per table row, 3 a row of low halves per
-// table row.  The state is loaded
-// where the table row is (beside the grad rows: these items are bound by dependent round trips)
-// and written once, with the row.  The row-wise sum of squares has a fixed order per site: a lane's
-// elements in element order, then an xor butterfly over the lanes holding the row (every level one
-// commutative add, so every lane ends with the same bits), then (slices of D > 256) the waves in
-// wave order.
 //   SplitDescent    W = bits(hi << 16 | lo);  W' = fmaf(-lr, G, W);  hi' = bits(W') >> 16, lo' = bits(W') & 0xffff
-//                   (kState 3: hi = the bf16 table's element, lo = a uint16 [nrows][D] state row: the table
-//                   holds the truncated high half of an fp32 master weight, the step is Descent's on fp32)
-struct Descent {
-    float lr;
-    typedef float State;
-    static constexpr int kState = 0;
-    __device__ __forceinline__ float* base(int) const { return nullptr; }
-};
-struct Adagrad {
-    float lr, eps;
-    float* const* state;  // [T] device pointers, fp32 [nrows][D]
-    typedef float State;
-    static constexpr int kState = 1;
-    __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
-};
-struct RowwiseAdagrad {
-    float lr, eps;
-    float* const* state;  // [T] device pointers, fp32 [nrows]
-    typedef float State;
-    static constexpr int kState = 2;
-    __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
-};
-struct SplitDescent {
-    float lr;
-    uint16_t* const* lo;  // [T] device pointers, uint16 [nrows][D]: the low halves
-    typedef uint16_t State;
-    static constexpr int kState = 3;
-    __device__ __forceinline__ uint16_t* base(int t) const { return ldg<uint16_t*>(lo + t); }
-};
+//                   (hi = the bf16 table's element, lo = a uint16 [nrows][D] state row: the table holds
+//                   the truncated high half of an fp32 master weight, the step is Descent's on fp32)
+// A rule holds its parameters, its state's row address (state_row), its once-hit positions per lane group
+// (singles_ppg), the any-D kernels' write of one column (scalar_write) and the MODEs and table element types
+// it is instantiated for (kCarriesBuild, kF32Tables).  The vector items below still branch on kState (0 none,
+// 1 a state row per table row, 2 a state word, 3 a row of low halves): written once over a per-rule row type
+// they no longer compiled to the same code.  The state is loaded where the table row
+// is (beside the grad rows: these items are bound by dependent round trips) and written once, with the row.
 
 // N (4 or 8) consecutive 16-bit halves of a split row, kept as raw bits in one 8-B or 16-B vector (half
 // the registers of their fp32 values while they wait beside the grad rows).
@@ -204,6 +164,107 @@ __device__ __forceinline__ float sum_squares(const float* g, float ss) {
 // the row-wise accumulator after a row whose squares sum to ss, and the row's step size
 __device__ __forceinline__ float rowwise_m(float m, float ss, int D) { return m + ss / (float)D; }
 __device__ __forceinline__ float rowwise_scale(float lr, float eps, float m) { return lr / (__builtin_sqrtf(m) + eps); }
+
+// A rule with a state row or word in flight beside each table row takes SPPG / DIV once-hit positions per
+// lane group.  The MODE 1 kernels sit at the 168-register limit of three workgroups per CU; at SPPG the
+// Adagrad instantiations spill up to 1300 registers to scratch, with these counts none does.
+constexpr int fewer_singles(int sppg, int div) { return sppg >= div ? sppg / div : 1; }
+
+struct Descent {
+    float lr;
+    typedef float State;
+    static constexpr int kState = 0;  // (the items' per-rule branches: 0 none, 1 a state row, 2 a state word, 3 low halves)
+    static constexpr bool kCarriesBuild = true;  // MODE >= 2: the next batch's build rides on its launches
+    static constexpr bool kF32Tables = true;
+    __device__ __forceinline__ float* base(int) const { return nullptr; }
+    template <int D> __device__ static __forceinline__ float* state_row(float*, uint32_t) { return nullptr; }
+    template <typename G> static constexpr int singles_ppg() { return G::SPPG; }
+    static constexpr int scalar_threads(int D) { return D; }  // any-D kernels: threads per row
+    template <typename TT, typename F>
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float*, int64_t, int, int c, F&& colsum) const {
+        row[c] = from_f32<TT>(__builtin_fmaf(-lr, colsum(c), to_f32(row[c])));
+    }
+};
+
+struct Adagrad {
+    float lr, eps;
+    float* const* state;  // [T] device pointers, fp32 [nrows][D]
+    typedef float State;
+    static constexpr int kState = 1;
+    static constexpr bool kCarriesBuild = false;
+    static constexpr bool kF32Tables = true;
+    __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
+    template <int D> __device__ static __forceinline__ float* state_row(float* st, uint32_t r) { return st + (int64_t)r * D; }
+    // (a state row per table row: a quarter of SPPG for fp32 gradient rows, else half)
+    template <typename G> static constexpr int singles_ppg() { return fewer_singles(G::SPPG, G::NE == 4 ? 4 : 2); }
+    static constexpr int scalar_threads(int D) { return D; }
+    template <typename TT, typename F>
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float* __restrict__ st, int64_t r, int D, int c,
+                                                 F&& colsum) const {
+        const float g = colsum(c);
+        float a = st[r * D + c], w = to_f32(row[c]);
+        adagrad_step<1>(lr, eps, &g, &a, &w);
+        st[r * D + c] = a;
+        row[c] = from_f32<TT>(w);
+    }
+};
+
+// The row-wise sum of squares has a fixed order per site: a lane's elements in element order, then an
+// xor butterfly over the lanes holding the row (every level one commutative add, so every lane ends
+// with the same bits), then (slices of D > 256) the waves in wave order.
+struct RowwiseAdagrad {
+    float lr, eps;
+    float* const* state;  // [T] device pointers, fp32 [nrows]
+    typedef float State;
+    static constexpr int kState = 2;
+    static constexpr bool kCarriesBuild = false;
+    static constexpr bool kF32Tables = true;
+    __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
+    template <int D> __device__ static __forceinline__ float* state_row(float* st, uint32_t r) { return st + r; }
+    // (a state word per table row: a quarter of SPPG for fp32 gradient rows of one vector per lane, else half)
+    template <typename G> static constexpr int singles_ppg() { return fewer_singles(G::SPPG, G::NE == 4 && G::VPL == 1 ? 4 : 2); }
+    static constexpr int scalar_threads(int) { return 1; }  // (two passes over the row's sums)
+    // (c = 0: the thread has the whole row; the squares in column order, then the step)
+    template <typename TT, typename F>
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float* __restrict__ st, int64_t r, int D, int,
+                                                 F&& colsum) const {
+        float ss = 0.0f;
+        for (int k = 0; k < D; ++k) {
+            const float g = colsum(k);
+            ss = __builtin_fmaf(g, g, ss);
+        }
+        const float m = rowwise_m(st[r], ss, D);
+        const float s = rowwise_scale(lr, eps, m);
+        st[r] = m;
+        for (int k = 0; k < D; ++k) row[k] = from_f32<TT>(__builtin_fmaf(-s, colsum(k), to_f32(row[k])));
+    }
+};
+
+struct SplitDescent {
+    float lr;
+    uint16_t* const* lo;  // [T] device pointers, uint16 [nrows][D]: the low halves
+    typedef uint16_t State;
+    static constexpr int kState = 3;
+    static constexpr bool kCarriesBuild = false;
+    static constexpr bool kF32Tables = false;  // split rows live in bf16 tables
+    __device__ __forceinline__ uint16_t* base(int t) const { return ldg<uint16_t*>(lo + t); }
+    template <int D> __device__ static __forceinline__ uint16_t* state_row(uint16_t* st, uint32_t r) { return st + (int64_t)r * D; }
+    // The split rule's halves wait as bits, a row's two halves in the registers of Descent's fp32 row, so
+    // it keeps SPPG -- but for fp32 gradient rows of 16 vectors (D = 64), whose MODE 1 kernel spilt 4
+    // registers at SPPG = 8: half as many there.
+    template <typename G> static constexpr int singles_ppg() { return G::NE == 4 && G::LPR == 16 ? G::SPPG / 2 : G::SPPG; }
+    static constexpr int scalar_threads(int D) { return D; }
+    template <typename TT, typename F>
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, uint16_t* __restrict__ st, int64_t r, int D, int c,
+                                                 F&& colsum) const {
+        static_assert(sizeof(TT) == 2, "split rows live in bf16 tables");
+        const float g = colsum(c);
+        uint16_t h = ldg<uint16_t>(row + c), l = ldg<uint16_t>(st + r * D + c);
+        split_step1(lr, g, h, l);
+        stg<uint16_t>(row + c, h);
+        stg<uint16_t>(st + r * D + c, l);
+    }
+};
 
 // ---- a chunk, by one lane group (lane v of LPR; gl0 = the group's first lane in the wave)
 template <typename TT, typename GT, int VPR, typename R>
@@ -323,7 +384,7 @@ __device__ __forceinline__ void run_singles(const SinglesArgs& sa, int64_t cap, 
                                             const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L,
                                             const R& rule, int v, int gl0) {
     typedef ApplyGeom<GT, VPR> G;
-    constexpr int NE = G::NE, D = G::D, LPR = G::LPR, PPG = singles_ppg<G, R::kState>();
+    constexpr int NE = G::NE, D = G::D, LPR = G::LPR, PPG = R::template singles_ppg<G>();
     constexpr int KX = (PPG + LPR - 1) / LPR;
     uint32_t pr[KX];  // the row of position p0 + k*LPR + v, ~0u when it is not a single
 #pragma unroll
@@ -634,11 +695,6 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
 
 // ---- a slice of a hot segment located by (virtual table vt, local slice sl): sd = {p0, p1,
 // row, h}; the segment's descriptor ix.hot[vt][h] = {beg, end, row, first slice}
-template <int KSTATE, int D, typename S>
-__device__ __forceinline__ S* state_row(S* st, uint32_t r) {
-    return KSTATE == 1 || KSTATE == 3 ? st + (int64_t)r * D : (KSTATE == 2 ? st + r : nullptr);
-}
-
 template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_slice(const IndexerDev& ix, int vt, int sl, const int4& sd, TT* __restrict__ table,
                                           typename R::State* __restrict__ st, const GT* __restrict__ gbase, int64_t grad_ld,
@@ -649,7 +705,7 @@ __device__ __forceinline__ void run_slice(const IndexerDev& ix, int vt, int sl, 
     const int ns = (hd.y - hd.x + kHotSlice - 1) / kHotSlice;
     float* pbase = ix.partial + (int64_t)vt * ix.pcap * ix.pdim;
     slice_body<TT, GT, VPR, R>(ix.perm + off + sd.x, sd.y - sd.x, table + (int64_t)(uint32_t)sd.z * D,
-                               state_row<R::kState, D>(st, (uint32_t)sd.z), ns, pbase + (int64_t)sl * ix.pdim,
+                               R::template state_row<D>(st, (uint32_t)sd.z), ns, pbase + (int64_t)sl * ix.pdim,
                                pbase + (int64_t)hd.w * ix.pdim, ix.pdim, ix.hot_cnt + off + sd.w, gbase, grad_ld, L,
                                rule, sm);
 }
@@ -663,7 +719,7 @@ __device__ __forceinline__ void run_slice_rec(const IndexerDev& ix, int k, int f
                                               const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
     constexpr int D = ApplyGeom<GT, VPR>::D;
     slice_body<TT, GT, VPR, R>(ix.perm + r0.x, r0.y - r0.x, table + (int64_t)(uint32_t)r0.z * D,
-                               state_row<R::kState, D>(st, (uint32_t)r0.z), r1.x, ix.partial + (int64_t)k * ix.pdim,
+                               R::template state_row<D>(st, (uint32_t)r0.z), r1.x, ix.partial + (int64_t)k * ix.pdim,
                                ix.partial + (int64_t)first * ix.pdim, ix.pdim, ix.hot_cnt + first, gbase, grad_ld, L,
                                rule, sm);
 }

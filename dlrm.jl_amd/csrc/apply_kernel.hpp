@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
                                                                   int64_t grad_offset, R rule,
                                                                   const unsigned* __restrict__ err, SinglesArgs sa,
                                                                   PrepArgs pa) {
-    static_assert(R::kState == 0 || MODE <= 1, "the next batch's build rides on Descent launches only");
+    static_assert(R::kCarriesBuild || MODE <= 1, "the next batch's build rides on Descent launches only");
     constexpr bool SG = MODE == 1;
     int bid = blockIdx.x, nblk = gridDim.x;
     if constexpr (MODE >= 2) {
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
     }
     if (err0) return;
     const int citems = Stot + (Ctot + NG - 1) / NG;
-    constexpr int PPG = singles_ppg<G, R::kState>();           // once-hit positions per lane group
+    constexpr int PPG = R::template singles_ppg<G>();          // once-hit positions per lane group
     constexpr int SP = NG * PPG;                               // positions per singles item
     const int per_t = SG ? (sa.N + SP - 1) / SP : 0;          // singles items per real table
     const int items = citems + (T_ >> ix.vshift) * per_t;
@@ -227,40 +227,8 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
 }
 
 
-// Generic (any D) versions: one thread per element column; the row-wise rule one thread per row
-// (two passes over the row's sums: the squares in column order, then the step).
-// The write of column c of row r (kState 2: of the whole row), colsum(c) = the column's gradient sum.
-template <typename TT, typename R, typename F>
-__device__ __forceinline__ void scalar_write(const R& rule, TT* __restrict__ row, typename R::State* __restrict__ st,
-                                             int64_t r, int D, int c, F&& colsum) {
-    if constexpr (R::kState == 0) {
-        row[c] = from_f32<TT>(__builtin_fmaf(-rule.lr, colsum(c), to_f32(row[c])));
-    } else if constexpr (R::kState == 3) {
-        static_assert(sizeof(TT) == 2, "split rows live in bf16 tables");
-        const float g = colsum(c);
-        uint16_t hi = ldg<uint16_t>(row + c), lo = ldg<uint16_t>(st + r * D + c);
-        split_step1(rule.lr, g, hi, lo);
-        stg<uint16_t>(row + c, hi);
-        stg<uint16_t>(st + r * D + c, lo);
-    } else if constexpr (R::kState == 1) {
-        const float g = colsum(c);
-        float a = st[r * D + c], w = to_f32(row[c]);
-        adagrad_step<1>(rule.lr, rule.eps, &g, &a, &w);
-        st[r * D + c] = a;
-        row[c] = from_f32<TT>(w);
-    } else {
-        float ss = 0.0f;
-        for (int k = 0; k < D; ++k) {
-            const float g = colsum(k);
-            ss = __builtin_fmaf(g, g, ss);
-        }
-        const float m = rowwise_m(st[r], ss, D);
-        const float lr = rowwise_scale(rule.lr, rule.eps, m);
-        st[r] = m;
-        for (int k = 0; k < D; ++k) row[k] = from_f32<TT>(__builtin_fmaf(-lr, colsum(k), to_f32(row[k])));
-    }
-}
-
+// Generic (any D) versions: R::scalar_threads(D) threads per row (one per element column; the row-wise
+// rule one per row), each calling the rule's scalar_write with colsum(c) = column c's gradient sum.
 template <typename TT, typename GT, typename R>
 __global__ __launch_bounds__(256) void sgd_chunks_scalar(IndexerDev ix, TableDesc* __restrict__ tabs, int D, int L,
                                                          const GT* __restrict__ grad, int64_t grad_ld,
@@ -273,14 +241,14 @@ __global__ __launch_bounds__(256) void sgd_chunks_scalar(IndexerDev ix, TableDes
     const int t = blockIdx.y;
     const int nchunks = ix.counts[(int64_t)t * 8 + CNT_C];
     const int64_t off = ix.part_off(t);
-    const int W = R::kState == 2 ? 1 : D;  // threads per row
+    const int W = R::scalar_threads(D);  // threads per row
     const int64_t total = (int64_t)nchunks * W;
     TT* table = (TT*)tabs[t >> ix.vshift].data;
     typename R::State* st = rule.base(t >> ix.vshift);
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int cid = (int)(e / W);
         const int4 cd = ix.chunks[2 * (off + cid)];
-        scalar_write<TT>(rule, table + (int64_t)(uint32_t)cd.z * D, st, (int64_t)(uint32_t)cd.z, D, (int)(e % W), [&](int c) {
+        rule.scalar_write(table + (int64_t)(uint32_t)cd.z * D, st, (int64_t)(uint32_t)cd.z, D, (int)(e % W), [&](int c) {
             float acc = 0.0f;
             for (int i = cd.x; i < cd.y; ++i)
                 acc += to_f32(grad[(int64_t)(ix.perm[off + i] / L) * grad_ld + grad_offset + (int64_t)(t >> ix.vshift) * D + c]);
@@ -297,14 +265,14 @@ __global__ __launch_bounds__(256) void sgd_hot_scalar(IndexerDev ix, TableDesc* 
     const int t = blockIdx.y;
     const int nhot = ix.counts[(int64_t)t * 8 + CNT_H];
     const int64_t off = ix.part_off(t);
-    const int W = R::kState == 2 ? 1 : D;  // threads per row
+    const int W = R::scalar_threads(D);  // threads per row
     const int64_t total = (int64_t)nhot * W;
     TT* table = (TT*)tabs[t >> ix.vshift].data;
     typename R::State* st = rule.base(t >> ix.vshift);
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int h = (int)(e / W);
         const int4 hd = ix.hot[off + h];
-        scalar_write<TT>(rule, table + (int64_t)(uint32_t)hd.z * D, st, (int64_t)(uint32_t)hd.z, D, (int)(e % W), [&](int c) {
+        rule.scalar_write(table + (int64_t)(uint32_t)hd.z * D, st, (int64_t)(uint32_t)hd.z, D, (int)(e % W), [&](int c) {
             float acc = 0.0f;
             for (int i = hd.x; i < hd.y; ++i)
                 acc += to_f32(grad[(int64_t)(ix.perm[off + i] / L) * grad_ld + grad_offset + (int64_t)(t >> ix.vshift) * D + c]);
@@ -320,7 +288,7 @@ __global__ __launch_bounds__(256) void sgd_singles_scalar(SinglesArgs sa, int64_
                                                           const unsigned* __restrict__ err) {
     if (*err) return;
     const int t = blockIdx.y;
-    const int W = R::kState == 2 ? 1 : D;  // threads per position
+    const int W = R::scalar_threads(D);  // threads per position
     const int64_t total = (int64_t)sa.N * W;
     TT* table = (TT*)tabs[t].data;
     typename R::State* st = rule.base(t);
@@ -329,7 +297,7 @@ __global__ __launch_bounds__(256) void sgd_singles_scalar(SinglesArgs sa, int64_
         if (!sa.single[(int64_t)t * cap + p]) continue;
         const int64_t r = load_index(sa.idx, sa.itype, (int64_t)t * sa.tstride + p) - sa.base;
         if (r < 0 || r >= tabs[t].nrows) continue;
-        scalar_write<TT>(rule, table + r * D, st, r, D, (int)(e % W), [&](int c) {
+        rule.scalar_write(table + r * D, st, r, D, (int)(e % W), [&](int c) {
             return 0.0f + to_f32(grad[(int64_t)(p / L) * grad_ld + grad_offset + (int64_t)t * D + c]);
         });
     }
@@ -339,14 +307,14 @@ __global__ __launch_bounds__(256) void sgd_singles_scalar(SinglesArgs sa, int64_
 // the apply launch that also carries the next batch's build (MODE >= 2): build workgroups first
 template <typename TT, typename GT, int VPR, int MODE>
 static void launch_apply_build(hipStream_t s, unsigned grid, const IndexerDev& ix, TableDesc* tabs, int T_, int L,
-                               const void* grad, int64_t grad_ld, int64_t grad_offset, float lr, const unsigned* err,
-                               const SinglesArgs& sa, const PrepArgs& pa) {
+                               const void* grad, int64_t grad_ld, int64_t grad_offset, const Descent& rule,
+                               const unsigned* err, const SinglesArgs& sa, const PrepArgs& pa) {
     static const hipError_t attr = hipFuncSetAttribute((const void*)sgd_apply_kernel<TT, GT, VPR, MODE>,
                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                                        (int)sizeof(WaveBuildLds));
     (void)attr;
     hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, MODE>), dim3(grid), dim3(kApplyThreads), sizeof(WaveBuildLds), s,
-                       ix, tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, Descent{lr}, err, sa, pa);
+                       ix, tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, rule, err, sa, pa);
 }
 
 template <typename TT, typename GT, int VPR, typename R>
@@ -356,7 +324,7 @@ static void launch_apply_vec(hipStream_t s, const IndexerDev& ix, TableDesc* tab
     typedef ApplyGeom<GT, VPR> G;
     // persistent grid: resident workgroups only (never more than the worst-case item count per
     // table: N / kHotSlice + N / (kChunk + 1) + 1 hot slices, N / NG chunk items, singles items)
-    const int64_t SP = G::NG * singles_ppg<G, R::kState>();
+    const int64_t SP = G::NG * R::template singles_ppg<G>();
     const int64_t ib = (int64_t)T_ * (N / kHotSlice + N / (kMinChunk + 1) + 1 + (N + G::NG - 1) / G::NG) +
                        (sa.single ? (int64_t)(T_ >> ix.vshift) * ((N + SP - 1) / SP) : 0);
     static int per_cu = 0;
@@ -373,32 +341,25 @@ static void launch_apply_vec(hipStream_t s, const IndexerDev& ix, TableDesc* tab
     if (grid < 1) grid = 1;
     // (the once-hit items and the next batch's indexer are separate instantiations: the step's
     // apply stays lean)
-    if constexpr (R::kState != 0) {
-        // the Adagrad rules: MODE 0 and 1 only; a next batch's build gets its own launch
-        if (sa.single)
-            hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, 1, R>), dim3((unsigned)grid), dim3(kApplyThreads), 0, s, ix,
-                               tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, rule, err, sa, PrepArgs{});
-        else
-            hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, 0, R>), dim3((unsigned)grid), dim3(kApplyThreads), 0, s, ix,
-                               tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, rule, err, sa, PrepArgs{});
-        if (pa) launch_step_index(s, *pa);
-    } else if (pa && !sa.single) {
-        const float lr = rule.lr;
-        // MODE 2: <= 2048 positions per table; above, 2 + wave_big_kind (3 rounds, 5 scan)
-        const int mode = pa->N <= kStepIndexMaxN ? 2 : 2 + wave_big_kind(*pa);
-        const unsigned g2 = (unsigned)(grid + prep_groups(*pa));
-        if (mode == 2) launch_apply_build<TT, GT, VPR, 2>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, err, sa, *pa);
-        else if (mode == 5) launch_apply_build<TT, GT, VPR, 5>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, err, sa, *pa);
-        else launch_apply_build<TT, GT, VPR, 3>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, lr, err, sa, *pa);
-    } else if (sa.single) {
+    if constexpr (R::kCarriesBuild) {
+        if (pa && !sa.single) {
+            // MODE 2: <= 2048 positions per table; above, 2 + wave_big_kind (3 rounds, 5 scan)
+            const int mode = pa->N <= kStepIndexMaxN ? 2 : 2 + wave_big_kind(*pa);
+            const unsigned g2 = (unsigned)(grid + prep_groups(*pa));
+            if (mode == 2) launch_apply_build<TT, GT, VPR, 2>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, *pa);
+            else if (mode == 5) launch_apply_build<TT, GT, VPR, 5>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, *pa);
+            else launch_apply_build<TT, GT, VPR, 3>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, *pa);
+            return;
+        }
+    }
+    if (sa.single)
         hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, 1, R>), dim3((unsigned)grid), dim3(kApplyThreads), 0, s, ix,
                            tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, rule, err, sa, PrepArgs{});
-        // MODE 2 has no once-hit items: the next batch's build (if any) gets its own launch
-        if (pa) launch_step_index(s, *pa);
-    } else {
+    else
         hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, 0, R>), dim3((unsigned)grid), dim3(kApplyThreads), 0, s, ix,
                            tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, rule, err, sa, PrepArgs{});
-    }
+    // no MODE carries both once-hit items and the next batch's build: that build gets its own launch
+    if (pa) launch_step_index(s, *pa);
 }
 
 template <typename TT, typename GT, typename R>
@@ -412,6 +373,15 @@ static bool dispatch_apply(int vpr, hipStream_t s, const IndexerDev& ix, TableDe
         default: return false;
     }
 #undef DLRM_CASE
+}
+
+// f(TT(), GT()) for the table and gradient element types (a rule without kF32Tables: bf16 tables, the caller checked)
+template <typename R, typename F>
+static void by_dtypes(int tdtype, int gdtype, F&& f) {
+    if constexpr (R::kF32Tables) {
+        if (tdtype == DLRM_F32) return gdtype == DLRM_F32 ? f(float(), float()) : f(float(), uint16_t());
+    }
+    return gdtype == DLRM_F32 ? f(uint16_t(), float()) : f(uint16_t(), uint16_t());
 }
 
 // tabs_aligned16: every table row (and, for the element-wise Adagrad and the split rule, every state row) is
@@ -432,21 +402,10 @@ static int launch_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tab
     const int64_t slots = (int64_t)T_ * (N + 1);  // (item counts stay in int)
     if (aligned && slots < (1ll << 31)) {
         const int vpr = D * gesz / 16;
-        if constexpr (R::kState == 3) {  // (bf16 tables only: the caller checked)
-            if (gdtype == DLRM_F32)
-                done = dispatch_apply<uint16_t, float, R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N, err, sa, pa);
-            else
-                done = dispatch_apply<uint16_t, uint16_t, R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N,
-                                                             err, sa, pa);
-        } else if (tdtype == DLRM_F32 && gdtype == DLRM_F32)
-            done = dispatch_apply<float, float, R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N, err, sa, pa);
-        else if (tdtype == DLRM_BF16 && gdtype == DLRM_F32)
-            done = dispatch_apply<uint16_t, float, R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N, err, sa, pa);
-        else if (tdtype == DLRM_F32 && gdtype == DLRM_BF16)
-            done = dispatch_apply<float, uint16_t, R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N, err, sa, pa);
-        else
-            done = dispatch_apply<uint16_t, uint16_t, R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N,
-                                                         err, sa, pa);
+        by_dtypes<R>(tdtype, gdtype, [&](auto tt, auto gt) {
+            done = dispatch_apply<decltype(tt), decltype(gt), R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N,
+                                                                 err, sa, pa);
+        });
     }
     if (!done && pa) launch_step_index(s, *pa);
     if (!done) {
@@ -454,22 +413,17 @@ static int launch_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tab
         const unsigned gx = (unsigned)(gx0 < 1 ? 1 : (gx0 > 4096 ? 4096 : gx0));
         const int64_t hx0 = ((N / (kChunk + 1)) * D + 255) / 256;
         const unsigned hx = (unsigned)(hx0 < 1 ? 1 : (hx0 > 1024 ? 1024 : hx0));
-#define DLRM_SCALAR(TT, GT)                                                                                         \
-    hipLaunchKernelGGL((sgd_chunks_scalar<TT, GT, R>), dim3(gx, T_), dim3(256), 0, s, ix, tabs, D, L, (const GT*)grad, \
-                       grad_ld, grad_offset, rule, err);                                                            \
-    hipLaunchKernelGGL((sgd_hot_scalar<TT, GT, R>), dim3(hx, T_), dim3(256), 0, s, ix, tabs, D, L, (const GT*)grad, \
-                       grad_ld, grad_offset, rule, err);                                                            \
-    if (sa.single)                                                                                                  \
-        hipLaunchKernelGGL((sgd_singles_scalar<TT, GT, R>), dim3(gx, T_ >> ix.vshift), dim3(256), 0, s, sa, ix.cap, \
-                           tabs, D, L, (const GT*)grad, grad_ld, grad_offset, rule, err);
-        if constexpr (R::kState == 3) {
-            if (gdtype == DLRM_F32) { DLRM_SCALAR(uint16_t, float) }
-            else { DLRM_SCALAR(uint16_t, uint16_t) }
-        } else if (tdtype == DLRM_F32 && gdtype == DLRM_F32) { DLRM_SCALAR(float, float) }
-        else if (tdtype == DLRM_BF16 && gdtype == DLRM_F32) { DLRM_SCALAR(uint16_t, float) }
-        else if (tdtype == DLRM_F32 && gdtype == DLRM_BF16) { DLRM_SCALAR(float, uint16_t) }
-        else { DLRM_SCALAR(uint16_t, uint16_t) }
-#undef DLRM_SCALAR
+        by_dtypes<R>(tdtype, gdtype, [&](auto tt, auto gt) {
+            typedef decltype(tt) TT;
+            typedef decltype(gt) GT;
+            hipLaunchKernelGGL((sgd_chunks_scalar<TT, GT, R>), dim3(gx, T_), dim3(256), 0, s, ix, tabs, D, L,
+                               (const GT*)grad, grad_ld, grad_offset, rule, err);
+            hipLaunchKernelGGL((sgd_hot_scalar<TT, GT, R>), dim3(hx, T_), dim3(256), 0, s, ix, tabs, D, L, (const GT*)grad,
+                               grad_ld, grad_offset, rule, err);
+            if (sa.single)
+                hipLaunchKernelGGL((sgd_singles_scalar<TT, GT, R>), dim3(gx, T_ >> ix.vshift), dim3(256), 0, s, sa, ix.cap,
+                                   tabs, D, L, (const GT*)grad, grad_ld, grad_offset, rule, err);
+        });
     }
     return ctx_hip(ctx, hipGetLastError(), "sgd_apply launch");
 }
