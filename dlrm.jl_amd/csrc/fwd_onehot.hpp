@@ -9,6 +9,24 @@
 #ifndef WT
 #define WT(kind, slot, b) do {} while (0)
 #endif
+// The forward's timeline (DLRM_WTRACE build only): six stamps per wave, kept in registers and
+// written after the output stores -- a store between the row loads would sit in the same in-order
+// vmcnt queue as the loads and disturb what is measured.  WTS_USE(v) makes the stamp that follows
+// wait for v (a loaded fragment, an accumulator).
+#ifdef DLRM_WTRACE
+#define WTS_DECL unsigned long long wts_[6] = {0, 0, 0, 0, 0, 0}
+#define WTS_USE(v) do { __builtin_amdgcn_sched_barrier(0); asm volatile("" ::"v"(v)); } while (0)
+#define WTS(slot) do { __builtin_amdgcn_sched_barrier(0); wts_[slot] = wall_clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
+// (in the column-step loop of fwd_body_onehot: step v's fragments have landed; first and last step)
+#define WTS_LANDED(v) do { if (u0 == 0 && ((v) == 0 || (v) == UV - 1)) { _Pragma("unroll") for (int I_ = 0; I_ < NB; ++I_) WTS_USE(a[v][I_]); WTS((v) == 0 ? 2 : 3); } } while (0)
+#define WTS_FLUSH(kind, b) do { if ((threadIdx.x & 63) == 0 && (b) < 8192) { _Pragma("unroll") for (int s_ = 0; s_ < 6; ++s_) g_wt[kind][s_][b] = wts_[s_]; } } while (0)
+#else
+#define WTS_DECL do {} while (0)
+#define WTS_USE(v) do {} while (0)
+#define WTS(slot) do {} while (0)
+#define WTS_LANDED(v) do {} while (0)
+#define WTS_FLUSH(kind, b) do {} while (0)
+#endif
 
 namespace dlrm {
 
@@ -88,6 +106,11 @@ struct GatherArgs {
 // The compiler's own schedule interleaved one load, a wait and its MFMAs (one 1-KB load in flight
 // per wave: the row stream ran at 2 TB/s); the sched_barriers pin the order
 //   index / table loads | row loads | MFMAs | x staging.
+// WIN (column steps in flight; 0 or >= UV: all of them, the order above): a rolling window --
+// steps 0 .. WIN-1 are issued, then per step v in ascending order its MFMAs (behind the compiler's
+// vmcnt wait) and the loads of step v + WIN.  Every fragment keeps its own registers (a[UV][NB]:
+// the x staging and the ys rows read them after the MFMAs) and every accumulator its order, so
+// the output bits do not depend on WIN.
 // Row 0 of T is x itself: it arrives with the rows, and the output's x head (fast_vcat) is
 // staged from those fragments instead of a second load of x.
 // Summation order (every forward kernel, so all forms agree bit for bit): for F <= 32 (NB <= 2)
@@ -139,7 +162,7 @@ template <typename T, int NB> struct FwdPart {
 // TP: the table pointers / row counts from a TabPtrs kernel argument (else from ga.tabs).
 // DEFER: raise the bounds flag after the stores instead of where the index is checked.
 template <typename T, int NB, bool FUSED, int WPB, int DC = 0, int WPS = 1, bool CONTIG = false, bool TP = false,
-          bool DEFER = false>
+          bool DEFER = false, int WIN_ = 0>
 __device__ __forceinline__ void fwd_body_onehot(int bid, int nblocks, float* stage_all, int d_, int F, int B,
                                                 const T* __restrict__ x, int64_t x_ld, T* __restrict__ ys,
                                                 int64_t ys_ld, T* __restrict__ out, int64_t out_ld, int padding,
@@ -174,21 +197,14 @@ __device__ __forceinline__ void fwd_body_onehot(int bid, int nblocks, float* sta
 #define DLRM_FWD_VEC_ROW 1
 #endif
     constexpr bool VEC_ROW = DLRM_FWD_VEC_ROW && sizeof(T) == 4 && DC >= 128;
-    // EARLY: the first Gram tile (pairs i < 16) and x go out while the MFMAs of the other two tiles
-    // run: tile-outer MFMA order (each tile's summation order unchanged: bit-identical output)
-#ifndef DLRM_FWD_EARLY
-#define DLRM_FWD_EARLY 0
-#endif
-    constexpr bool EARLY = DLRM_FWD_EARLY && VEC_ROW && WPS == 1 && !CONTIG && NB == 2 && DC > 0 && DC == CBLK;
-    const int F16 = F < 16 ? F : 16;
-    const int E1 = d + F16 * (F16 - 1) / 2;  // EARLY: x + the pairs of tile 00
     const bool vec_out = W % 4 == 0 && out_ld % 4 == 0 && ((uintptr_t)out & (4 * sizeof(T) - 1)) == 0;
     bool bad_any = false;  // an out-of-range index was skipped (zero row) by this lane
     for (int64_t b0 = (int64_t)bid * SPB; b0 < B; b0 += (int64_t)nblocks * SPB) {
         const int64_t bs = b0 + pair;
         const bool live = bs < B;
         const int64_t b = live ? bs : B - 1;  // a padding sample (WPS = 2) re-reads a real one, stores nothing
-        if (h == 0) WT(0, 0, b);
+        WTS_DECL;
+        WTS(0);
         const T* xb = x + b * x_ld;
         T* yb = (ys && live) ? ys + b * ys_ld : nullptr;
         T* orow = out + b * out_ld;
@@ -224,6 +240,9 @@ __device__ __forceinline__ void fwd_body_onehot(int bid, int nblocks, float* sta
                 src[I] = row == 0 ? xb : (row < F ? ys + b * ys_ld + (int64_t)row * d : nullptr);
             }
         }
+#pragma unroll
+        for (int I = 0; I < NB; ++I) WTS_USE(src[I]);
+        WTS(1);
         // acc[p][ij]: partial p (column-step parity) of tile ij; WPS = 2 keeps only its own
         constexpr int NPART = (WPS == 1 && NB <= 2) ? 2 : 1;  // NB > 2: one chain (registers)
         f32x4_t acc[NPART][NT];
@@ -235,65 +254,64 @@ __device__ __forceinline__ void fwd_body_onehot(int bid, int nblocks, float* sta
             // this wave's column steps of the block: interleaved uu = WPS * v + h, or CONTIG
             // (contiguous halves) uu = h * UV + v
             constexpr int UV = UU / WPS;
+            constexpr int WIN = (WIN_ > 0 && WIN_ < UV) ? WIN_ : UV;
             __builtin_amdgcn_sched_barrier(0);
             frag a[UV][NB];
+            if constexpr (WIN < UV) {
+                // the rolling window: the row loads of column step v (fragments a[v][*]; every step
+                // is inside d here: DC > 0 and UV steps cover it)
+                static_assert(DC > 0 && WPS == 1 && !CONTIG && UU * FR::COLS == DC, "window: fixed-size kernels");
+                auto load_step = [&](int v) {
+                    const int col = v * FR::COLS + q * FR::PER_LANE;
 #pragma unroll
-            for (int v = 0; v < UV; ++v) {
-                const int uu = CONTIG ? h * UV + v : WPS * v + h;
-                const int col = u0 + uu * FR::COLS + q * FR::PER_LANE;
-                // column steps wholly past d (small d; wave-uniform) issue no load
-                if (DC > 0 ? (uu * FR::COLS < DC) : (u0 + uu * FR::COLS < d)) {
+                    for (int I = 0; I < NB; ++I) a[v][I] = ldg<frag>(src[I] ? src[I] + col : zero + (col & ZMASK));
+                };
 #pragma unroll
-                    for (int I = 0; I < NB; ++I) {
-                        const bool ok = src[I] && col < d;
-                        a[v][I] = ldg<frag>(ok ? src[I] + col : zero + (col & ZMASK));
-                    }
-                } else {
+                for (int v = 0; v < WIN; ++v) load_step(v);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int I = 0; I < NB; ++I) a[v][I] = FR::zero();
+                for (int v = 0; v < UV; ++v) {
+                    WTS_LANDED(v);
+                    int ij = 0;
+#pragma unroll
+                    for (int I = 0; I < NB; ++I)
+#pragma unroll
+                        for (int J = 0; J <= I; ++J, ++ij) FR::mma(acc[NPART == 2 ? (v & 1) : 0][ij], a[v][I], a[v][J]);
+                    // step v's MFMAs are issued: the window rolls on to step v + WIN
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (v + WIN < UV) load_step(v + WIN);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
-            }
-            __builtin_amdgcn_sched_barrier(0);
+            } else {
 #pragma unroll
-            for (int v = 0; v < UV; ++v) {
-                const int uu = CONTIG ? h * UV + v : WPS * v + h;
-                if (!(DC > 0 ? (uu * FR::COLS < DC) : (u0 + uu * FR::COLS < d))) continue;  // (wave-uniform)
-                int ij = 0;
+                for (int v = 0; v < UV; ++v) {
+                    const int uu = CONTIG ? h * UV + v : WPS * v + h;
+                    const int col = u0 + uu * FR::COLS + q * FR::PER_LANE;
+                    // column steps wholly past d (small d; wave-uniform) issue no load
+                    if (DC > 0 ? (uu * FR::COLS < DC) : (u0 + uu * FR::COLS < d)) {
 #pragma unroll
-                for (int I = 0; I < NB; ++I)
+                        for (int I = 0; I < NB; ++I) {
+                            const bool ok = src[I] && col < d;
+                            a[v][I] = ldg<frag>(ok ? src[I] + col : zero + (col & ZMASK));
+                        }
+                    } else {
 #pragma unroll
-                    for (int J = 0; J <= I; ++J, ++ij)
-                        if (!EARLY || ij == 0)
+                        for (int I = 0; I < NB; ++I) a[v][I] = FR::zero();
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int v = 0; v < UV; ++v) {
+                    const int uu = CONTIG ? h * UV + v : WPS * v + h;
+                    if (!(DC > 0 ? (uu * FR::COLS < DC) : (u0 + uu * FR::COLS < d))) continue;  // (wave-uniform)
+                    WTS_LANDED(v);
+                    int ij = 0;
+#pragma unroll
+                    for (int I = 0; I < NB; ++I)
+#pragma unroll
+                        for (int J = 0; J <= I; ++J, ++ij)
                             FR::mma(acc[NPART == 2 ? (CONTIG ? (((u0 + uu * FR::COLS) >> 6) & 1) : (uu & 1)) : 0][ij],
                                     a[v][I], a[v][J]);
-            }
-            if constexpr (EARLY) {
-                // x (fast_vcat) and tile 00's pairs staged and stored now; tiles 10 and 11 after
-#pragma unroll
-                for (int v = 0; v < UV; ++v) {
-                    const int col = u0 + v * FR::COLS + q * FR::PER_LANE;
-                    if (c == 0 && col < d) {
-                        float f[FR::PER_LANE];
-                        FR::to_f(f, a[v][0]);
-#pragma unroll
-                        for (int k = 0; k < FR::PER_LANE; k += 4)
-                            *(f32x4_t*)(stage + col + k) = f32x4_t{f[k], f[k + 1], f[k + 2], f[k + 3]};
-                    }
-                }
-                const f32x4_t z0 = acc[0][0] + acc[NPART - 1][0];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int i = 4 * q + r;
-                    if (i < F && c < i) stage[d + i * (i - 1) / 2 + c] = z0[r];
-                }
-                wave_lds_sync();
-                if (live) store_staged<T, 64>(orow, stage, 0, E1, lane);
-#pragma unroll
-                for (int v = 0; v < UV; ++v) {
-                    const int uu = v;
-                    if (!(uu * FR::COLS < DC)) continue;
-                    FR::mma(acc[NPART == 2 ? (uu & 1) : 0][1], a[v][1], a[v][0]);
-                    FR::mma(acc[NPART == 2 ? (uu & 1) : 0][2], a[v][1], a[v][1]);
                 }
             }
             // fast_vcat: x (row 0: lanes c == 0 of I = 0) into the output head, and the lookup
@@ -304,7 +322,7 @@ __device__ __forceinline__ void fwd_body_onehot(int bid, int nblocks, float* sta
                 const int uu = CONTIG ? h * UV + v : WPS * v + h;
                 const int col = u0 + uu * FR::COLS + q * FR::PER_LANE;
                 if (col < d && live) {
-                    if (c == 0 && !EARLY) {
+                    if (c == 0) {
                         float f[FR::PER_LANE];
                         FR::to_f(f, a[v][0]);
                         if (staged) {
@@ -327,7 +345,6 @@ __device__ __forceinline__ void fwd_body_onehot(int bid, int nblocks, float* sta
                 }
             }
         }
-        if (h == 0) WT(0, 1, b);
         // Z = even + odd partials
         f32x4_t z[NT];
         if constexpr (WPS == 1 && NPART == 1) {
@@ -344,6 +361,9 @@ __device__ __forceinline__ void fwd_body_onehot(int bid, int nblocks, float* sta
 #pragma unroll
             for (int k = 0; k < NT; ++k) z[k] = acc[0][k] + xch[k * 64 + lane];
         }
+#pragma unroll
+        for (int k = 0; k < NT; ++k) WTS_USE(z[k]);
+        WTS(4);
         // Z[i][j], i > j: triangular_slice_kernel! order (i-major), after x
         if (h == 0 && live) {
             int ij = 0;
@@ -351,7 +371,6 @@ __device__ __forceinline__ void fwd_body_onehot(int bid, int nblocks, float* sta
             for (int I = 0; I < NB; ++I)
 #pragma unroll
                 for (int J = 0; J <= I; ++J, ++ij) {
-                    if (EARLY && ij == 0) continue;  // (staged and stored already)
                     const int j = J * 16 + c;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -375,8 +394,8 @@ __device__ __forceinline__ void fwd_body_onehot(int bid, int nblocks, float* sta
             } else if (live && VEC_ROW) {
                 // rows of W = d + P floats start at any 4-B boundary (479 at the metric config): the
                 // head elements up to the row's first 16-B boundary, then 16-B stores of the staged
-                // row (read from LDS as four floats), then the tail (EARLY: [E1, W) only)
-                store_staged<T, 64 * WPS>(orow, stage, EARLY ? E1 : 0, W, lane + 64 * h);
+                // row (read from LDS as four floats), then the tail
+                store_staged<T, 64 * WPS>(orow, stage, 0, W, lane + 64 * h);
             } else if (live) {
                 for (int e = lane + 64 * h; e < W; e += 64 * WPS) stg<T>(orow + e, from_f32<T>(stage[e]));
             }
@@ -384,7 +403,8 @@ __device__ __forceinline__ void fwd_body_onehot(int bid, int nblocks, float* sta
         } else if constexpr (WPS == 2) {
             __syncthreads();  // xch is rewritten by the next pass
         }
-        if (h == 0) WT(0, 2, b);
+        WTS(5);
+        if (h == 0) WTS_FLUSH(0, b);
     }
     if (DEFER && bad_any) raise_index_error(ga.err);
 }

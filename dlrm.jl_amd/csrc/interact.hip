@@ -46,7 +46,9 @@ extern "C" int dlrm_debug_phase_fwd_reset(void) {
 
 #ifdef DLRM_WTRACE
 // Per-sample wave timestamps (wall_clock64, 100 MHz) of the forward (kind 0) and backward
-// (kind 1) bodies; only in the tracing build (tools/wave_trace.sh).
+// (kind 1) bodies; only in the tracing build (tools/wave_trace.sh).  Forward slots: 0 start,
+// 1 indices returned, 2 first column step landed, 3 last column step landed, 4 MFMAs done,
+// 5 output stores issued (the one-hot body stamps all six, fwd_onehot.hpp; the pooled body 0, 4, 5).
 __device__ unsigned long long g_wt[2][6][8192];
 #define WT(kind, slot, b) do { if ((threadIdx.x & 63) == 0 && (b) < 8192) g_wt[kind][slot][b] = wall_clock64(); } while (0)
 extern "C" int dlrm_debug_wtrace(unsigned long long* out) {
@@ -67,9 +69,20 @@ namespace dlrm {
 #define DLRM_DEFER_RAISE 1
 #endif
 constexpr bool kDeferRaise = DLRM_DEFER_RAISE;
+// Column steps of row loads a wave of the one-hot forward keeps in flight (fwd_onehot.hpp, WIN;
+// 0: all of a column block).  The rolling window is chosen per instantiation, where it was measured
+// to win in the training step: three of the eight steps for the fused fp32 lookup + interaction of
+// 17..32 features at d = 128 (DLRM_FWD_WIN builds another window there; DESIGN.md section 3: 2, 3, 4
+// and 6 measured).  Every other instantiation keeps every step in flight.
+#ifndef DLRM_FWD_WIN
+#define DLRM_FWD_WIN 3
+#endif
+template <typename T, int NB, bool FUSED, int DC> constexpr int fwd_window() {
+    return (std::is_same<T, float>::value && NB == 2 && FUSED && DC == 128) ? DLRM_FWD_WIN : 0;
+}
 template <int NB, bool FUSED, bool POOL> constexpr bool fwd_tab_ptrs() { return FUSED && !POOL && NB <= 2; }
 
-template <typename T, int NB, bool FUSED, int WPB, bool POOL = false, int DC = 0>
+template <typename T, int NB, bool FUSED, int WPB, bool POOL = false, int DC = 0, int WIN = 0>
 __device__ __forceinline__ void fwd_body(int bid, int nblocks, float* stage_all, int d_, int F, int B,
                                          const T* __restrict__ x, int64_t x_ld, T* __restrict__ ys, int64_t ys_ld,
                                          T* __restrict__ out, int64_t out_ld, int padding, const GatherArgs& ga,
@@ -80,7 +93,7 @@ __device__ __forceinline__ void fwd_body(int bid, int nblocks, float* stage_all,
         // sample (column halves) at d = 128 -- tools/fwd_probe.hip: 10.5 vs 11.9 us
         constexpr int WPS = 1;
         constexpr bool TP = fwd_tab_ptrs<NB, FUSED, POOL>();
-        fwd_body_onehot<T, NB, FUSED, WPB, DC, WPS, false, TP, kDeferRaise && TP>(
+        fwd_body_onehot<T, NB, FUSED, WPB, DC, WPS, false, TP, kDeferRaise && TP, WIN>(
             bid, nblocks, stage_all, d_, F, B, x, x_ld, ys, ys_ld, out, out_ld, padding, ga, tp);
         return;
     }
@@ -196,7 +209,7 @@ __device__ __forceinline__ void fwd_body(int bid, int nblocks, float* stage_all,
         f32x4_t acc[NB * (NB + 1) / 2];
 #pragma unroll
         for (int k = 0; k < NB * (NB + 1) / 2; ++k) acc[k] = NB <= 2 ? acc2[0][k] + acc2[1][k] : acc2[0][k];
-        WT(0, 1, b);
+        WT(0, 4, b);
         // Z[i][j], i > j: triangular_slice_kernel! order (i-major), after x
         {
             int ij = 0;
@@ -225,7 +238,7 @@ __device__ __forceinline__ void fwd_body(int bid, int nblocks, float* stage_all,
             for (int e = lane; e < W; e += 64) stg<T>(orow + e, from_f32<T>(stage[e]));
             wave_lds_sync();
         }
-        WT(0, 2, b);
+        WT(0, 5, b);
     }
 }
 
@@ -236,8 +249,8 @@ __global__ __launch_bounds__(64 * WPB, 2) void interact_fwd_kernel(int d, int F,
                                                                    T* __restrict__ out, int64_t out_ld, int padding,
                                                                    GatherArgs ga, TabPtrs tp) {
     __shared__ __attribute__((aligned(16))) float stage_all[WPB * kStage];
-    fwd_body<T, NB, FUSED, WPB, POOL, DC>(blockIdx.x, gridDim.x, stage_all, d, F, B, x, x_ld, ys, ys_ld, out, out_ld, padding,
-                                ga, &tp);
+    fwd_body<T, NB, FUSED, WPB, POOL, DC, fwd_window<T, NB, FUSED, DC>()>(blockIdx.x, gridDim.x, stage_all, d, F, B, x, x_ld,
+                                                                          ys, ys_ld, out, out_ld, padding, ga, &tp);
 }
 
 // The forward of a training step with the SparseIndexer build in the same grid (split form:
@@ -959,6 +972,14 @@ static unsigned grid_for(int64_t items, int per_block, int cus) {
 
 // samples per 4-wave workgroup of the one-hot forward (fwd_body: one wave per sample)
 static int fwd_samples_per_block(int, int) { return 4; }
+// The tracing build holds the d = 128 forward at the shipped two workgroups per CU with unused
+// dynamic LDS (16 KB static + 40 KB: two fit in 160 KB): the stamps change the kernel's register
+// count, and a third workgroup would change the timeline they are there to show.
+#ifdef DLRM_WTRACE
+constexpr size_t kFwdTraceLds = 40 * 1024;
+#else
+constexpr size_t kFwdTraceLds = 0;
+#endif
 
 template <typename T, int NB, bool FUSED>
 static void launch_fwd_nb(hipStream_t s, int cus, int d, int F, int B, const void* x, int64_t x_ld, void* ys,
@@ -970,7 +991,7 @@ static void launch_fwd_nb(hipStream_t s, int cus, int d, int F, int B, const voi
         hipLaunchKernelGGL((interact_fwd_kernel<T, NB, FUSED, true>), dim3(g), dim3(256), 0, s, d, F, B, (const T*)x,
                            x_ld, (T*)ys, ys_ld, (T*)out, out_ld, padding, ga, tp);
     else if (d == 128)  // the BASELINE feature size, compiled for it
-        hipLaunchKernelGGL((interact_fwd_kernel<T, NB, FUSED, false, 128>), dim3(g), dim3(256), 0, s, d, F, B,
+        hipLaunchKernelGGL((interact_fwd_kernel<T, NB, FUSED, false, 128>), dim3(g), dim3(256), kFwdTraceLds, s, d, F, B,
                            (const T*)x, x_ld, (T*)ys, ys_ld, (T*)out, out_ld, padding, ga, tp);
     else
         hipLaunchKernelGGL((interact_fwd_kernel<T, NB, FUSED, false>), dim3(g), dim3(256), 0, s, d, F, B, (const T*)x,

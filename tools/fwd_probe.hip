@@ -117,16 +117,17 @@ __global__ void fill_random(float* p, int64_t n, uint32_t seed) {
 
 
 // The shipped one-hot body (dlrm.jl_amd/csrc/fwd_onehot.hpp), instantiated here with its knobs.
-template <int WPS, bool CONTIG, int WPB, bool TP, bool DEFER>
+// WIN: column steps of row loads in flight per wave (0: all eight, no rolling window).
+template <int WPS, bool CONTIG, int WPB, bool TP, bool DEFER, int WIN>
 __global__ __launch_bounds__(64 * WPB, 2) void libbody(int d, int F, int B, const float* __restrict__ x, int64_t x_ld,
                                                       float* __restrict__ out, int64_t out_ld, int padding,
                                                       dlrm::GatherArgs ga, dlrm::TabPtrs tp) {
     __shared__ __attribute__((aligned(16))) float stage_all[WPB * dlrm::kStage];
-    dlrm::fwd_body_onehot<float, 2, true, WPB, 128, WPS, CONTIG, TP, DEFER>(
+    dlrm::fwd_body_onehot<float, 2, true, WPB, 128, WPS, CONTIG, TP, DEFER, WIN>(
         blockIdx.x, gridDim.x, stage_all, d, F, B, x, x_ld, nullptr, 0, out, out_ld, padding, ga, &tp);
 }
 
-template <int WPS, bool CONTIG, int WPB, bool TP = false, bool DEFER = false>
+template <int WPS, bool CONTIG, int WPB, bool TP = false, bool DEFER = false, int WIN = 0>
 double run_body(const dlrm::TableDesc* dtabs, const int* idx, const float* x, float* out, unsigned* err,
                 const dlrm::TableDesc* htabs = nullptr) {
     hipEvent_t e0, e1;
@@ -136,7 +137,7 @@ double run_body(const dlrm::TableDesc* dtabs, const int* idx, const float* x, fl
         dlrm::GatherArgs ga{dtabs, idx + (size_t)(i % NBATCH) * T * B, 0, B, 0, 1, err, nullptr, nullptr};
         dlrm::TabPtrs tp{};
         if (TP) dlrm::fill_tab_ptrs(tp, htabs, T);
-        hipLaunchKernelGGL((libbody<WPS, CONTIG, WPB, TP, DEFER>), dim3(grid), dim3(64 * WPB), 0, 0, D, F, B, x,
+        hipLaunchKernelGGL((libbody<WPS, CONTIG, WPB, TP, DEFER, WIN>), dim3(grid), dim3(64 * WPB), 0, 0, D, F, B, x,
                            (int64_t)D, out, (int64_t)W, 1, ga, tp);
     };
     for (int i = 0; i < NBATCH; ++i) go(i);
@@ -552,6 +553,12 @@ int main() {
             printf("%s body wps2 defer raise %7.2f us\n", lname, run_body<2, false, 4, false, true>(dtabs, idx, x, out, err, hd.data()));
             printf("%s body wps2 TabPtrs+defer%6.2f us\n", lname, run_body<2, false, 4, true, true>(dtabs, idx, x, out, err, hd.data()));
             printf("%s body wps1 TabPtrs+defer%6.2f us\n", lname, run_body<1, false, 4, true, true>(dtabs, idx, x, out, err, hd.data()));
+            // the shipped form (wps1, TabPtrs, deferred raise) with a rolling window of row loads
+            printf("%s body wps1 window 2    %7.2f us\n", lname, run_body<1, false, 4, true, true, 2>(dtabs, idx, x, out, err, hd.data()));
+            printf("%s body wps1 window 3    %7.2f us\n", lname, run_body<1, false, 4, true, true, 3>(dtabs, idx, x, out, err, hd.data()));
+            printf("%s body wps1 window 4    %7.2f us\n", lname, run_body<1, false, 4, true, true, 4>(dtabs, idx, x, out, err, hd.data()));
+            printf("%s body wps1 window 6    %7.2f us\n", lname, run_body<1, false, 4, true, true, 6>(dtabs, idx, x, out, err, hd.data()));
+            printf("%s body wps1 window 8    %7.2f us\n", lname, run_body<1, false, 4, true, true, 8>(dtabs, idx, x, out, err, hd.data()));
             printf("%s body wps2 contig wpb8 %7.2f us\n", lname, run_body<2, true, 8>(dtabs, idx, x, out, err));
             printf("%s body wps1             %7.2f us\n", lname, run_body<1, false, 4>(dtabs, idx, x, out, err));
             float* zf;
