@@ -76,6 +76,7 @@ struct dlrm_indexer {
     bool split = false;  // built by dlrm_step_fwd's kernel: once-hit rows are left to the backward
     bool prepared = false;  // built by dlrm_step_bwd_prepare for the next dlrm_step_fwd (not yet consumed)
     bool singles_done = false;  // a split backward has applied this build's once-hit rows already
+    bool singles_split = false;  // ... with the split rule (dlrm_split_step_bwd), not Descent
     // device words for the bounds errors of builds that may run beside a step's write-deciding
     // kernels, which read the ctx's flag to decide whether to write (raising there would be a race,
     // ADVICE r5): [0] dlrm_indexer_prepare (a side-stream build beside the current step; cleared
@@ -155,7 +156,7 @@ static void record_build(dlrm_indexer* ix, bool split, const void* indices, int 
     ix->built = true;
     ix->split = split;
     ix->prepared = false;
-    ix->singles_done = false;
+    ix->singles_done = ix->singles_split = false;
     ix->dev.has_map = 0;  // (set by dlrm_step_bwd_prepare, whose wave build writes the item map)
     ix->dev.build_err = nullptr;  // (set by dlrm_indexer_prepare)
     ix->indices = indices;
@@ -737,7 +738,7 @@ static int indexer_carve(dlrm_ctx* ctx, dlrm_indexer* ix, int parts) {
     ix->dev = d;
     ix->TV = (int)T;
     ix->bytes = total;
-    ix->built = ix->prepared = ix->singles_done = false;
+    ix->built = ix->prepared = ix->singles_done = ix->singles_split = false;
     ix->dev.has_map = 0;
     ix->dev.build_err = nullptr;
     return DLRM_OK;
@@ -955,7 +956,8 @@ static int read_indexer_table(dlrm_ctx* ctx, const dlrm_indexer* ix, int v, Inde
 int dlrm_indexer_state(const dlrm_indexer* ix, unsigned* state) {
     if (!ix || !state) return DLRM_E_ARG;
     *state = (ix->built ? DLRM_IX_BUILT : 0u) | (ix->split ? DLRM_IX_SPLIT : 0u) |
-             (ix->prepared ? DLRM_IX_PREPARED : 0u) | (ix->singles_done ? DLRM_IX_SINGLES_DONE : 0u);
+             (ix->prepared ? DLRM_IX_PREPARED : 0u) | (ix->singles_done ? DLRM_IX_SINGLES_DONE : 0u) |
+             (ix->singles_done && ix->singles_split ? DLRM_IX_SINGLES_SPLIT : 0u);
     return DLRM_OK;
 }
 
@@ -1023,16 +1025,18 @@ struct UpdateRule {
     const char* no_atomic;     // why the rule has no atomic mode; NULL: it has one
     const char* singles_done;  // how a split backward stepped the once-hit rows, which the rule cannot take over;
                                // NULL: it skips them (their dt rows are all the backward left unwritten)
+    bool split_rule;           // the rule of dlrm_split_step_bwd: it completes that backward, and no other does
 };
-static const UpdateRule kSgdUpdate = {"dlrm_sgd_update", false, nullptr, nullptr, nullptr};
+static const UpdateRule kSgdUpdate = {"dlrm_sgd_update", false, nullptr, nullptr, nullptr, false};
 // (an atomic add never holds the row's whole sum, which the rule squares; a split backward stepped its once-hit
 // rows with Descent and left their dt rows unwritten)
 static const UpdateRule kAdagradUpdate = {"dlrm_adagrad_update", false, "the optimizer state was",
-                                          "the rule needs each row's complete sum", "Descent"};
+                                          "the rule needs each row's complete sum", "Descent", false};
 // (an atomic add on one half cannot carry into the other; a split backward wrote its once-hit rows' high halves
-// with a rounded bf16 step and left their dt rows unwritten)
+// with a rounded bf16 step and left their dt rows unwritten -- but dlrm_split_step_bwd's backward stepped them
+// with this rule, and then the update takes the repeated rows that are left)
 static const UpdateRule kSplitUpdate = {"dlrm_split_sgd_update", true, "the low halves were",
-                                        "a row's two halves are stepped together", "a rounded bf16 Descent"};
+                                        "a row's two halves are stepped together", "a rounded bf16 Descent", true};
 
 // The common part of the update entry points, from the index checks to the indexer's build: sa = the
 // launch's once-hit items.  *atomic: DLRM_UPDATE_ATOMIC of a rule that has the mode (nothing is built).
@@ -1059,7 +1063,10 @@ static int update_prologue(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, con
     if (flags & DLRM_UPDATE_PREBUILT) {
         if (!built_from(ix, indices, itype, table_stride, index_base, batch, lookups))
             return ctx_fail(ctx, DLRM_E_STATE, "%s: indexer was not built from these indices", r.fn);
-        if (ix->singles_done && r.singles_done)
+        if (ix->singles_done && ix->singles_split && !r.split_rule)
+            return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_split_step_bwd) already stepped this build's "
+                            "once-hit rows with the split rule", r.fn);
+        if (ix->singles_done && !ix->singles_split && r.singles_done)
             return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_step_bwd) already stepped this build's "
                             "once-hit rows with %s", r.fn, r.singles_done);
     } else {
@@ -1228,42 +1235,67 @@ int dlrm_step_fwd(dlrm_ctx* ctx, const dlrm_tables* tb, dlrm_indexer* ix, const 
     return dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, 1);
 }
 
+// The once-hit rule of a training step's backward and apply: Descent (op NULL; dlrm_step_bwd) or the split rule
+// on split-bf16 tables (dlrm_split_step_bwd).  An indexer remembers which one stepped its once-hit rows
+// (singles_split), and only the same rule's apply completes that backward.
+struct StepRule {
+    const char* fn;      // the entry point, for the messages
+    dlrm_split_sgd* op;  // the low halves; NULL: Descent
+};
+
 static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* indices, int itype,
                          int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
                          const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
-                         int64_t dt_ld, float lr, unsigned flags, const PrepArgs* prep) {
-    CHECK_ARG(ctx && tb && ix, "dlrm_step_bwd: null ctx/tables/indexer");
+                         int64_t dt_ld, float lr, unsigned flags, const PrepArgs* prep,
+                         const StepRule& rule = StepRule{"dlrm_step_bwd", nullptr}) {
+    CHECK_ARG(ctx && tb && ix, "%s: null ctx/tables/indexer", rule.fn);
+    dlrm_split_sgd* const op = rule.op;
     int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, 1);
     if (rc) return rc;
+    if (op) {  // (dlrm_split_sgd_update's argument errors)
+        CHECK_ARG(tb->dtype == DLRM_BF16, "%s: split tables are bf16 (the high halves)", rule.fn);
+        CHECK_ARG(op->T == tb->T && op->D == tb->D, "%s: the low halves were created for %d tables of dim %d", rule.fn,
+                  op->T, op->D);
+    }
     const int d = tb->D, F = tb->T + 1;
     const int64_t P = (int64_t)F * (F - 1) / 2;
     CHECK_ARG(padding >= 0 && x_ld >= d && dout_ld >= d + P + padding && dx_ld >= d && dt_ld >= (int64_t)F * d,
-              "dlrm_step_bwd: leading dimensions too small");
-    CHECK_ARG(batch == 0 || (x && dout && dx && dt), "dlrm_step_bwd: null buffer");
+              "%s: leading dimensions too small", rule.fn);
+    CHECK_ARG(batch == 0 || (x && dout && dx && dt), "%s: null buffer", rule.fn);
     if (!built_from(ix, indices, itype, table_stride, index_base, batch, 1))
-        return ctx_fail(ctx, DLRM_E_STATE, "dlrm_step_bwd: the indexer was not built by dlrm_step_fwd from these indices");
-    CHECK_ARG(flags != (DLRM_STEP_BWD_ONLY | DLRM_STEP_APPLY_ONLY), "dlrm_step_bwd: flags %u", flags);
+        return ctx_fail(ctx, DLRM_E_STATE, "%s: the indexer was not built by dlrm_step_fwd from these indices", rule.fn);
+    CHECK_ARG(flags != (DLRM_STEP_BWD_ONLY | DLRM_STEP_APPLY_ONLY), "%s: flags %u", rule.fn, flags);
     rc = ensure_partials(ctx, ix, tb->D);
     if (rc) return rc;
     // the split backward (once-hit rows updated there) where the shape has it; otherwise the
     // gather backward writes every dt row and the apply takes a split indexer's once-hit rows too
-    const bool split_bwd = ix->split && step_split_supported(tb->aligned16, tb->T, tb->dtype, d, x, x_ld);
+    // (the split rule: its backward loads the low halves as 8-B or 16-B vectors)
+    const bool split_bwd = ix->split && step_split_supported(tb->aligned16, tb->T, tb->dtype, d, x, x_ld) &&
+                           (!op || op->aligned16);
     if (flags & DLRM_STEP_APPLY_ONLY) {
         // the apply of a split build only completes a backward that stepped the once-hit rows
         if (split_bwd && !ix->singles_done)
-            return ctx_fail(ctx, DLRM_E_STATE, "dlrm_step_bwd(APPLY_ONLY): no backward has run on this build");
+            return ctx_fail(ctx, DLRM_E_STATE, "%s(APPLY_ONLY): no backward has run on this build", rule.fn);
+        // ... with this rule: the other one's once-hit rows hold another step
+        if (ix->singles_done && ix->singles_split != (op != nullptr))
+            return ctx_fail(ctx, DLRM_E_STATE, "%s(APPLY_ONLY): this build's once-hit rows were stepped by %s", rule.fn,
+                            ix->singles_split ? "dlrm_split_step_bwd (the split rule)" : "dlrm_step_bwd (Descent)");
         rc = DLRM_OK;
     } else if (split_bwd) {
         // a second backward on one build would step its once-hit rows twice
         if (ix->singles_done)
             return ctx_fail(ctx, DLRM_E_STATE,
-                            "dlrm_step_bwd: this build's once-hit rows were already stepped (one backward per "
-                            "dlrm_step_fwd)");
+                            "%s: this build's once-hit rows were already stepped (one backward per "
+                            "dlrm_step_fwd)", rule.fn);
         CHECK_ARG((uintptr_t)dx % 16 == 0 && (uintptr_t)dt % 16 == 0 && dx_ld % 4 == 0 && dt_ld % 4 == 0,
-                  "dlrm_step_bwd: dx and dt must be 16-B aligned with leading dimensions divisible by 4");
+                  "%s: dx and dt must be 16-B aligned with leading dimensions divisible by 4", rule.fn);
         rc = launch_step_bwd(ctx, tb->d_desc, tb->T, tb->dtype, indices, itype, table_stride, index_base, d, batch, x,
-                             x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, lr, tb->h_desc.data());
-        if (rc == DLRM_OK) ix->singles_done = true;
+                             x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, lr, tb->h_desc.data(),
+                             op ? op->d_ptr : nullptr);
+        if (rc == DLRM_OK) {
+            ix->singles_done = true;
+            ix->singles_split = op != nullptr;
+        }
     } else {
         rc = launch_interact_bwd_gather(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
                                         index_base, 1, d, batch, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, nullptr, tb->h_desc.data());
@@ -1273,6 +1305,9 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
     // them as chunks)
     const SinglesArgs sa{(ix->split && !split_bwd) ? ix->dev.single : nullptr, indices, itype, table_stride,
                          index_base, batch};
+    if (op)
+        return launch_split_step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_ptr, tb->T, tb->D,
+                                       (int64_t)batch, dt, dt_ld, d, lr, sa, prep);
     return launch_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, tb->T, tb->D, tb->dtype, 1, (int64_t)batch, dt,
                             DLRM_F32, dt_ld, d, lr, sa, prep);
 }
@@ -1285,12 +1320,13 @@ int dlrm_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* 
                          dx, dx_ld, dt, dt_ld, lr, flags, nullptr);
 }
 
-int dlrm_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* indices, int itype,
-                          int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
-                          const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
-                          int64_t dt_ld, float lr, dlrm_indexer* next, const void* next_indices, unsigned flags) {
-    CHECK_ARG(ctx && tb && ix && next && next != ix, "dlrm_step_bwd_prepare: null or shared indexer");
-    CHECK_ARG(next->T == tb->T && batch <= next->dev.cap, "dlrm_step_bwd_prepare: next indexer too small");
+static int step_bwd_prepare_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* indices, int itype,
+                                 int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
+                                 const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
+                                 int64_t dt_ld, float lr, dlrm_indexer* next, const void* next_indices, unsigned flags,
+                                 const StepRule& rule) {
+    CHECK_ARG(ctx && tb && ix && next && next != ix, "%s_prepare: null or shared indexer", rule.fn);
+    CHECK_ARG(next->T == tb->T && batch <= next->dev.cap, "%s_prepare: next indexer too small", rule.fn);
     int rc = check_indices(ctx, tb, next_indices, itype, table_stride, batch, 1);
     if (rc) return rc;
     // the next batch's build runs as extra workgroups of this step's apply launch: the step
@@ -1299,13 +1335,14 @@ int dlrm_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, cons
     // (the split backward's shapes only: the apply launch that carries the build has no once-hit items)
     const bool inapply = batch > 0 && tb->T > 0 && batch <= kWaveApplyMaxN && NB <= 2 && tb->aligned16 &&
                          wave_fits(next, batch) &&
-                         step_split_supported(tb->aligned16, tb->T, tb->dtype, tb->D, x, x_ld);
+                         step_split_supported(tb->aligned16, tb->T, tb->dtype, tb->D, x, x_ld) &&
+                         (!rule.op || rule.op->aligned16);
     if (!inapply)  // no pipelined form for this shape: the plain step (the next forward builds)
         return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
-                             padding, dx, dx_ld, dt, dt_ld, lr, flags, nullptr);
+                             padding, dx, dx_ld, dt, dt_ld, lr, flags, nullptr, rule);
     if (flags & DLRM_STEP_BWD_ONLY)  // (the next build rides on the apply launch)
         return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
-                             padding, dx, dx_ld, dt, dt_ld, lr, flags, nullptr);
+                             padding, dx, dx_ld, dt, dt_ld, lr, flags, nullptr, rule);
     next->built = false;
     next->prepared = false;
     // the wave build: 2^wave_parts_log2(batch) parts per table, one wave each (4 per workgroup)
@@ -1314,12 +1351,42 @@ int dlrm_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, cons
     const PrepArgs pa{next->dev, tb->d_desc, tb->T, next_indices, itype, table_stride, index_base, batch,
                       next->prep_err + 1};
     rc = step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
-                       dx, dx_ld, dt, dt_ld, lr, flags, &pa);
+                       dx, dx_ld, dt, dt_ld, lr, flags, &pa, rule);
     if (rc) return rc;
     record_build(next, true, next_indices, itype, table_stride, index_base, batch, 1);
     next->prepared = true;
     next->dev.has_map = 1;
     return DLRM_OK;
+}
+
+int dlrm_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* indices, int itype,
+                          int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
+                          const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
+                          int64_t dt_ld, float lr, dlrm_indexer* next, const void* next_indices, unsigned flags) {
+    return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
+                                 padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags,
+                                 StepRule{"dlrm_step_bwd", nullptr});
+}
+
+// ---- the same step on split-bf16 tables: the split rule in the backward's once-hit write and in the apply
+int dlrm_split_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dlrm_indexer* ix, const void* indices,
+                        int itype, int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
+                        const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
+                        int64_t dt_ld, float lr, unsigned flags) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_split_step_bwd: null ctx/tables/optimizer/indexer");
+    return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
+                         dx, dx_ld, dt, dt_ld, lr, flags, nullptr, StepRule{"dlrm_split_step_bwd", op});
+}
+
+int dlrm_split_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dlrm_indexer* ix,
+                                const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                                const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding, float* dx,
+                                int64_t dx_ld, float* dt, int64_t dt_ld, float lr, dlrm_indexer* next,
+                                const void* next_indices, unsigned flags) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_split_step_bwd_prepare: null ctx/tables/optimizer/indexer");
+    return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
+                                 padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags,
+                                 StepRule{"dlrm_split_step_bwd", op});
 }
 
 // ---- diagnostics: a native backtrace on a fatal signal (SIGSEGV / SIGBUS / SIGABRT), written to

@@ -90,7 +90,7 @@ __device__ __forceinline__ void add_vec(float* acc, const typename Vec<GT>::type
 //                   the truncated high half of an fp32 master weight, the step is Descent's on fp32)
 // A rule holds its parameters, its state's row address (state_row), its once-hit positions per lane group
 // (singles_ppg), the any-D kernels' write of one column (scalar_write) and the MODEs and table element types
-// it is instantiated for (kCarriesBuild, kF32Tables).  The vector items below still branch on kState (0 none,
+// it is instantiated for (kCarriesBuild, kBuildWithApply, kF32Tables).  The vector items below still branch on kState (0 none,
 // 1 a state row per table row, 2 a state word, 3 a row of low halves): written once over a per-rule row type
 // they no longer compiled to the same code.  The state is loaded where the table row
 // is (beside the grad rows: these items are bound by dependent round trips) and written once, with the row.
@@ -175,6 +175,7 @@ struct Descent {
     typedef float State;
     static constexpr int kState = 0;  // (the items' per-rule branches: 0 none, 1 a state row, 2 a state word, 3 low halves)
     static constexpr bool kCarriesBuild = true;  // MODE >= 2: the next batch's build rides on its launches
+    static constexpr bool kBuildWithApply = true;  // ... instantiated where its MODE 0 / 1 launches are
     static constexpr bool kF32Tables = true;
     __device__ __forceinline__ float* base(int) const { return nullptr; }
     template <int D> __device__ static __forceinline__ float* state_row(float*, uint32_t) { return nullptr; }
@@ -192,6 +193,7 @@ struct Adagrad {
     typedef float State;
     static constexpr int kState = 1;
     static constexpr bool kCarriesBuild = false;
+    static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = true;
     __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
     template <int D> __device__ static __forceinline__ float* state_row(float* st, uint32_t r) { return st + (int64_t)r * D; }
@@ -218,6 +220,7 @@ struct RowwiseAdagrad {
     typedef float State;
     static constexpr int kState = 2;
     static constexpr bool kCarriesBuild = false;
+    static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = true;
     __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
     template <int D> __device__ static __forceinline__ float* state_row(float* st, uint32_t r) { return st + r; }
@@ -245,7 +248,10 @@ struct SplitDescent {
     uint16_t* const* lo;  // [T] device pointers, uint16 [nrows][D]: the low halves
     typedef uint16_t State;
     static constexpr int kState = 3;
-    static constexpr bool kCarriesBuild = false;
+    // MODE >= 2 over bf16 tables and the training step's fp32 dt, in a unit of their own (split_step.hip:
+    // launch_split_step_apply), so split_sgd.hip stays the MODE 0 / 1 unit it was
+    static constexpr bool kCarriesBuild = true;
+    static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = false;  // split rows live in bf16 tables
     __device__ __forceinline__ uint16_t* base(int t) const { return ldg<uint16_t*>(lo + t); }
     template <int D> __device__ static __forceinline__ uint16_t* state_row(uint16_t* st, uint32_t r) { return st + (int64_t)r * D; }

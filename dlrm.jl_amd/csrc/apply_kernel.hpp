@@ -1,7 +1,7 @@
 // apply_kernel.hpp -- the apply launch of update! (sgd_apply_kernel over apply.hpp's work items), its
 // any-D fallback kernels and their launchers, by update rule.  update.hip instantiates Descent
 // (every MODE), adagrad.hip and adagrad_rowwise.hip the Adagrad rules, split_sgd.hip the split rule (MODE 0
-// and 1): one translation unit per rule, so they compile side by side.
+// and 1) and split_step.hip its build-carrying launches (MODE 2 / 3 / 5): they compile side by side.
 #pragma once
 #include "apply.hpp"
 
@@ -45,7 +45,7 @@ static inline int wave_big_kind(const PrepArgs& pa) {
 // workgroups of a build (4 parts each)
 __host__ __device__ __forceinline__ int prep_groups(const PrepArgs& pa) { return (pa.T << pa.ix.vshift) / kWaveParts; }
 
-// R: the update rule (apply.hpp: Descent, Adagrad, RowwiseAdagrad, SplitDescent -- all but the first in MODE 0
+// R: the update rule (apply.hpp: Descent, Adagrad, RowwiseAdagrad, SplitDescent -- the Adagrad rules in MODE 0
 // and 1 only).
 template <typename TT, typename GT, int VPR, int MODE, typename R = Descent>
 __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev ix, TableDesc* __restrict__ tabs, int T_,
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
                                                                   int64_t grad_offset, R rule,
                                                                   const unsigned* __restrict__ err, SinglesArgs sa,
                                                                   PrepArgs pa) {
-    static_assert(R::kCarriesBuild || MODE <= 1, "the next batch's build rides on Descent launches only");
+    static_assert(R::kCarriesBuild || MODE <= 1, "the next batch's build rides on Descent and SplitDescent launches only");
     constexpr bool SG = MODE == 1;
     int bid = blockIdx.x, nblk = gridDim.x;
     if constexpr (MODE >= 2) {
@@ -305,22 +305,22 @@ __global__ __launch_bounds__(256) void sgd_singles_scalar(SinglesArgs sa, int64_
 
 
 // the apply launch that also carries the next batch's build (MODE >= 2): build workgroups first
-template <typename TT, typename GT, int VPR, int MODE>
+template <typename TT, typename GT, int VPR, int MODE, typename R>
 static void launch_apply_build(hipStream_t s, unsigned grid, const IndexerDev& ix, TableDesc* tabs, int T_, int L,
-                               const void* grad, int64_t grad_ld, int64_t grad_offset, const Descent& rule,
+                               const void* grad, int64_t grad_ld, int64_t grad_offset, const R& rule,
                                const unsigned* err, const SinglesArgs& sa, const PrepArgs& pa) {
-    static const hipError_t attr = hipFuncSetAttribute((const void*)sgd_apply_kernel<TT, GT, VPR, MODE>,
+    static const hipError_t attr = hipFuncSetAttribute((const void*)sgd_apply_kernel<TT, GT, VPR, MODE, R>,
                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                                        (int)sizeof(WaveBuildLds));
     (void)attr;
-    hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, MODE>), dim3(grid), dim3(kApplyThreads), sizeof(WaveBuildLds), s,
+    hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, MODE, R>), dim3(grid), dim3(kApplyThreads), sizeof(WaveBuildLds), s,
                        ix, tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, rule, err, sa, pa);
 }
 
-template <typename TT, typename GT, int VPR, typename R>
-static void launch_apply_vec(hipStream_t s, const IndexerDev& ix, TableDesc* tabs, int T_, int L, const void* grad,
-                             int64_t grad_ld, int64_t grad_offset, const R& rule, int64_t N, const unsigned* err,
-                             const SinglesArgs& sa, const PrepArgs* pa) {
+// the persistent grid of an apply launch (T_ = virtual tables), from the occupancy of the MODE 0 kernel -- or of
+// OCC, in a unit that does not hold the MODE 0 kernel
+template <typename TT, typename GT, int VPR, typename R, int OCC = 0>
+static int64_t apply_grid(const IndexerDev& ix, int T_, int64_t N, const SinglesArgs& sa) {
     typedef ApplyGeom<GT, VPR> G;
     // persistent grid: resident workgroups only (never more than the worst-case item count per
     // table: N / kHotSlice + N / (kChunk + 1) + 1 hot slices, N / NG chunk items, singles items)
@@ -329,7 +329,7 @@ static void launch_apply_vec(hipStream_t s, const IndexerDev& ix, TableDesc* tab
                        (sa.single ? (int64_t)(T_ >> ix.vshift) * ((N + SP - 1) / SP) : 0);
     static int per_cu = 0;
     if (!per_cu) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sgd_apply_kernel<TT, GT, VPR, 0, R>, kApplyThreads,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sgd_apply_kernel<TT, GT, VPR, OCC, R>, kApplyThreads,
                                                          0) != hipSuccess || per_cu < 1)
             per_cu = 1;
     }
@@ -339,19 +339,35 @@ static void launch_apply_vec(hipStream_t s, const IndexerDev& ix, TableDesc* tab
     int64_t grid = (int64_t)per_cu * (cus > 0 ? cus : 256);
     if (grid > ib) grid = ib;
     if (grid < 1) grid = 1;
+    return grid;
+}
+
+// ... and the launch that carries the build `pa` (no once-hit items: sa.single is NULL), by the build's size
+template <typename TT, typename GT, int VPR, typename R, int OCC = 0>
+static void launch_apply_build_vec(hipStream_t s, const IndexerDev& ix, TableDesc* tabs, int T_, int L, const void* grad,
+                                   int64_t grad_ld, int64_t grad_offset, const R& rule, int64_t N, const unsigned* err,
+                                   const SinglesArgs& sa, const PrepArgs& pa) {
+    // MODE 2: <= 2048 positions per table; above, 2 + wave_big_kind (3 rounds, 5 scan)
+    const int mode = pa.N <= kStepIndexMaxN ? 2 : 2 + wave_big_kind(pa);
+    const unsigned g2 = (unsigned)(apply_grid<TT, GT, VPR, R, OCC>(ix, T_, N, sa) + prep_groups(pa));
+    if (mode == 2) launch_apply_build<TT, GT, VPR, 2, R>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, pa);
+    else if (mode == 5) launch_apply_build<TT, GT, VPR, 5, R>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, pa);
+    else launch_apply_build<TT, GT, VPR, 3, R>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, pa);
+}
+
+template <typename TT, typename GT, int VPR, typename R>
+static void launch_apply_vec(hipStream_t s, const IndexerDev& ix, TableDesc* tabs, int T_, int L, const void* grad,
+                             int64_t grad_ld, int64_t grad_offset, const R& rule, int64_t N, const unsigned* err,
+                             const SinglesArgs& sa, const PrepArgs* pa) {
     // (the once-hit items and the next batch's indexer are separate instantiations: the step's
     // apply stays lean)
-    if constexpr (R::kCarriesBuild) {
+    if constexpr (R::kCarriesBuild && R::kBuildWithApply) {
         if (pa && !sa.single) {
-            // MODE 2: <= 2048 positions per table; above, 2 + wave_big_kind (3 rounds, 5 scan)
-            const int mode = pa->N <= kStepIndexMaxN ? 2 : 2 + wave_big_kind(*pa);
-            const unsigned g2 = (unsigned)(grid + prep_groups(*pa));
-            if (mode == 2) launch_apply_build<TT, GT, VPR, 2>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, *pa);
-            else if (mode == 5) launch_apply_build<TT, GT, VPR, 5>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, *pa);
-            else launch_apply_build<TT, GT, VPR, 3>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, *pa);
+            launch_apply_build_vec<TT, GT, VPR, R>(s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N, err, sa, *pa);
             return;
         }
     }
+    const int64_t grid = apply_grid<TT, GT, VPR, R>(ix, T_, N, sa);
     if (sa.single)
         hipLaunchKernelGGL((sgd_apply_kernel<TT, GT, VPR, 1, R>), dim3((unsigned)grid), dim3(kApplyThreads), 0, s, ix,
                            tabs, T_, L, (const GT*)grad, grad_ld, grad_offset, rule, err, sa, PrepArgs{});

@@ -394,7 +394,8 @@ int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T, int dtype, cons
                     int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
                     int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
                     float lr,
-    const TableDesc* htabs = nullptr);
+    const TableDesc* htabs = nullptr,
+    uint16_t* const* split_lo = nullptr);  // split-bf16 tables: the device array of low-half pointers
 int launch_interact_bwd(dlrm_ctx* ctx, int dtype, int d, int F, int B, const void* dout, int64_t dout_ld,
                         const void* t, int64_t t_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld);
 int64_t hix_table_slots(int64_t cap);
@@ -442,6 +443,12 @@ int launch_rowwise_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc*
 int launch_split_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint16_t* const* lo,
                            int T, int D, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
                            int64_t grad_offset, float lr, const SinglesArgs& singles);
+// the training step's split apply over the fp32 dt (split_step.hip): with `prep` and no once-hit items the
+// next batch's build rides on the launch (MODE 2 / 3 / 5), otherwise launch_split_sgd_apply and, with `prep`,
+// the build's own launch.
+int launch_split_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint16_t* const* lo,
+                            int T, int D, int64_t N, const float* dt, int64_t dt_ld, int64_t dt_offset, float lr,
+                            const SinglesArgs& singles, const PrepArgs* prep);
 int launch_triangular_slice(dlrm_ctx* ctx, int dtype, int sz, int B, const void* z, int64_t z_bs, void* out,
                             int64_t out_ld);
 int launch_triangular_slice_back(dlrm_ctx* ctx, int dtype, int sz, int B, const void* dy, int64_t dy_ld, void* a,

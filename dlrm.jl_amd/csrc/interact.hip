@@ -59,6 +59,7 @@ extern "C" int dlrm_debug_wtrace(unsigned long long* out) {
 #endif
 
 #include "fwd_onehot.hpp"
+#include "apply.hpp"  // the split rule's step (split_step, Halves)
 
 namespace dlrm {
 
@@ -338,14 +339,52 @@ struct StepUpdate {
     int64_t cap;
     float lr;
     const unsigned* err;    // the ctx's bounds flag: set -> no table row is written (the row goes to dt)
+    static constexpr bool kSplit = false;
+};
+// The same for split-bf16 tables (apply.hpp SplitDescent; dlrm_split_step_bwd): the table holds the high
+// halves of fp32 master weights, lo[t] their low halves.  A once-hit row's master weight is merged from
+// the gathered bf16 element (the wave's tile holds it exactly, as bf16 bits or as their fp32 value) and
+// its low half, stepped in fp32 and written back as two halves.  A struct of its own, so the Descent
+// kernels keep their arguments.
+struct SplitStepUpdate : StepUpdate {
+    uint16_t* const* lo;    // [T] device pointers, uint16 [nrows][d]
+    static constexpr bool kSplit = true;
 };
 
-template <typename T, int NB, bool GATHER, bool UPD = false, int SBU_ = 0, int DC = 0>
+// (the kernels' shared text names the low halves of either argument struct)
+__device__ __forceinline__ uint16_t* const* step_lo(const StepUpdate&) { return nullptr; }
+__device__ __forceinline__ uint16_t* const* step_lo(const SplitStepUpdate& su) { return su.lo; }
+
+// the d = 128 split kernels' per-table low-half pointers in LDS (a function-local array: only their instantiations hold it)
+template <int N> __device__ __forceinline__ uint16_t** lo_tab() {
+    __shared__ uint16_t* t[N];
+    return t;
+}
+
+// N once-hit elements of a split row: hb = the gathered high halves as fp32 bits (bf16 << 16), lv the low
+// halves, g the gradient; w = fmaf(-lr, 0 + g, w) on the merged weight (split_step1: the apply's singles
+// arithmetic, NaN quiet-bit rule included), both halves stored.
+template <int N>
+__device__ __forceinline__ void split_once_hit(float lr, const float* g, const uint32_t* hb, typename Halves<N>::type lv,
+                                               uint16_t* hrow, uint16_t* lrow) {
+    typename Halves<N>::type hv;
+    float gg[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+        hv[e] = (uint16_t)(hb[e] >> 16);
+        gg[e] = 0.0f + g[e];
+    }
+    split_step<N>(lr, gg, hv, lv);
+    stg_nt<typename Halves<N>::type>(hrow, hv);
+    stg_nt<typename Halves<N>::type>(lrow, lv);
+}
+
+template <typename T, int NB, bool GATHER, bool UPD = false, int SBU_ = 0, int DC = 0, typename SU = StepUpdate>
 __device__ __forceinline__ void bwd_body(int bid, int nblocks, float* smem, int d_, int F, int B,
                                          const T* __restrict__ dout, int64_t dout_ld, const T* __restrict__ t,
                                          int64_t t_ld, float* __restrict__ dx, int64_t dx_ld,
                                          float* __restrict__ dt, int64_t dt_ld, const GatherArgs& ga,
-                                         const T* __restrict__ x, int64_t x_ld, const StepUpdate& su = StepUpdate{}) {
+                                         const T* __restrict__ x, int64_t x_ld, const SU& su = SU{}) {
     const int d = DC > 0 ? DC : d_;  // DC: the feature size as a compile-time constant
     typedef BwdGeom<NB> G;
     constexpr int KS = 4 * NB;          // max k-steps (F <= 16 NB)
@@ -356,9 +395,11 @@ __device__ __forceinline__ void bwd_body(int bid, int nblocks, float* smem, int 
     // used instead of held in registers across the index loads
     TableDesc* tds = (TableDesc*)(smem + G::WPB * G::template lds_floats<UPD>());
     int64_t* dmap = (int64_t*)(tds + (F - 1));  // GATHER + ga.dtb: [2][F-1] row bases / strides of dt
+    uint16_t** lop = (uint16_t**)(tds + (F - 1));  // the split step (no dtb): [F-1] low-half pointers
     if (GATHER) {
         for (int t = threadIdx.x; t < F - 1; t += blockDim.x) {
             tds[t] = load_table(ga.tabs, t);
+            if constexpr (SU::kSplit) lop[t] = ldg<uint16_t*>(su.lo + t);
             if (ga.dtb) {
                 dmap[t] = ga.dtb[t];
                 dmap[F - 1 + t] = ga.dtl[t];
@@ -530,10 +571,19 @@ __device__ __forceinline__ void bwd_body(int bid, int nblocks, float* smem, int 
                                 const f32x4_t v = f32x4_t{acc[I][0][r], acc[I][1][r], acc[I][2][r], acc[I][3][r]};
                                 if (UPD && urow[I][r] != ~0u) {
                                     const f32x4_t tw = *(const f32x4_t*)(Tt + f * 64 + 4 * c);
+                                    if constexpr (SU::kSplit) {
+                                        const int64_t ro = (int64_t)urow[I][r] * d + n0;
+                                        const float g4[4] = {v[0], v[1], v[2], v[3]};
+                                        const uint32_t hb[4] = {__float_as_uint(tw[0]), __float_as_uint(tw[1]),
+                                                                __float_as_uint(tw[2]), __float_as_uint(tw[3])};
+                                        split_once_hit<4>(su.lr, g4, hb, load_halves<4>(lop[f - 1] + ro),
+                                                          (uint16_t*)tds[f - 1].data + ro, lop[f - 1] + ro);
+                                    } else {
                                     float wv[4];
 #pragma unroll
                                     for (int e = 0; e < 4; ++e) wv[e] = __builtin_fmaf(-su.lr, 0.0f + v[e], tw[e]);
                                     store_row<T, 4>((T*)tds[f - 1].data + (int64_t)urow[I][r] * d, n0, wv);
+                                    }
                                 } else if (!mapped) {
                                     stg<f32x4_t>(dt + b * dt_ld + (int64_t)f * d + n0, v);
                                 } else if (f > 0) {
@@ -633,6 +683,8 @@ __global__ __launch_bounds__(256, 2) void interact_bwd_update_kernel(int d, int 
 // x + b * x_ld + kk * d (x / x_ld carry ys / ys_ld), no index, flag or once-hit update; every dt row
 // is written.  Up to 96 features (NB <= 6): the gather-free backward of the pooled workload
 // (F = 65), one wave per 64-column super-block.
+// (SU: the once-hit rule's arguments, StepUpdate or SplitStepUpdate.  The body is text shared by the two
+// kernels below, bwd_split_body.inc: as an inlined function template it no longer compiled to the same code.)
 template <typename T, int NB, int DC, int SPB, int WPS = 2, bool MAPPED = false, int CPL = 4, bool YS = false>
 __global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) void interact_bwd_split_kernel(int d_, int F, int B, const T* __restrict__ dout,
                                                                    int64_t dout_ld, float* __restrict__ dx,
@@ -640,259 +692,32 @@ __global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) vo
                                                                    int64_t dt_ld, GatherArgs ga,
                                                                    const T* __restrict__ x, int64_t x_ld,
                                                                    StepUpdate su) {
-    static_assert(CPL == 4 || (CPL == 8 && sizeof(T) == 2), "8 columns per lane: bf16 rows");
-    constexpr int NS = 16 * NB;
-    constexpr int KS = 4 * NB;
-    constexpr int PMAX = NS * (NS - 1) / 2;
-    constexpr int SBC = 16 * CPL;  // columns per super-block
-    // the wave's tile of T: fp32 (CPL = 4) or the rows' own bf16 (CPL = 8)
-    typedef typename std::conditional<CPL == 8, uint16_t, float>::type TileT;
-    const int d = DC > 0 ? DC : d_;
-    __shared__ float pk_all[SPB][PMAX];  // each sample's packed gradient row
-    // each wave's tile of T (the once-hit update reads it; YS has none)
-    __shared__ __attribute__((aligned(16))) TileT tt_all[YS ? 1 : WPS * SPB][YS ? 4 : NS * SBC];
-    __shared__ TableDesc tds[YS ? 1 : NS];
-    __shared__ int64_t dmap[MAPPED ? 2 * NS : 1];  // table t's dt rows at dt + dmap[t] + b * dmap[F - 1 + t]
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int pair = w / WPS, h = w % WPS;
-    constexpr bool mapped = MAPPED;
-    const int c = lane & 15, q = lane >> 4;
-    const int64_t b = (int64_t)blockIdx.x * SPB + pair;
-    const bool live = b < B;
-    const int64_t bb = live ? b : 0;  // a padding sample reads sample 0 (and stores nothing)
-    const int ksteps = (F + 3) / 4;
-    const int P = F * (F - 1) / 2;
-    const T* ob = dout + bb * dout_ld;
-    float* pk = pk_all[pair];
-    TileT* Tt = tt_all[YS ? 0 : w];
-    if (h == 0) WT(1, 0, b);
-    // the table descriptors (F - 1 <= NS <= 32 < blockDim: one per thread), held in registers and
-    // written to LDS after the other independent loads are issued, so no wave waits for them alone
-    const bool tdl_ok = !YS && (int)threadIdx.x < F - 1;
-    const TableDesc tdl = YS ? TableDesc{nullptr, 0} : load_table(ga.tabs, tdl_ok ? (int)threadIdx.x : 0);
-    int64_t dm0 = 0, dm1 = 0;
-    if constexpr (MAPPED) {
-        dm0 = ldg<int64_t>(ga.dtb + (tdl_ok ? threadIdx.x : 0));
-        dm1 = ldg<int64_t>(ga.dtl + (tdl_ok ? threadIdx.x : 0));
-    }
-    // ---- every independent load first: table `lane`'s index and flag, the packed gradients, x part
-    const bool tl = !YS && lane < F - 1;
-    const int64_t myidx = YS ? 0 : load_index_if(tl, ga.idx, ga.itype, (int64_t)(tl ? lane : 0) * ga.tstride + bb);
-    // su.single NULL (dlrm_interact_bwd_blocked, YS): no once-hit update, every table row goes to dt
-    const uint8_t myfl = su.single ? ldg<uint8_t>(su.single + (tl ? (int64_t)lane * su.cap + bb : 0)) : (uint8_t)0;
-    constexpr int PPW = (PMAX + 64 * WPS - 1) / (64 * WPS);  // packed values staged per lane
-    float pv[PPW];
-#pragma unroll
-    for (int k = 0; k < PPW; ++k) {
-        const int p = h * 64 + lane + 64 * WPS * k;
-        const float v = to_f32(ldg<T>(ob + d + (p < P ? p : 0)));
-        pv[k] = p < P ? v : 0.0f;
-    }
-    // super-blocks per wave (CPL = 4, WPS = 2: d <= 512 when not fixed; WPS = 1: d <= 64;
-    // CPL = 8: d <= 128, one wave)
-    // (DC = 0: WPS = 1 / 2 cover d <= 64 / 512; YS: d = 64 * WPS, one super-block per wave)
-    constexpr int SBW = YS ? 1
-                           : DC > 0 ? ((DC / SBC + WPS - 1) / WPS > 0 ? (DC / SBC + WPS - 1) / WPS : 1)
-                                    : (WPS == 2 ? 4 : 1);
-    constexpr int XV = SBC / 64;  // dout x-part values per lane and super-block
-    float xv[SBW][XV];
-#pragma unroll
-    for (int sbi = 0; sbi < SBW; ++sbi)
-#pragma unroll
-        for (int k = 0; k < XV; ++k) {
-            const int n = SBC * h + SBC * WPS * sbi + 64 * k + lane;
-            xv[sbi][k] = to_f32(ldg<T>(ob + (n < d ? n : 0)));
-        }
-    const bool frozen = su.single ? *su.err != 0 : true;  // a bounds error this step: no table row is written
-    if (su.single && blockIdx.x == 0 && threadIdx.x == 0) snapshot_error(su.err, frozen ? 1u : 0u);
-    if (tdl_ok) {
-        tds[threadIdx.x] = tdl;
-        if constexpr (MAPPED) {
-            dmap[threadIdx.x] = dm0;
-            dmap[F - 1 + threadIdx.x] = dm1;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < PPW; ++k) {
-        const int p = h * 64 + lane + 64 * WPS * k;
-        if (p < PMAX) pk[p] = pv[k];
-    }
-    __syncthreads();  // tds, pk
-    // validate this lane's table index; rows travel as 32-bit (~0u = invalid / no table)
-    uint32_t myrow = ~0u;
-    if (tl) {
-        const int64_t r = myidx - ga.base;
-        if (r >= 0 && r < tds[lane].nrows) myrow = (uint32_t)r;
-        else if (h == 0 && live) raise_index_error(ga.err);
-    }
-    const T* rowp[KS];
-    unsigned livek = 0;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        const int kk = 4 * s + q;
-        const uint32_t r = (uint32_t)__shfl((int)myrow, kk >= 1 ? kk - 1 : 0, 64);
-        const bool tab = s < ksteps && kk >= 1 && kk < F && r != ~0u;
-        const T* src = YS ? ((s < ksteps && kk < F) ? x + bb * x_ld + (int64_t)kk * d : nullptr)
-                   : (s < ksteps && kk == 0) ? x + bb * x_ld
-                                             : (tab ? (const T*)tds[kk - 1].data + (int64_t)r * d : nullptr);
-        livek |= src ? (1u << s) : 0u;
-        // (CPL = 8: a masked row reads the zero row -- a 16-B aligned source whatever dout's layout)
-        rowp[s] = src ? src : (CPL == 8 ? (const T*)g_zero_row : ob);
-    }
-    uint32_t urow[NB][4];
-#pragma unroll
-    for (int I = 0; I < NB; ++I)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int f = I * 16 + 4 * q + r;
-            const int src = (f >= 1 && f < F) ? f - 1 : 0;
-            const uint32_t row = (uint32_t)__shfl((int)myrow, src, 64);
-            const int fl = __shfl((int)myfl, src, 64);
-            urow[I][r] = (f >= 1 && f < F && !frozen && fl != 0) ? row : ~0u;
-        }
-    if (h == 0) WT(1, 1, b);
-#pragma unroll
-    for (int sbi = 0; sbi < SBW; ++sbi) {
-        const int sb = SBC * h + SBC * WPS * sbi;
-        if (sb >= d) break;
-        const int n0 = sb + CPL * c;  // this lane's CPL output columns
-        const bool colok = n0 < d;
-        const int nc = colok ? n0 : 0;
-        f32x4_t acc[NB][CPL];
-#pragma unroll
-        for (int I = 0; I < NB; ++I)
-#pragma unroll
-            for (int e = 0; e < CPL; ++e) acc[I][e] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if constexpr (CPL == 4) {
-            f32x4_t bv[KS];
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                const f32x4_t v = load4_f32(rowp[s] + nc);
-                bv[s] = ((livek >> s) & 1u) && colok ? v : f32x4_t{0.f, 0.f, 0.f, 0.f};
-            }
-            if (sbi > 0) wave_lds_sync();  // the previous super-block's tile reads are done
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-                if (s < ksteps) *(f32x4_t*)(Tt + (4 * s + q) * SBC + 4 * c) = bv[s];
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                if (s < ksteps) {
-                    const int kk = 4 * s + q;
-#pragma unroll
-                    for (int I = 0; I < NB; ++I) {
-                        // S[16I+c][kk]: the symmetric zero-diagonal unpack of the pair row
-                        const int i = I * 16 + c;
-                        const int hi = i > kk ? i : kk, lo = i > kk ? kk : i;
-                        const float av = (i != kk && hi < F) ? pk[hi * (hi - 1) / 2 + lo] : 0.0f;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            acc[I][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[s][e], acc[I][e], 0, 0, 0);
-                    }
-                }
-            }
-        } else {
-            typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-            u32x4_t bv[KS];  // 8 bf16 columns of row 4s+q, packed
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                const u32x4_t v = ldg<u32x4_t>(rowp[s] + nc);
-                bv[s] = ((livek >> s) & 1u) && colok ? v : u32x4_t{0u, 0u, 0u, 0u};
-            }
-            if (sbi > 0) wave_lds_sync();  // the previous super-block's tile reads are done
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-                if (s < ksteps) *(u32x4_t*)(Tt + (4 * s + q) * SBC + 8 * c) = bv[s];
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                if (s < ksteps) {
-                    const int kk = 4 * s + q;
-#pragma unroll
-                    for (int I = 0; I < NB; ++I) {
-                        const int i = I * 16 + c;
-                        const int hi = i > kk ? i : kk, lo = i > kk ? kk : i;
-                        const float av = (i != kk && hi < F) ? pk[hi * (hi - 1) / 2 + lo] : 0.0f;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const uint32_t wd = bv[s][e >> 1];
-                            const float bvf = __uint_as_float((e & 1) ? (wd & 0xffff0000u) : (wd << 16));
-                            acc[I][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bvf, acc[I][e], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
-        if (h == 0 && sbi == 0) WT(1, 2, b);
-        // dout's x part for this lane's columns (lanes 0..15 hold output row 0)
-        float xo[CPL];
-#pragma unroll
-        for (int e = 0; e < CPL; ++e) {
-            const int n = CPL * c + e;  // column within the super-block: lane n & 63 of xv[sbi][n >> 6]
-            float xs = __shfl(xv[sbi][0], n & 63, 64);
-#pragma unroll
-            for (int k = 1; k < XV; ++k) {
-                const float t = __shfl(xv[sbi][k], n & 63, 64);
-                xs = (n >> 6) == k ? t : xs;
-            }
-            xo[e] = xs;
-        }
-        wave_lds_sync();  // the tile of T (written before the MFMAs)
-        if (!live || !colok) continue;
-#pragma unroll
-        for (int I = 0; I < NB; ++I)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int f = I * 16 + 4 * q + r;
-                if (f < F) {
-                    float v[CPL];
-#pragma unroll
-                    for (int e = 0; e < CPL; ++e) v[e] = acc[I][e][r];
-                    if (urow[I][r] != ~0u) {
-                        float wv[CPL];
-                        float tw[CPL];  // the row as gathered
-                        if constexpr (CPL == 4) {
-                            const f32x4_t t4 = *(const f32x4_t*)(Tt + f * SBC + 4 * c);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) tw[e] = t4[e];
-                        } else {
-                            typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-                            const u32x4_t t8 = *(const u32x4_t*)(Tt + f * SBC + 8 * c);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e)
-                                tw[e] = __uint_as_float((e & 1) ? (t8[e >> 1] & 0xffff0000u) : (t8[e >> 1] << 16));
-                        }
-#pragma unroll
-                        for (int e = 0; e < CPL; ++e) wv[e] = __builtin_fmaf(-su.lr, 0.0f + v[e], tw[e]);
-                        store_row<T, CPL, true>((T*)tds[f - 1].data + (int64_t)urow[I][r] * d, n0, wv);
-                    } else if (!mapped && (f > 0 || !su.single)) {
-                        // (the training step (su.single set) leaves dt's x row alone: dx carries it)
-                        // (CPL = 8: a lane's two 16-B pieces are 32 B apart, so each store instruction
-                        // covers half of every line: plain stores let L2 merge the halves, where
-                        // non-temporal ones left as partial-line writes, 95 -> 117 MB per launch)
-#pragma unroll
-                        for (int e = 0; e < CPL; e += 4) {
-                            const f32x4_t pv4 = f32x4_t{v[e], v[e + 1], v[e + 2], v[e + 3]};
-                            if constexpr (CPL == 8) stg<f32x4_t>(dt + b * dt_ld + (int64_t)f * d + n0 + e, pv4);
-                            else stg_nt<f32x4_t>(dt + b * dt_ld + (int64_t)f * d + n0 + e, pv4);
-                        }
-                    } else if (f > 0) {
-#pragma unroll
-                        for (int e = 0; e < CPL; e += 4)
-                            stg_nt<f32x4_t>(dt + dmap[f - 1] + b * dmap[F - 2 + f] + n0 + e,
-                                            f32x4_t{v[e], v[e + 1], v[e + 2], v[e + 3]});
-                    }
-                    if (f == 0)
-#pragma unroll
-                        for (int e = 0; e < CPL; e += 4)
-                            stg<f32x4_t>(dx + b * dx_ld + n0 + e, f32x4_t{xo[e] + v[e], xo[e + 1] + v[e + 1],
-                                                                         xo[e + 2] + v[e + 2], xo[e + 3] + v[e + 3]});
-                }
-            }
-        if (h == 0 && sbi == 0) {
-            WT(1, 3, b);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            WT(1, 4, b);
-        }
-    }
+    typedef StepUpdate SU;
+#include "bwd_split_body.inc"
+}
+
+// The training step's backward on split-bf16 tables (dlrm_split_step_bwd): the same kernel with the split
+// rule's once-hit write, in the step's three default geometries (d = 128: two waves per sample, or 8
+// columns per lane for B > 2048 and more than 16 features; d <= 64: one wave per sample), NB = 1 and 2.
+template <int NB, int DC, int SPB, int WPS, int CPL>
+__global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : 4) void interact_bwd_split_lo_kernel(
+    int d_, int F, int B, const uint16_t* __restrict__ dout, int64_t dout_ld, float* __restrict__ dx, int64_t dx_ld,
+    float* __restrict__ dt, int64_t dt_ld, GatherArgs ga, const uint16_t* __restrict__ x, int64_t x_ld,
+    SplitStepUpdate su) {
+    typedef uint16_t T;
+    typedef SplitStepUpdate SU;
+    constexpr bool MAPPED = false, YS = false;
+#include "bwd_split_body.inc"
+}
+// ... and interact_bwd_update_kernel's (any other d with F <= 32)
+template <int NB>
+__global__ __launch_bounds__(256, 2) void interact_bwd_update_lo_kernel(
+    int d, int F, int B, const uint16_t* __restrict__ dout, int64_t dout_ld, float* __restrict__ dx, int64_t dx_ld,
+    float* __restrict__ dt, int64_t dt_ld, GatherArgs ga, const uint16_t* __restrict__ x, int64_t x_ld,
+    SplitStepUpdate su) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    bwd_body<uint16_t, NB, true, true, 1, 0, SplitStepUpdate>(blockIdx.x, gridDim.x, smem, d, F, B, dout, dout_ld, nullptr, 0,
+                                                              dx, dx_ld, dt, dt_ld, ga, x, x_ld, su);
 }
 
 // ------------------------------------------------------------------ scalar fallbacks
@@ -1296,11 +1121,50 @@ int launch_step_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, i
 // Training-step backward after launch_step_fwd: once-hit rows updated in place, dt rows of the
 // others written for the apply.  The caller checked the shape (launch_step_fwd accepted it)
 // and the 16-B alignment of dx / dt.
+// The same on split-bf16 tables (lo = the device array of low-half pointers, 16-B aligned rows): the default
+// geometries only (the DLRM_BWD_SPB / DLRM_BWD_CPL / DLRM_UPD_SBU overrides are the Descent kernels').
+static int launch_step_bwd_lo(dlrm_ctx* ctx, const GatherArgs& ga, int F, int d, int B, const uint16_t* x, int64_t x_ld,
+                              const uint16_t* dout, int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
+                              const SplitStepUpdate& su) {
+    const int NB = (F + 15) / 16;
+    hipStream_t s = ctx_stream(ctx);
+#define DLRM_LAUNCH_LO(N_, DC_, S_, W_, C_)                                                                        \
+    hipLaunchKernelGGL((interact_bwd_split_lo_kernel<N_, DC_, S_, W_, C_>), dim3((unsigned)((B + S_ - 1) / S_)),    \
+                       dim3(64 * W_ * S_), 0, s, d, F, B, dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, x, x_ld, su)
+    if (!knobs().bwd_nosplit && d == 128) {
+        // 8 columns per lane (B > 2048), one wave per sample, 2 samples per block: with 17..32 features.  With
+        // up to 16 the split write took that form from 6 to 5 waves per SIMD (96 VGPRs against Descent's 80),
+        // so those shapes keep the two-wave form, which holds Descent's 8.
+        if (B > 2048 && NB == 2) {
+            DLRM_LAUNCH_LO(2, 128, 2, 1, 8);
+        } else {         // two waves per sample, 4 samples per block
+            if (NB == 1) DLRM_LAUNCH_LO(1, 128, 4, 2, 4); else DLRM_LAUNCH_LO(2, 128, 4, 2, 4);
+        }
+        return ctx_hip(ctx, hipGetLastError(), "split_step_bwd(split) launch");
+    }
+    if (!knobs().bwd_nosplit && d <= 64) {  // one wave per sample, 8 samples per block
+        if (NB == 1) DLRM_LAUNCH_LO(1, 0, 8, 1, 4); else DLRM_LAUNCH_LO(2, 0, 8, 1, 4);
+        return ctx_hip(ctx, hipGetLastError(), "split_step_bwd(one wave per sample) launch");
+    }
+#undef DLRM_LAUNCH_LO
+#define DLRM_LAUNCH_LOUP(N_)                                                                                       \
+    {                                                                                                              \
+        typedef BwdGeom<N_> G;                                                                                     \
+        const size_t lds = sizeof(float) * G::template lds_floats<true>() * G::WPB +                               \
+                           (sizeof(TableDesc) + sizeof(uint16_t*)) * (F - 1);                                      \
+        hipLaunchKernelGGL((interact_bwd_update_lo_kernel<N_>), dim3(grid_for(B, G::WPB, ctx_num_cus(ctx))),        \
+                           dim3(64 * G::WPB), lds, s, d, F, B, dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, x, x_ld, su); \
+    }
+    if (NB == 1) DLRM_LAUNCH_LOUP(1) else DLRM_LAUNCH_LOUP(2)
+#undef DLRM_LAUNCH_LOUP
+    return ctx_hip(ctx, hipGetLastError(), "split_step_bwd launch");
+}
+
 int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, const void* idx, int itype,
                     int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
                     int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
                     float lr,
-                    const TableDesc* htabs) {
+                    const TableDesc* htabs, uint16_t* const* lo) {
     if (B == 0 || T_ == 0) return DLRM_OK;
     const int F = T_ + 1;
     const int NB = (F + 15) / 16;
@@ -1308,6 +1172,11 @@ int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, con
     const int cus = ctx_num_cus(ctx);
     GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
     StepUpdate su{ix.single, ix.cap, lr, ctx_error_word(ctx)};
+    if (lo) {  // split-bf16 tables (the caller checked the dtype and the low halves' alignment)
+        const SplitStepUpdate sl{su, lo};
+        return launch_step_bwd_lo(ctx, ga, F, d, B, (const uint16_t*)x, x_ld, (const uint16_t*)dout, dout_ld, dx, dx_ld,
+                                  dt, dt_ld, sl);
+    }
     // one super-block of T rows in flight: two (the gather backward's choice) spill here
     const int sbu = knobs().upd_sbu;
     // d = 128 (two 64-column super-blocks): two waves per sample (interact_bwd_split_kernel)

@@ -15,6 +15,10 @@
 #   model = kaggle_dlrm(; embedding_constructor = x -> DLRMHip.HipEmbedding(ctx, x),
 #                         interaction = DLRMHip.HipDotInteraction(ctx))
 #
+# (`Context(0; fused = true, lr = η)` runs that chain on the fused training-step kernels;
+# `Context(0; fused = true, split = HipSplitDescent(η))` does so on split-bf16 tables, through
+# dlrm_split_step_bwd / dlrm_split_step_bwd_prepare.)
+#
 # and `_Train.train!` / `DLRMModel` stay unchanged.  Dense inputs x (bottom-MLP output) and the
 # interaction output cross PCIe here because the MLPs stay on the CPU in the reference; the
 # embedding tables, the gathered rows and every kernel's scratch stay in HBM.
@@ -50,12 +54,18 @@ mutable struct Context
     # defer_update (fused, lr known): update! leaves its apply launch to the next maplookup, which runs
     # it with that batch's indexer build -- no host synchronisation per step (bounds: see poll_bounds!)
     defer::Bool
+    # split (fused): a HipSplitDescent -- the split analogue of lr on 2-byte tables: the pullback runs the
+    # split rule's backward (dlrm_split_step_bwd) and update! with that same optimizer its apply
+    split::Any
     function Context(device::Integer; stream::Ptr{Cvoid} = C_NULL, fused::Bool = false, lr = nothing,
-                     defer_update::Bool = true)
+                     defer_update::Bool = true, split = nothing)
         out = Ref{Ptr{Cvoid}}(C_NULL)
         rc = ccall((:dlrm_ctx_create, libdlrm), Cint, (Cint, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), device, stream, out)
         rc == 0 || throw(DLRMError(rc, "dlrm_ctx_create"))
-        ctx = new(out[], fused, lr === nothing ? nothing : Float32(lr), defer_update)
+        split === nothing || lr === nothing || Float32(lr) == split.eta ||
+            throw(ArgumentError("Context: lr = $lr beside split = HipSplitDescent($(split.eta))"))
+        split === nothing || (lr = split.eta)
+        ctx = new(out[], fused, lr === nothing ? nothing : Float32(lr), defer_update, split)
         finalizer(c -> ccall((:dlrm_ctx_destroy, libdlrm), Cint, (Ptr{Cvoid},), c.ptr), ctx)
         return ctx
     end
@@ -520,6 +530,47 @@ function _rule_update(opt::HipSplitDescent, ctx, tables, ixptr, flags, idxptr, s
           batch, lookups, dtptr, DLRM_F32, ld, off, opt.eta)
 end
 
+# The training step's backward / apply launches of a fused step `st` (dlrm_step_bwd and _prepare), or, on a
+# context built with `split = HipSplitDescent(η)`, the split rule's (dlrm_split_step_bwd and _prepare).
+function _step_bwd(ctx, st, delta_ld, flags)
+    d, B = size(st.x)
+    if ctx.split !== nothing
+        _, h = split_state(ctx.split, st.tables)
+        return ccall((:dlrm_split_step_bwd, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid}, Int64,
+                      Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cuint),
+                     ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
+                     st.x.ptr, d, st.delta.ptr, delta_ld, st.padding, st.dx.ptr, d, st.dt.ptr,
+                     size(st.dt, 1), ctx.lr, flags)
+    end
+    ccall((:dlrm_step_bwd, libdlrm), Cint,
+          (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid}, Int64,
+           Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cuint),
+          ctx.ptr, tableset(st.tables), st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
+          st.x.ptr, d, st.delta.ptr, delta_ld, st.padding, st.dx.ptr, d, st.dt.ptr,
+          size(st.dt, 1), ctx.lr, flags)
+end
+function _step_bwd_prepare(ctx, st, nix, next, flags)
+    d, B = size(st.x)
+    if ctx.split !== nothing
+        _, h = split_state(ctx.split, st.tables)
+        return ccall((:dlrm_split_step_bwd_prepare, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid},
+                      Int64, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat,
+                      Ptr{Cvoid}, Ptr{Cvoid}, Cuint),
+                     ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
+                     st.x.ptr, d, st.delta.ptr, size(st.delta, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
+                     size(st.dt, 1), ctx.lr, nix.ptr, next.data.ptr, flags)
+    end
+    ccall((:dlrm_step_bwd_prepare, libdlrm), Cint,
+          (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid},
+           Int64, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat,
+           Ptr{Cvoid}, Ptr{Cvoid}, Cuint),
+          ctx.ptr, tableset(st.tables), st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
+          st.x.ptr, d, st.delta.ptr, size(st.delta, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
+          size(st.dt, 1), ctx.lr, nix.ptr, next.data.ptr, flags)
+end
+
 # update!(HipADAGrad / HipRowwiseADAGrad / HipSplitDescent, tables, grads, indexers): the unfused path
 # builds the indexer in the call; after a fused step's pullback that wrote every dt row (a fused context
 # without a learning rate) the forward's split indexer is reused (_fused_update!).
@@ -697,22 +748,11 @@ function flush!(tables; next = nothing)
     d, B = size(st.x)
     if next !== nothing && next.batch == st.idx.batch && next.lookups == 1
         nix = st.spare === nothing ? HipIndexer(ctx, length(st.tables), B) : st.spare
-        check(ctx, ccall((:dlrm_step_bwd_prepare, libdlrm), Cint,
-                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid},
-                          Int64, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat,
-                          Ptr{Cvoid}, Ptr{Cvoid}, Cuint),
-                         ctx.ptr, tableset(st.tables), st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
-                         st.x.ptr, d, st.delta.ptr, size(st.delta, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
-                         size(st.dt, 1), ctx.lr, nix.ptr, next.data.ptr, STEP_APPLY_ONLY))
+        check(ctx, _step_bwd_prepare(ctx, st, nix, next, STEP_APPLY_ONLY))
         st.spare, st.ix = st.ix, nix
         st.pending = next => next          # train_step_fwd! finds this batch's indexer prepared
     else
-        check(ctx, ccall((:dlrm_step_bwd, libdlrm), Cint,
-                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid}, Int64,
-                          Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cuint),
-                         ctx.ptr, tableset(st.tables), st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
-                         st.x.ptr, d, st.delta.ptr, size(st.delta, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
-                         size(st.dt, 1), ctx.lr, STEP_APPLY_ONLY))
+        check(ctx, _step_bwd(ctx, st, size(st.delta, 1), STEP_APPLY_ONLY))
     end
     delete!(CHAIN_PENDING, tables)
     return nothing
@@ -791,12 +831,7 @@ function ChainRulesCore.rrule(dot::HipDotInteraction, X, ys::HipLookup{T}) where
         # a DeviceMatrix Δ (the top MLP on the GPU) is read in place; a host one is uploaded
         st.delta = Δh isa DeviceMatrix ? Δh : upload!(DeviceMatrix{T}(st.ctx, size(Δh)...), Matrix{T}(Δh))
         if st.ctx.lr !== nothing   # once-hit rows stepped here, the others' dt rows left for update!
-            check(st.ctx, ccall((:dlrm_step_bwd, libdlrm), Cint,
-                                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid},
-                                 Int64, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cuint),
-                                st.ctx.ptr, tableset(st.tables), st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch,
-                                1, B, st.x.ptr, d, st.delta.ptr, size(Δh, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
-                                size(st.dt, 1), st.ctx.lr, STEP_BWD_ONLY))
+            check(st.ctx, _step_bwd(st.ctx, st, size(Δh, 1), STEP_BWD_ONLY))  # (split context: the split rule's)
             st.bwd = :once_hit_applied
         else                       # every dt row written (T re-gathered, no ys)
             check(st.ctx, ccall((:dlrm_interact_bwd_gather, libdlrm), Cint,
@@ -831,7 +866,10 @@ end
 function _fused_update!(opt, st, tables)
     ctx = st.ctx
     d, B = size(st.x)
-    if opt isa Union{AbstractHipADAGrad,HipSplitDescent}
+    ctx.split === nothing || opt === ctx.split ||
+        throw(ArgumentError("this context steps its tables with its HipSplitDescent (the pullback ran its backward); " *
+                            "update! got $(nameof(typeof(opt)))"))
+    if opt isa Union{AbstractHipADAGrad,HipSplitDescent} && ctx.split === nothing
         # every dt row is needed: the forward's split indexer, the once-hit rows as singles items
         st.bwd === :once_hit_applied &&
             throw(ArgumentError("the pullback already stepped the once-hit rows with Descent (η = $(ctx.lr)) and left " *
@@ -854,12 +892,7 @@ function _fused_update!(opt, st, tables)
         return nothing
     elseif st.bwd === :once_hit_applied
         opt.eta == ctx.lr || throw(ArgumentError("the pullback stepped the once-hit rows with η = $(ctx.lr), update! got $(opt.eta)"))
-        check(ctx, ccall((:dlrm_step_bwd, libdlrm), Cint,
-                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid}, Int64,
-                          Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cuint),
-                         ctx.ptr, tableset(st.tables), st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
-                         st.x.ptr, d, st.delta.ptr, size(st.delta, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
-                         size(st.dt, 1), ctx.lr, STEP_APPLY_ONLY))
+        check(ctx, _step_bwd(ctx, st, size(st.delta, 1), STEP_APPLY_ONLY))
     elseif st.bwd === :all_dt         # the forward's split indexer: once-hit rows as singles items
         check(ctx, ccall((:dlrm_sgd_update, libdlrm), Cint,
                          (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cuint, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint,

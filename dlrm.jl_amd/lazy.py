@@ -21,6 +21,9 @@ DLRMHip.jl's lazy `maplookup` for `HipEmbedding`):
   update!              -> dlrm_step_bwd(DLRM_STEP_APPLY_ONLY) (the repeated rows), or, without a
                           known η, dlrm_sgd_update(PREBUILT) with the forward's split indexer
 
+`HipTables(tables, opt=SplitDescent(η))` on bfloat16 tables is the same chain with the split rule: the
+pullback is dlrm_split_step_bwd(DLRM_STEP_BWD_ONLY), update! with that optimizer its APPLY_ONLY launch.
+
 Three launches per step, bit for bit the result of `HotPath.step` and of the five-launch chain.
 
 With the learning rate known, `update!` is deferred by default (`HipTables(..., defer_update=True)`, a
@@ -52,10 +55,19 @@ class HipTables:
     lr known, update! leaves its apply launch to the next maplookup (bounds errors surface there,
     from a snapshot of the device flag, or at check_bounds / a read of the tables); False: update!
     runs it at once and synchronises to check bounds, as the reference's update! returns with the
-    tables written."""
+    tables written.  opt: a SplitDescent(η) on bfloat16 tables, the split analogue of lr=η: the pullback
+    runs the split rule's backward (dlrm_split_step_bwd) and update! with that same optimizer object runs
+    or defers its apply."""
 
-    def __init__(self, tables, *, lr=None, index_base=1, defer_update=True):
+    def __init__(self, tables, *, lr=None, index_base=1, defer_update=True, opt=None):
         self._ts = as_table_set(tables) if not isinstance(tables, EmbeddingTableSet) else tables
+        if opt is not None:
+            if not isinstance(opt, SplitDescent):
+                raise TypeError("HipTables: opt is a SplitDescent (Descent: lr=eta)")
+            if lr is not None and float(lr) != opt.eta:
+                raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}")
+            lr = opt.eta
+        self.opt = opt
         self.lr = None if lr is None else float(lr)
         self.index_base = int(index_base)  # 1: Julia's, as maplookup / update_ default to
         self.defer_update = bool(defer_update)
@@ -129,7 +141,8 @@ class HipTables:
         from .hotpath import HotPath
         hp = self._hp.get(batch)
         if hp is None:
-            hp = HotPath(self._ts, batch, 1, lr=0.0 if self.lr is None else self.lr, index_base=self.index_base)
+            hp = HotPath(self._ts, batch, 1, lr=0.0 if self.lr is None else self.lr, index_base=self.index_base,
+                         opt=self.opt, fused_step=self.opt is not None)
             if not hp.step_api:
                 raise ValueError("HipTables: this table set has no training-step kernels (deterministic, one-hot)")
             self._hp[batch] = hp
@@ -255,8 +268,10 @@ def update_lazy(opt, tables, grads, *, check_bounds=None):
     if len(grads) != len(tables) or any(g.lazy is not lz or g.table_index != t for t, g in enumerate(grads)):
         raise ValueError("update_ expects the per-table views of one maplookup pullback")
     hp = lz.hp
+    if tables.opt is not None and opt is not tables.opt:
+        raise ValueError(f"these HipTables step with {tables.opt!r} (the pullback ran its backward); update! got {opt!r}")
     tables.flush()
-    if isinstance(opt, _StatefulOpt):
+    if isinstance(opt, _StatefulOpt) and tables.opt is None:
         # every dt row is needed: the forward's split indexer, the once-hit rows as singles items
         if lz.applied:
             raise ValueError(f"the pullback already stepped the once-hit rows with Descent (HipTables(lr={tables.lr})) "
@@ -264,7 +279,7 @@ def update_lazy(opt, tables, grads, *, check_bounds=None):
                              f"{type(opt).__name__}")
         hp.opt_update(lz.idx, prebuilt=True, opt=opt)
     elif lz.applied:
-        if opt.eta != tables.lr:
+        if tables.opt is None and opt.eta != tables.lr:
             raise ValueError(f"the pullback stepped the once-hit rows with η = {tables.lr}; update! got {opt.eta}")
         if tables.defer_update and not check_bounds:
             tables._pending = lz  # applied by the next maplookup's launch (or any read of the tables)
@@ -273,6 +288,8 @@ def update_lazy(opt, tables, grads, *, check_bounds=None):
             tables._unchecked = tables._unchecked or check_bounds is None
             return tables
         hp.step_bwd(lz.delta, x=lz.x, idx=lz.idx, flags=_lib.STEP_APPLY_ONLY)
+    elif tables.opt is not None:  # (a shape without the split backward: every dt row was written)
+        hp.opt_update(lz.idx, prebuilt=True, opt=opt)
     else:
         hp.lr = opt.eta
         hp.sgd_update(lz.idx, prebuilt=True)  # the forward's split indexer: once-hit rows as singles items

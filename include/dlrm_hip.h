@@ -290,9 +290,12 @@ int dlrm_indexer_set_chunk(dlrm_ctx* ctx, dlrm_indexer* indexer, int max_positio
 int dlrm_indexer_set_parts(dlrm_ctx* ctx, dlrm_indexer* indexer, int parts);
 
 /* Host-side state of the last build (no GPU call): a mask of DLRM_IX_* bits.  SINGLES_DONE: a
- * split backward (dlrm_step_bwd) has stepped this build's once-hit rows, so its dt holds only
- * the repeated rows' gradients.  (The Julia shim's pullback state, DLRMHip.jl `st.bwd`.) */
-enum { DLRM_IX_BUILT = 1, DLRM_IX_SPLIT = 2, DLRM_IX_PREPARED = 4, DLRM_IX_SINGLES_DONE = 8 };
+ * split backward (dlrm_step_bwd or dlrm_split_step_bwd) has stepped this build's once-hit rows, so
+ * its dt holds only the repeated rows' gradients; SINGLES_SPLIT, set with it: that backward was
+ * dlrm_split_step_bwd's (the split rule on split-bf16 tables), so only the split rule's apply may
+ * complete it.  (The Julia shim's pullback state, DLRMHip.jl `st.bwd`.) */
+enum { DLRM_IX_BUILT = 1, DLRM_IX_SPLIT = 2, DLRM_IX_PREPARED = 4, DLRM_IX_SINGLES_DONE = 8,
+       DLRM_IX_SINGLES_SPLIT = 16 };
 int dlrm_indexer_state(const dlrm_indexer* indexer, unsigned* state);
 
 /* Backward of a training step without a materialized ys (see above). */
@@ -392,15 +395,17 @@ int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagrad* opt, d
  *
  * Do not mix: dlrm_sgd_update, dlrm_adagrad_update or dlrm_step_bwd on such tables write a ROUNDED
  * bf16 step into the high half and leave the low half as it was, after which the pair no longer
- * holds the master weight.
+ * holds the master weight.  The fused training step of these tables is dlrm_split_step_bwd (below).
  *
  * dlrm_split_sgd_create uploads the per-table low-half pointers once: tables that are not
  * DLRM_BF16, or a table with rows and lo[t] == NULL, return DLRM_E_ARG.  16-B aligned lo[t] (and
  * dim * 2 % 16 == 0) let the vector kernels run; anything else takes the any-dim kernels with the
  * same results.  dlrm_split_sgd_update: tables that are not DLRM_BF16, or an optimizer created for
  * another table count / dim, return DLRM_E_ARG; DLRM_UPDATE_ATOMIC returns DLRM_E_UNSUPPORTED;
- * DLRM_UPDATE_PREBUILT is honoured; an indexer in state DLRM_IX_SINGLES_DONE returns DLRM_E_STATE
- * (a split backward has already written those rows' high halves with a rounded bf16 step); a
+ * DLRM_UPDATE_PREBUILT is honoured; an indexer in state DLRM_IX_SINGLES_DONE without
+ * DLRM_IX_SINGLES_SPLIT returns DLRM_E_STATE (dlrm_step_bwd's backward has already written those
+ * rows' high halves with a rounded bf16 step), with DLRM_IX_SINGLES_SPLIT (dlrm_split_step_bwd's
+ * backward stepped them with this rule) only the repeated rows are applied, from their dt rows; a
  * split indexer whose singles are not done is taken whole, once-hit rows included.  Launches
  * neither allocate nor synchronise beyond what dlrm_sgd_update does, so the call is
  * graph-capturable.  dlrm_split_sgd_destroy of NULL returns 0. */
@@ -461,6 +466,37 @@ int dlrm_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_indexer* inde
                           const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
                           float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr,
                           dlrm_indexer* next_indexer, const void* next_indices, unsigned flags);
+
+/* ---- the training step on split-bf16 tables (see "split-bf16 tables" above): dlrm_step_bwd and
+ * dlrm_step_bwd_prepare with the split rule in place of Descent, after the same forward
+ * (dlrm_step_fwd / dlrm_lookup_interact_fwd read the high halves only).
+ *   dlrm_split_step_bwd = dlrm_interact_bwd_gather + dlrm_split_sgd_update(opt, PREBUILT): dx is
+ *   bit-identical to dlrm_interact_bwd_gather's and both halves of every touched row end up
+ *   bit-identical to dlrm_split_sgd_update's.  A once-hit row is stepped inside the backward: its
+ *   master weight is the gathered bf16 element (high half) merged with its low half,
+ *   W' = fmaf(-lr, 0 + g, W), both halves stored (NaN: the quiet bit, as above); its dt row is
+ *   never written.  The apply launch steps the repeated rows from their dt rows with the same rule.
+ * Arguments, flags (DLRM_STEP_BWD_ONLY / DLRM_STEP_APPLY_ONLY), alignment rules and fallbacks are
+ * dlrm_step_bwd's: a shape without a split backward (F > 32, x or rows not 16-B aligned, low-half
+ * pointers not 16-B aligned) runs dlrm_interact_bwd_gather and lets the split apply take the
+ * once-hit rows; dlrm_split_step_bwd_prepare on a shape without an in-apply build runs the plain
+ * step.  Tables that are not DLRM_BF16, or an optimizer created for another table count / dim,
+ * return DLRM_E_ARG.  A set bounds flag leaves both halves of every row unwritten.
+ * The indexer remembers the rule that stepped its once-hit rows (DLRM_IX_SINGLES_SPLIT), and only
+ * that rule completes the backward: dlrm_step_bwd(APPLY_ONLY), dlrm_sgd_update(PREBUILT) and
+ * dlrm_adagrad_update(PREBUILT) after dlrm_split_step_bwd's backward return DLRM_E_STATE, and so
+ * does dlrm_split_step_bwd(APPLY_ONLY) after dlrm_step_bwd's; nothing is written.
+ * dlrm_split_sgd_update(PREBUILT) after dlrm_split_step_bwd(BWD_ONLY) applies the repeated rows. */
+int dlrm_split_step_bwd(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_split_sgd* opt, dlrm_indexer* indexer,
+                        const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                        const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
+                        float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr, unsigned flags);
+int dlrm_split_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_split_sgd* opt,
+                                dlrm_indexer* indexer,
+                                const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                                const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
+                                float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr,
+                                dlrm_indexer* next_indexer, const void* next_indices, unsigned flags);
 
 /* ---- table-sharded exchange over RCCL ------------------------------------
  * DLRM.jl is one process: maplookup hands its output straight to the interaction (model.jl:161-163).
