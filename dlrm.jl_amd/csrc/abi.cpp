@@ -62,6 +62,10 @@ struct dlrm_adagrad : StatePtrs<float> {
 // The low halves of split-bf16 tables
 struct dlrm_split_sgd : StatePtrs<uint16_t> {};
 
+// The rule that stepped a split build's once-hit rows inside the step backward, and its bit of dlrm_indexer_state
+enum { kRuleDescent = 0, kRuleSplit = 1, kRuleAdagrad = 2, kRuleRowwise = 3 };
+static const unsigned kRuleBits[4] = {0u, DLRM_IX_SINGLES_SPLIT, DLRM_IX_SINGLES_ADAGRAD, DLRM_IX_SINGLES_ROWWISE};
+
 struct dlrm_indexer {
     dlrm_ctx* ctx = nullptr;
     int T = 0;
@@ -76,7 +80,7 @@ struct dlrm_indexer {
     bool split = false;  // built by dlrm_step_fwd's kernel: once-hit rows are left to the backward
     bool prepared = false;  // built by dlrm_step_bwd_prepare for the next dlrm_step_fwd (not yet consumed)
     bool singles_done = false;  // a split backward has applied this build's once-hit rows already
-    bool singles_split = false;  // ... with the split rule (dlrm_split_step_bwd), not Descent
+    int singles_rule = 0;  // ... with this rule (kRule*): Descent, or the rule of dlrm_split_step_bwd / dlrm_adagrad_step_bwd
     // device words for the bounds errors of builds that may run beside a step's write-deciding
     // kernels, which read the ctx's flag to decide whether to write (raising there would be a race,
     // ADVICE r5): [0] dlrm_indexer_prepare (a side-stream build beside the current step; cleared
@@ -156,7 +160,8 @@ static void record_build(dlrm_indexer* ix, bool split, const void* indices, int 
     ix->built = true;
     ix->split = split;
     ix->prepared = false;
-    ix->singles_done = ix->singles_split = false;
+    ix->singles_done = false;
+    ix->singles_rule = kRuleDescent;
     ix->dev.has_map = 0;  // (set by dlrm_step_bwd_prepare, whose wave build writes the item map)
     ix->dev.build_err = nullptr;  // (set by dlrm_indexer_prepare)
     ix->indices = indices;
@@ -738,7 +743,8 @@ static int indexer_carve(dlrm_ctx* ctx, dlrm_indexer* ix, int parts) {
     ix->dev = d;
     ix->TV = (int)T;
     ix->bytes = total;
-    ix->built = ix->prepared = ix->singles_done = ix->singles_split = false;
+    ix->built = ix->prepared = ix->singles_done = false;
+    ix->singles_rule = kRuleDescent;
     ix->dev.has_map = 0;
     ix->dev.build_err = nullptr;
     return DLRM_OK;
@@ -957,7 +963,7 @@ int dlrm_indexer_state(const dlrm_indexer* ix, unsigned* state) {
     if (!ix || !state) return DLRM_E_ARG;
     *state = (ix->built ? DLRM_IX_BUILT : 0u) | (ix->split ? DLRM_IX_SPLIT : 0u) |
              (ix->prepared ? DLRM_IX_PREPARED : 0u) | (ix->singles_done ? DLRM_IX_SINGLES_DONE : 0u) |
-             (ix->singles_done && ix->singles_split ? DLRM_IX_SINGLES_SPLIT : 0u);
+             (ix->singles_done ? kRuleBits[ix->singles_rule] : 0u);
     return DLRM_OK;
 }
 
@@ -1025,18 +1031,21 @@ struct UpdateRule {
     const char* no_atomic;     // why the rule has no atomic mode; NULL: it has one
     const char* singles_done;  // how a split backward stepped the once-hit rows, which the rule cannot take over;
                                // NULL: it skips them (their dt rows are all the backward left unwritten)
-    bool split_rule;           // the rule of dlrm_split_step_bwd: it completes that backward, and no other does
+    int rule;                  // kRule*: it completes the step backward of its own rule, and no other does
 };
-static const UpdateRule kSgdUpdate = {"dlrm_sgd_update", false, nullptr, nullptr, nullptr, false};
+static const UpdateRule kSgdUpdate = {"dlrm_sgd_update", false, nullptr, nullptr, nullptr, kRuleDescent};
 // (an atomic add never holds the row's whole sum, which the rule squares; a split backward stepped its once-hit
 // rows with Descent and left their dt rows unwritten)
 static const UpdateRule kAdagradUpdate = {"dlrm_adagrad_update", false, "the optimizer state was",
-                                          "the rule needs each row's complete sum", "Descent", false};
+                                          "the rule needs each row's complete sum", "Descent", kRuleAdagrad};
+// (the same entry point with a row-wise handle: the rule's kind comes from the handle)
+static const UpdateRule kRowwiseUpdate = {"dlrm_adagrad_update", false, "the optimizer state was",
+                                          "the rule needs each row's complete sum", "Descent", kRuleRowwise};
 // (an atomic add on one half cannot carry into the other; a split backward wrote its once-hit rows' high halves
 // with a rounded bf16 step and left their dt rows unwritten -- but dlrm_split_step_bwd's backward stepped them
 // with this rule, and then the update takes the repeated rows that are left)
 static const UpdateRule kSplitUpdate = {"dlrm_split_sgd_update", true, "the low halves were",
-                                        "a row's two halves are stepped together", "a rounded bf16 Descent", true};
+                                        "a row's two halves are stepped together", "a rounded bf16 Descent", kRuleSplit};
 
 // The common part of the update entry points, from the index checks to the indexer's build: sa = the
 // launch's once-hit items.  *atomic: DLRM_UPDATE_ATOMIC of a rule that has the mode (nothing is built).
@@ -1063,12 +1072,17 @@ static int update_prologue(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, con
     if (flags & DLRM_UPDATE_PREBUILT) {
         if (!built_from(ix, indices, itype, table_stride, index_base, batch, lookups))
             return ctx_fail(ctx, DLRM_E_STATE, "%s: indexer was not built from these indices", r.fn);
-        if (ix->singles_done && ix->singles_split && !r.split_rule)
+        // only the rule that stepped a build's once-hit rows applies its repeated rows
+        if (ix->singles_done && ix->singles_rule == kRuleSplit && r.rule != kRuleSplit)
             return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_split_step_bwd) already stepped this build's "
                             "once-hit rows with the split rule", r.fn);
-        if (ix->singles_done && !ix->singles_split && r.singles_done)
+        if (ix->singles_done && ix->singles_rule == kRuleDescent && r.singles_done)
             return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_step_bwd) already stepped this build's "
                             "once-hit rows with %s", r.fn, r.singles_done);
+        if (ix->singles_done && ix->singles_rule >= kRuleAdagrad && r.rule != ix->singles_rule)
+            return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_adagrad_step_bwd) already stepped this build's "
+                            "once-hit rows with the %s Adagrad rule", r.fn,
+                            ix->singles_rule == kRuleRowwise ? "row-wise" : "element-wise");
     } else {
         rc = dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, lookups);
         if (rc) return rc;
@@ -1117,7 +1131,7 @@ int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_i
     CHECK_ARG(ctx && tb && op && ix, "dlrm_adagrad_update: null ctx/tables/optimizer/indexer");
     SinglesArgs sa;
     bool atomic;
-    const int rc = update_prologue(ctx, tb, ix, kAdagradUpdate, op, flags, indices, itype, table_stride, index_base, batch,
+    const int rc = update_prologue(ctx, tb, ix, op->rowwise ? kRowwiseUpdate : kAdagradUpdate, op, flags, indices, itype, table_stride, index_base, batch,
                                    lookups, grad, grad_dtype, grad_ld, grad_offset, &sa, &atomic);
     if (rc) return rc;
     if (op->rowwise)
@@ -1235,21 +1249,30 @@ int dlrm_step_fwd(dlrm_ctx* ctx, const dlrm_tables* tb, dlrm_indexer* ix, const 
     return dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, 1);
 }
 
-// The once-hit rule of a training step's backward and apply: Descent (op NULL; dlrm_step_bwd) or the split rule
-// on split-bf16 tables (dlrm_split_step_bwd).  An indexer remembers which one stepped its once-hit rows
-// (singles_split), and only the same rule's apply completes that backward.
+// The once-hit rule of a training step's backward and apply: Descent (dlrm_step_bwd), the split rule on
+// split-bf16 tables (dlrm_split_step_bwd) or a sparse Adagrad rule (dlrm_adagrad_step_bwd; element-wise or
+// row-wise by its handle).  An indexer remembers which one stepped its once-hit rows (singles_rule), and only
+// the same rule's apply completes that backward.
 struct StepRule {
-    const char* fn;      // the entry point, for the messages
-    dlrm_split_sgd* op;  // the low halves; NULL: Descent
+    const char* fn;              // the entry point, for the messages
+    int kind = kRuleDescent;     // kRule*
+    dlrm_split_sgd* op = nullptr;   // kRuleSplit: the low halves
+    dlrm_adagrad* ada = nullptr;    // kRuleAdagrad / kRuleRowwise: the state
+    float eps = 0.0f;               // ... and the rule's epsilon
 };
+// who stepped a build's once-hit rows, for the messages
+static const char* const kRuleNames[4] = {"dlrm_step_bwd (Descent)", "dlrm_split_step_bwd (the split rule)",
+                                          "dlrm_adagrad_step_bwd (the element-wise Adagrad rule)",
+                                          "dlrm_adagrad_step_bwd (the row-wise Adagrad rule)"};
 
 static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* indices, int itype,
                          int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
                          const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
                          int64_t dt_ld, float lr, unsigned flags, const PrepArgs* prep,
-                         const StepRule& rule = StepRule{"dlrm_step_bwd", nullptr}) {
+                         const StepRule& rule = StepRule{"dlrm_step_bwd"}) {
     CHECK_ARG(ctx && tb && ix, "%s: null ctx/tables/indexer", rule.fn);
     dlrm_split_sgd* const op = rule.op;
+    dlrm_adagrad* const ada = rule.ada;
     int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, 1);
     if (rc) return rc;
     if (op) {  // (dlrm_split_sgd_update's argument errors)
@@ -1257,6 +1280,9 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
         CHECK_ARG(op->T == tb->T && op->D == tb->D, "%s: the low halves were created for %d tables of dim %d", rule.fn,
                   op->T, op->D);
     }
+    if (ada)  // (dlrm_adagrad_update's)
+        CHECK_ARG(ada->T == tb->T && ada->D == tb->D, "%s: the optimizer state was created for %d tables of dim %d",
+                  rule.fn, ada->T, ada->D);
     const int d = tb->D, F = tb->T + 1;
     const int64_t P = (int64_t)F * (F - 1) / 2;
     CHECK_ARG(padding >= 0 && x_ld >= d && dout_ld >= d + P + padding && dx_ld >= d && dt_ld >= (int64_t)F * d,
@@ -1269,17 +1295,19 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
     if (rc) return rc;
     // the split backward (once-hit rows updated there) where the shape has it; otherwise the
     // gather backward writes every dt row and the apply takes a split indexer's once-hit rows too
-    // (the split rule: its backward loads the low halves as 8-B or 16-B vectors)
+    // (the split rule: its backward loads the low halves as 8-B or 16-B vectors; the element-wise Adagrad rule its
+    // state rows as 16-B vectors; an Adagrad rule: the feature sizes whose backward has its once-hit write)
     const bool split_bwd = ix->split && step_split_supported(tb->aligned16, tb->T, tb->dtype, d, x, x_ld) &&
-                           (!op || op->aligned16);
+                           (!op || op->aligned16) &&
+                           (!ada || ((ada->rowwise || ada->aligned16) && adagrad_step_bwd_supported(ada->rowwise, tb->dtype, tb->T, d)));
     if (flags & DLRM_STEP_APPLY_ONLY) {
         // the apply of a split build only completes a backward that stepped the once-hit rows
         if (split_bwd && !ix->singles_done)
             return ctx_fail(ctx, DLRM_E_STATE, "%s(APPLY_ONLY): no backward has run on this build", rule.fn);
         // ... with this rule: the other one's once-hit rows hold another step
-        if (ix->singles_done && ix->singles_split != (op != nullptr))
+        if (ix->singles_done && ix->singles_rule != rule.kind)
             return ctx_fail(ctx, DLRM_E_STATE, "%s(APPLY_ONLY): this build's once-hit rows were stepped by %s", rule.fn,
-                            ix->singles_split ? "dlrm_split_step_bwd (the split rule)" : "dlrm_step_bwd (Descent)");
+                            kRuleNames[ix->singles_rule]);
         rc = DLRM_OK;
     } else if (split_bwd) {
         // a second backward on one build would step its once-hit rows twice
@@ -1289,12 +1317,17 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
                             "dlrm_step_fwd)", rule.fn);
         CHECK_ARG((uintptr_t)dx % 16 == 0 && (uintptr_t)dt % 16 == 0 && dx_ld % 4 == 0 && dt_ld % 4 == 0,
                   "%s: dx and dt must be 16-B aligned with leading dimensions divisible by 4", rule.fn);
-        rc = launch_step_bwd(ctx, tb->d_desc, tb->T, tb->dtype, indices, itype, table_stride, index_base, d, batch, x,
-                             x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, lr, tb->h_desc.data(),
-                             op ? op->d_ptr : nullptr);
+        if (ada)
+            rc = launch_adagrad_step_bwd(ctx, tb->d_desc, tb->T, tb->dtype, indices, itype, table_stride, index_base, d,
+                                         batch, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, lr, rule.eps,
+                                         ada->rowwise, ada->d_ptr);
+        else
+            rc = launch_step_bwd(ctx, tb->d_desc, tb->T, tb->dtype, indices, itype, table_stride, index_base, d, batch, x,
+                                 x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, lr, tb->h_desc.data(),
+                                 op ? op->d_ptr : nullptr);
         if (rc == DLRM_OK) {
             ix->singles_done = true;
-            ix->singles_split = op != nullptr;
+            ix->singles_rule = rule.kind;
         }
     } else {
         rc = launch_interact_bwd_gather(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
@@ -1308,6 +1341,12 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
     if (op)
         return launch_split_step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_ptr, tb->T, tb->D,
                                        (int64_t)batch, dt, dt_ld, d, lr, sa, prep);
+    if (ada && ada->rowwise)
+        return launch_rowwise_adagrad_step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, ada->d_ptr, tb->T, tb->D,
+                                                 tb->dtype, (int64_t)batch, dt, dt_ld, d, lr, rule.eps, sa, prep);
+    if (ada)
+        return launch_adagrad_step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && ada->aligned16, ada->d_ptr, tb->T,
+                                         tb->D, tb->dtype, (int64_t)batch, dt, dt_ld, d, lr, rule.eps, sa, prep);
     return launch_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, tb->T, tb->D, tb->dtype, 1, (int64_t)batch, dt,
                             DLRM_F32, dt_ld, d, lr, sa, prep);
 }
@@ -1336,7 +1375,9 @@ static int step_bwd_prepare_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* i
     const bool inapply = batch > 0 && tb->T > 0 && batch <= kWaveApplyMaxN && NB <= 2 && tb->aligned16 &&
                          wave_fits(next, batch) &&
                          step_split_supported(tb->aligned16, tb->T, tb->dtype, tb->D, x, x_ld) &&
-                         (!rule.op || rule.op->aligned16);
+                         (!rule.op || rule.op->aligned16) &&
+                         (!rule.ada || ((rule.ada->rowwise || rule.ada->aligned16) &&
+                                        adagrad_step_bwd_supported(rule.ada->rowwise, tb->dtype, tb->T, tb->D)));
     if (!inapply)  // no pipelined form for this shape: the plain step (the next forward builds)
         return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
                              padding, dx, dx_ld, dt, dt_ld, lr, flags, nullptr, rule);
@@ -1365,7 +1406,7 @@ int dlrm_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, cons
                           int64_t dt_ld, float lr, dlrm_indexer* next, const void* next_indices, unsigned flags) {
     return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
                                  padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags,
-                                 StepRule{"dlrm_step_bwd", nullptr});
+                                 StepRule{"dlrm_step_bwd"});
 }
 
 // ---- the same step on split-bf16 tables: the split rule in the backward's once-hit write and in the apply
@@ -1375,7 +1416,7 @@ int dlrm_split_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dlrm
                         int64_t dt_ld, float lr, unsigned flags) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_split_step_bwd: null ctx/tables/optimizer/indexer");
     return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
-                         dx, dx_ld, dt, dt_ld, lr, flags, nullptr, StepRule{"dlrm_split_step_bwd", op});
+                         dx, dx_ld, dt, dt_ld, lr, flags, nullptr, StepRule{"dlrm_split_step_bwd", kRuleSplit, op});
 }
 
 int dlrm_split_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dlrm_indexer* ix,
@@ -1386,7 +1427,33 @@ int dlrm_split_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* 
     CHECK_ARG(ctx && tb && op && ix, "dlrm_split_step_bwd_prepare: null ctx/tables/optimizer/indexer");
     return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
                                  padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags,
-                                 StepRule{"dlrm_split_step_bwd", op});
+                                 StepRule{"dlrm_split_step_bwd", kRuleSplit, op});
+}
+
+// ---- the same step with a sparse Adagrad rule (element-wise or row-wise: the handle's kind) in the backward's
+// once-hit write and in the apply
+static StepRule adagrad_step_rule(dlrm_adagrad* op, float eps) {
+    return StepRule{"dlrm_adagrad_step_bwd", op->rowwise ? kRuleRowwise : kRuleAdagrad, nullptr, op, eps};
+}
+
+int dlrm_adagrad_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, const void* indices,
+                          int itype, int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
+                          const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
+                          int64_t dt_ld, float lr, float eps, unsigned flags) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_adagrad_step_bwd: null ctx/tables/optimizer/indexer");
+    return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
+                         dx, dx_ld, dt, dt_ld, lr, flags, nullptr, adagrad_step_rule(op, eps));
+}
+
+int dlrm_adagrad_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix,
+                                  const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                                  const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding, float* dx,
+                                  int64_t dx_ld, float* dt, int64_t dt_ld, float lr, float eps, dlrm_indexer* next,
+                                  const void* next_indices, unsigned flags) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_adagrad_step_bwd_prepare: null ctx/tables/optimizer/indexer");
+    return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
+                                 padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags,
+                                 adagrad_step_rule(op, eps));
 }
 
 // ---- diagnostics: a native backtrace on a fatal signal (SIGSEGV / SIGBUS / SIGABRT), written to

@@ -1,0 +1,19 @@
+// adagrad_rowwise_step.hip — the apply launch of the training step with the row-wise Adagrad rule (gfx950) when
+// it carries the next batch's split indexer build (dlrm_adagrad_step_bwd_prepare): apply_step.hpp with
+// apply.hpp's RowwiseAdagrad rule.  MODE 0 and 1 stay in adagrad_rowwise.hip.
+#include "apply_step.hpp"
+
+namespace dlrm {
+
+int launch_rowwise_adagrad_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16,
+                                      float* const* state, int T_, int D, int tdtype, int64_t N, const float* dt,
+                                      int64_t dt_ld, int64_t dt_offset, float lr, float eps, const SinglesArgs& sa,
+                                      const PrepArgs* pa) {
+    return launch_step_apply_rule(ctx, ix, tabs, aligned16, T_, D, tdtype, N, dt, dt_ld, dt_offset,
+                                  RowwiseAdagrad{lr, eps, state}, sa, pa, [&](const SinglesArgs& s1) {
+                                      return launch_rowwise_adagrad_apply(ctx, ix, tabs, aligned16, state, T_, D, tdtype, 1, N,
+                                                                          dt, DLRM_F32, dt_ld, dt_offset, lr, eps, s1);
+                                  });
+}
+
+}  // namespace dlrm

@@ -192,7 +192,9 @@ struct Adagrad {
     float* const* state;  // [T] device pointers, fp32 [nrows][D]
     typedef float State;
     static constexpr int kState = 1;
-    static constexpr bool kCarriesBuild = false;
+    // MODE >= 2 over the training step's fp32 dt, in a unit of its own (adagrad_step.hip:
+    // launch_adagrad_step_apply), so adagrad.hip stays the MODE 0 / 1 unit it was
+    static constexpr bool kCarriesBuild = true;
     static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = true;
     __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }
@@ -219,7 +221,8 @@ struct RowwiseAdagrad {
     float* const* state;  // [T] device pointers, fp32 [nrows]
     typedef float State;
     static constexpr int kState = 2;
-    static constexpr bool kCarriesBuild = false;
+    // (MODE >= 2: adagrad_rowwise_step.hip, launch_rowwise_adagrad_step_apply)
+    static constexpr bool kCarriesBuild = true;
     static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = true;
     __device__ __forceinline__ float* base(int t) const { return ldg<float*>(state + t); }

@@ -1,7 +1,8 @@
 // apply_kernel.hpp -- the apply launch of update! (sgd_apply_kernel over apply.hpp's work items), its
 // any-D fallback kernels and their launchers, by update rule.  update.hip instantiates Descent
 // (every MODE), adagrad.hip and adagrad_rowwise.hip the Adagrad rules, split_sgd.hip the split rule (MODE 0
-// and 1) and split_step.hip its build-carrying launches (MODE 2 / 3 / 5): they compile side by side.
+// and 1), and split_step.hip, adagrad_step.hip and adagrad_rowwise_step.hip those three rules' build-carrying
+// launches (MODE 2 / 3 / 5): they compile side by side.
 #pragma once
 #include "apply.hpp"
 
@@ -45,15 +46,14 @@ static inline int wave_big_kind(const PrepArgs& pa) {
 // workgroups of a build (4 parts each)
 __host__ __device__ __forceinline__ int prep_groups(const PrepArgs& pa) { return (pa.T << pa.ix.vshift) / kWaveParts; }
 
-// R: the update rule (apply.hpp: Descent, Adagrad, RowwiseAdagrad, SplitDescent -- the Adagrad rules in MODE 0
-// and 1 only).
+// R: the update rule (apply.hpp: Descent, Adagrad, RowwiseAdagrad, SplitDescent).
 template <typename TT, typename GT, int VPR, int MODE, typename R = Descent>
 __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev ix, TableDesc* __restrict__ tabs, int T_,
                                                                   int L, const GT* __restrict__ grad, int64_t grad_ld,
                                                                   int64_t grad_offset, R rule,
                                                                   const unsigned* __restrict__ err, SinglesArgs sa,
                                                                   PrepArgs pa) {
-    static_assert(R::kCarriesBuild || MODE <= 1, "the next batch's build rides on Descent and SplitDescent launches only");
+    static_assert(R::kCarriesBuild || MODE <= 1, "the next batch's build rides on the launches of a rule that carries it");
     constexpr bool SG = MODE == 1;
     int bid = blockIdx.x, nblk = gridDim.x;
     if constexpr (MODE >= 2) {

@@ -1,9 +1,16 @@
 // bwd_split_body.inc -- the body of interact_bwd_split_kernel and interact_bwd_split_lo_kernel (interact.hip,
 // where the load plan is described), included inside each kernel's braces.  In scope: T, NB, DC, SPB, WPS,
 // MAPPED, CPL, YS, the kernel's arguments, and SU = the type of `su` (StepUpdate: Descent's once-hit write;
-// SplitStepUpdate: the split rule's, whose branches are `if constexpr (SU::kSplit)`).
+// SplitStepUpdate: the split rule's, whose branches are `if constexpr (SU::kSplit)`; AdagradStepUpdate: the
+// Adagrad rules', whose branches are `if constexpr (AG == 1)`, the element-wise rule, and `(AG == 2)`, the
+// row-wise one).
     static_assert(CPL == 4 || (CPL == 8 && sizeof(T) == 2), "8 columns per lane: bf16 rows");
     static_assert(!SU::kSplit || (sizeof(T) == 2 && !YS && !MAPPED), "split rows live in bf16 tables");
+    constexpr int AG = step_adagrad_kind((const SU*)nullptr);
+    static_assert(AG == 0 || (!YS && !MAPPED), "the Adagrad rules step the training step's tables");
+    // the row-wise sum of squares crosses the sample's two waves once: one super-block per wave, so the block
+    // barrier of that exchange sits in uniform control flow
+    static_assert(AG != 2 || WPS == 1 || DC == 128, "row-wise over two waves: d = 128");
     constexpr int NS = 16 * NB;
     constexpr int KS = 4 * NB;
     constexpr int PMAX = NS * (NS - 1) / 2;
@@ -56,6 +63,17 @@
             mylo = (long long)ldg<uint16_t*>(step_lo(su) + (tl ? lane : 0));
         }
     }
+    // Adagrad: the tables' state pointers travel the same two ways
+    long long myst = 0;
+    float** sop = nullptr;
+    if constexpr (AG != 0) {
+        if constexpr (LO_LDS) {
+            sop = state_tab<NS>();
+            myst = (long long)ldg<float*>(step_state(su) + (tdl_ok ? threadIdx.x : 0));
+        } else {
+            myst = (long long)ldg<float*>(step_state(su) + (tl ? lane : 0));
+        }
+    }
     constexpr int PPW = (PMAX + 64 * WPS - 1) / (64 * WPS);  // packed values staged per lane
     float pv[PPW];
 #pragma unroll
@@ -84,6 +102,7 @@
     if (tdl_ok) {
         tds[threadIdx.x] = tdl;
         if constexpr (SU::kSplit && LO_LDS) lop[threadIdx.x] = (uint16_t*)mylo;
+        if constexpr (AG != 0 && LO_LDS) sop[threadIdx.x] = (float*)myst;
         if constexpr (MAPPED) {
             dmap[threadIdx.x] = dm0;
             dmap[F - 1 + threadIdx.x] = dm1;
@@ -225,7 +244,21 @@
                     ulo[I][r] = (uint16_t*)__shfl(mylo, (f >= 1 && f < F) ? f - 1 : 0, 64);
                 }
         }
-        if (!live || !colok) continue;
+        float* ust[NB][4];
+        if constexpr (AG == 1 && !LO_LDS) {
+#pragma unroll
+            for (int I = 0; I < NB; ++I)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int f = I * 16 + 4 * q + r;
+                    ust[I][r] = (float*)__shfl(myst, (f >= 1 && f < F) ? f - 1 : 0, 64);
+                }
+        }
+        // (row-wise: its shuffles and its block barrier need uniform control flow, so padding samples and lanes
+        // past the row come along into the loop and leave it per tile row, after the row sums)
+        if constexpr (AG != 2) {
+            if (!live || !colok) continue;
+        }
 #pragma unroll
         for (int I = 0; I < NB; ++I) {
             // split: the low halves of this lane's once-hit rows among the four of tile row I (its CPL columns),
@@ -245,6 +278,101 @@
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (I * 16 + 4 * q + r < F && urow[I][r] != ~0u) lov[r] = load_halves<CPL>(lo_row(r));
+            }
+            // Adagrad: the state of this lane's once-hit rows, loaded here as the low halves are (after the
+            // MFMAs, the four of a tile row together) -- the element-wise rule's fp32 state row at the lane's
+            // columns (8 columns per lane: each at its write), the row-wise rule's word
+            // (with up to 16 features the state is loaded at each row's write instead: four in flight took the
+            // NB = 1 forms below Descent's 8 waves per SIMD)
+            constexpr bool ST4 = NB > 1 && CPL == 4;
+            float* usr[4];  // the four tables' state pointers (by shuffle)
+            if constexpr (AG == 1 && !LO_LDS) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) usr[r] = ust[I][r];
+            }
+            // row-wise: the four tile rows' sums of squares of G = 0 + g, in the order of the apply's once-hit item
+            // (apply.hpp run_singles, fp32 gradient rows: apply lane v holds columns 4v..4v+3) -- a lane's fma
+            // chain from 0 over four columns in column order, then the xor butterfly over the row's lanes from
+            // distance 1 up.  Lane c holds apply lane 16h + c's columns (8 columns per lane: lanes 2c and 2c + 1,
+            // so its two chains' sum is level 1 and the butterfly over c levels 2..16); a lane past the row
+            // (!colok: its accumulators are 0) adds +0, which keeps the bits of a sum >= 0.  d = 128 over two
+            // waves: each wave's 64 columns over c, then the last level, one commutative add of the two waves'
+            // totals, through LDS (a slot per tile row I: one barrier each, nothing is overwritten).
+            // The state word m of a row is one address for both waves, and wave 0 stores m' there: so only wave 0
+            // ever loads it (its c == 0 lanes, before the barrier) and hands it to both waves through the same LDS
+            // exchange.  Wave 1 never reads a word that wave 0 writes.
+            float rs[4];
+            float mx[4];  // two waves: the rows' state words, out of LDS
+            if constexpr (AG == 2) {
+                float m0w[4];
+                if constexpr (WPS == 2) {
+                    if (h == 0 && c == 0 && live) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int f = I * 16 + 4 * q + r;
+                            if (f < F && urow[I][r] != ~0u) m0w[r] = ldg<float>(sop[f - 1] + urow[I][r]);
+                        }
+                    }
+                }
+                if constexpr (!LO_LDS) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int f = I * 16 + 4 * q + r;
+                        usr[r] = (float*)__shfl(myst, (f >= 1 && f < F) ? f - 1 : 0, 64);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float g[CPL];
+#pragma unroll
+                    for (int e = 0; e < CPL; ++e) g[e] = 0.0f + acc[I][e][r];
+                    float ss = sum_squares<4>(g, 0.0f);
+                    if constexpr (CPL == 8) ss += sum_squares<4>(g + 4, 0.0f);
+#pragma unroll
+                    for (int o = 1; o < 16; o <<= 1) ss += __shfl_xor(ss, o, 64);
+                    rs[r] = ss;
+                }
+                if constexpr (WPS == 2) {
+                    float* sx = row_ss_tab<SPB * 3 * NS>();  // [SPB][wave 0's sums, wave 1's sums, m][NS]
+                    if (c == 0) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) sx[(pair * 3 + h) * NS + I * 16 + 4 * q + r] = rs[r];
+                        if (h == 0 && live) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const int f = I * 16 + 4 * q + r;
+                                if (f < F && urow[I][r] != ~0u) sx[(pair * 3 + 2) * NS + f] = m0w[r];
+                            }
+                        }
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        rs[r] += sx[(pair * 3 + (h ^ 1)) * NS + I * 16 + 4 * q + r];
+                        mx[r] = sx[(pair * 3 + 2) * NS + I * 16 + 4 * q + r];
+                    }
+                }
+                if (!live || !colok) continue;
+            }
+            auto st_base = [&](int r) {
+                const int f = I * 16 + 4 * q + r;
+                float* base;
+                if constexpr (LO_LDS) base = sop[f - 1];
+                else base = usr[r];
+                return base;
+            };
+            f32x4_t sv[AG == 1 && ST4 ? 4 : 1];
+            float mv[AG == 2 && ST4 && WPS == 1 ? 4 : 1];
+            if constexpr (AG == 1 && ST4) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (I * 16 + 4 * q + r < F && urow[I][r] != ~0u)
+                        sv[r] = ldg<f32x4_t>(st_base(r) + (int64_t)urow[I][r] * d + n0);
+            }
+            if constexpr (AG == 2 && ST4 && WPS == 1) {  // (one wave holds the row: its own loads, then its store)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (I * 16 + 4 * q + r < F && urow[I][r] != ~0u) mv[r] = ldg<float>(st_base(r) + urow[I][r]);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -275,6 +403,38 @@
                             for (int e = 0; e < CPL; ++e) hb[e] = __float_as_uint(tw[e]);
                             if constexpr (CPL == 8) lov[r] = load_halves<CPL>(lo_row(r));
                             split_once_hit<CPL>(su.lr, v, hb, lov[r], (uint16_t*)tds[f - 1].data + ro, lo_row(r));
+                        } else if constexpr (AG == 1) {
+                            // A += G^2, w -= lr G / (sqrt(A) + eps) with G = 0 + g: apply.hpp's adagrad_step
+                            float* srow = st_base(r) + (int64_t)urow[I][r] * d + n0;
+                            float gg[CPL], av[CPL];
+#pragma unroll
+                            for (int e = 0; e < CPL; e += 4) {
+                                f32x4_t a4;
+                                if constexpr (ST4) a4 = sv[r];
+                                else a4 = ldg<f32x4_t>(srow + e);
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    av[e + k] = a4[k];
+                                    gg[e + k] = 0.0f + v[e + k];
+                                }
+                            }
+                            adagrad_step<CPL>(su.lr, step_eps(su), gg, av, tw);
+#pragma unroll
+                            for (int e = 0; e < CPL; e += 4)
+                                stg_nt<f32x4_t>(srow + e, f32x4_t{av[e], av[e + 1], av[e + 2], av[e + 3]});
+                            store_row<T, CPL, true>((T*)tds[f - 1].data + (int64_t)urow[I][r] * d, n0, tw);
+                        } else if constexpr (AG == 2) {
+                            // m += ss / D, w -= (lr / (sqrt(m) + eps)) G: apply.hpp's helpers, one lane stores m
+                            float m0;
+                            if constexpr (WPS == 2) m0 = mx[r];
+                            else if constexpr (ST4) m0 = mv[r];
+                            else m0 = ldg<float>(st_base(r) + urow[I][r]);
+                            const float m = rowwise_m(m0, rs[r], d);
+                            const float sc = rowwise_scale(su.lr, step_eps(su), m);
+#pragma unroll
+                            for (int e = 0; e < CPL; ++e) wv[e] = __builtin_fmaf(-sc, 0.0f + v[e], tw[e]);
+                            store_row<T, CPL, true>((T*)tds[f - 1].data + (int64_t)urow[I][r] * d, n0, wv);
+                            if (c == 0 && h == 0) stg<float>(st_base(r) + urow[I][r], m);
                         } else {
 #pragma unroll
                         for (int e = 0; e < CPL; ++e) wv[e] = __builtin_fmaf(-su.lr, 0.0f + v[e], tw[e]);

@@ -449,6 +449,23 @@ int launch_split_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs,
 int launch_split_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint16_t* const* lo,
                             int T, int D, int64_t N, const float* dt, int64_t dt_ld, int64_t dt_offset, float lr,
                             const SinglesArgs& singles, const PrepArgs* prep);
+// the training step with a sparse Adagrad rule (dlrm_adagrad_step_bwd): whether the step backward has the rule's
+// once-hit write for this feature size (interact.hip), that backward, and the rule's apply over the fp32 dt
+// (adagrad_step.hip / adagrad_rowwise_step.hip): with `prep` and no once-hit items the next batch's build rides
+// on the launch where the shape's MODE 2 / 3 / 5 kernel exists, otherwise the rule's own apply and, with
+// `prep`, the build's own launch.
+bool adagrad_step_bwd_supported(bool rowwise, int dtype, int T, int d);
+int launch_adagrad_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T, int dtype, const void* idx, int itype,
+                            int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
+                            int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
+                            float lr, float eps, bool rowwise, float* const* state);
+int launch_adagrad_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16,
+                              float* const* state, int T, int D, int tdtype, int64_t N, const float* dt, int64_t dt_ld,
+                              int64_t dt_offset, float lr, float eps, const SinglesArgs& singles, const PrepArgs* prep);
+int launch_rowwise_adagrad_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16,
+                                      float* const* state, int T, int D, int tdtype, int64_t N, const float* dt,
+                                      int64_t dt_ld, int64_t dt_offset, float lr, float eps,
+                                      const SinglesArgs& singles, const PrepArgs* prep);
 int launch_triangular_slice(dlrm_ctx* ctx, int dtype, int sz, int B, const void* z, int64_t z_bs, void* out,
                             int64_t out_ld);
 int launch_triangular_slice_back(dlrm_ctx* ctx, int dtype, int sz, int B, const void* dy, int64_t dy_ld, void* a,

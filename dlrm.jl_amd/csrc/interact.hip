@@ -361,6 +361,35 @@ template <int N> __device__ __forceinline__ uint16_t** lo_tab() {
     return t;
 }
 
+// The same for the sparse Adagrad rules (apply.hpp Adagrad / RowwiseAdagrad; dlrm_adagrad_step_bwd): a once-hit
+// row's fp32 state (RW: one word per row, else a row of d) is loaded after the MFMAs, stepped with the apply's
+// own helpers on G = 0 + g, and written with the row.  A struct of its own again.
+template <bool RW>
+struct AdagradStepUpdate : StepUpdate {
+    float* const* state;    // [T] device pointers, fp32 [nrows][d] or (RW) [nrows]
+    float eps;
+};
+
+// (the shared text's rule of an argument struct: 0 Descent or split, 1 element-wise Adagrad, 2 row-wise)
+constexpr int step_adagrad_kind(const StepUpdate*) { return 0; }
+constexpr int step_adagrad_kind(const AdagradStepUpdate<false>*) { return 1; }
+constexpr int step_adagrad_kind(const AdagradStepUpdate<true>*) { return 2; }
+__device__ __forceinline__ float* const* step_state(const StepUpdate&) { return nullptr; }
+template <bool RW> __device__ __forceinline__ float* const* step_state(const AdagradStepUpdate<RW>& su) { return su.state; }
+__device__ __forceinline__ float step_eps(const StepUpdate&) { return 0.0f; }
+template <bool RW> __device__ __forceinline__ float step_eps(const AdagradStepUpdate<RW>& su) { return su.eps; }
+
+// the d = 128 Adagrad kernels' per-table state pointers in LDS, and the row-wise two-wave form's exchange of
+// each wave's sums of squares (function-local arrays again)
+template <int N> __device__ __forceinline__ float** state_tab() {
+    __shared__ float* t[N];
+    return t;
+}
+template <int N> __device__ __forceinline__ float* row_ss_tab() {
+    __shared__ float t[N];
+    return t;
+}
+
 // N once-hit elements of a split row: hb = the gathered high halves as fp32 bits (bf16 << 16), lv the low
 // halves, g the gradient; w = fmaf(-lr, 0 + g, w) on the merged weight (split_step1: the apply's singles
 // arithmetic, NaN quiet-bit rule included), both halves stored.
@@ -718,6 +747,19 @@ __global__ __launch_bounds__(256, 2) void interact_bwd_update_lo_kernel(
     extern __shared__ __attribute__((aligned(16))) float smem[];
     bwd_body<uint16_t, NB, true, true, 1, 0, SplitStepUpdate>(blockIdx.x, gridDim.x, smem, d, F, B, dout, dout_ld, nullptr, 0,
                                                               dx, dx_ld, dt, dt_ld, ga, x, x_ld, su);
+}
+
+// The training step's backward with a sparse Adagrad rule (dlrm_adagrad_step_bwd): the same kernel with the
+// rule's once-hit write (RW: row-wise), fp32 and bf16 tables, in the step's default geometries, NB = 1 and 2.
+// Other shapes take the gather backward and the rule's apply with once-hit items.
+template <typename T, int NB, int DC, int SPB, int WPS, int CPL, bool RW>
+__global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : 4) void interact_bwd_split_ag_kernel(
+    int d_, int F, int B, const T* __restrict__ dout, int64_t dout_ld, float* __restrict__ dx, int64_t dx_ld,
+    float* __restrict__ dt, int64_t dt_ld, GatherArgs ga, const T* __restrict__ x, int64_t x_ld,
+    AdagradStepUpdate<RW> su) {
+    typedef AdagradStepUpdate<RW> SU;
+    constexpr bool MAPPED = false, YS = false;
+#include "bwd_split_body.inc"
 }
 
 // ------------------------------------------------------------------ scalar fallbacks
@@ -1255,6 +1297,78 @@ int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, con
     }
 #undef DLRM_LAUNCH_BWDUP
     return ctx_hip(ctx, hipGetLastError(), "step_bwd launch");
+}
+
+// (The Adagrad step's launchers come last in this unit: its kernels are then instantiated, and emitted into the
+// code object, after every other kernel, whose offsets in it stay what they were.)
+// Shapes whose step backward has an Adagrad form (among step_split_supported's): d = 128 and d <= 64, the forms
+// of interact_bwd_split_kernel.  The row-wise rule also needs the vector apply's summation order to exist for
+// the shape (fp32 dt rows of d / 4 vectors, d / 4 a power of two: apply_kernel.hpp dispatch_apply); the any-D
+// kernels sum a row's squares in column order, which no lane layout here reproduces.  Any other d (the
+// interact_bwd_update_kernel shapes) and the DLRM_BWD_NOSPLIT override take the gather backward.
+// Forms that would run below Descent's occupancy are not instantiated either: with up to 16
+// features (NB = 1) Descent's forms hold 8 waves per SIMD at 56..59 VGPRs, and the row-wise forms need 77..87, the
+// element-wise one-wave form on fp32 tables 66.
+constexpr bool adagrad_form(bool rowwise, bool f32, int NB, int WPS) {
+    return rowwise ? NB == 2 : !(NB == 1 && WPS == 1 && f32);
+}
+bool adagrad_step_bwd_supported(bool rowwise, int dtype, int T_, int d) {
+    if (knobs().bwd_nosplit || !(d == 128 || d <= 64)) return false;
+    if (rowwise && !(d >= 8 && (d & (d - 1)) == 0)) return false;
+    return adagrad_form(rowwise, dtype == DLRM_F32, (T_ + 1 + 15) / 16, d == 128 ? 2 : 1);
+}
+
+// Training-step backward with a sparse Adagrad rule (state = the device array of state pointers; the
+// element-wise rule's rows 16-B aligned): the default geometries only, as launch_step_bwd_lo.
+template <typename T, bool RW>
+static int launch_step_bwd_ag(dlrm_ctx* ctx, const GatherArgs& ga, int F, int d, int B, const T* x, int64_t x_ld,
+                              const T* dout, int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
+                              const AdagradStepUpdate<RW>& su) {
+    const int NB = (F + 15) / 16;
+    hipStream_t s = ctx_stream(ctx);
+    // (a form adagrad_form leaves out is not instantiated: the caller asked adagrad_step_bwd_supported)
+#define DLRM_LAUNCH_AG(N_, DC_, S_, W_, C_)                                                                        \
+    if constexpr (adagrad_form(RW, sizeof(T) == 4, N_, W_))                                                        \
+        hipLaunchKernelGGL((interact_bwd_split_ag_kernel<T, N_, DC_, S_, W_, C_, RW>),                              \
+                           dim3((unsigned)((B + S_ - 1) / S_)), dim3(64 * W_ * S_), 0, s, d, F, B, dout, dout_ld,   \
+                           dx, dx_ld, dt, dt_ld, ga, x, x_ld, su);                                                  \
+    else                                                                                                           \
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "adagrad_step_bwd: no kernel for this shape")
+    if (d == 128) {
+        if constexpr (sizeof(T) == 2) {
+            // 8 columns per lane (bf16, B > 2048), one wave per sample, 2 samples per block: with 17..32 features,
+            // as the split rule (with up to 16 the two-wave form)
+            if (B > 2048 && NB == 2) {
+                DLRM_LAUNCH_AG(2, 128, 2, 1, 8);
+                return ctx_hip(ctx, hipGetLastError(), "adagrad_step_bwd(8 columns per lane) launch");
+            }
+        }
+        if (NB == 1) { DLRM_LAUNCH_AG(1, 128, 4, 2, 4); } else { DLRM_LAUNCH_AG(2, 128, 4, 2, 4); }
+        return ctx_hip(ctx, hipGetLastError(), "adagrad_step_bwd(split) launch");
+    }
+    // d <= 64: one wave per sample, 8 samples per block
+    if (NB == 1) { DLRM_LAUNCH_AG(1, 0, 8, 1, 4); } else { DLRM_LAUNCH_AG(2, 0, 8, 1, 4); }
+#undef DLRM_LAUNCH_AG
+    return ctx_hip(ctx, hipGetLastError(), "adagrad_step_bwd(one wave per sample) launch");
+}
+
+int launch_adagrad_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, const void* idx, int itype,
+                            int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
+                            int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
+                            float lr, float eps, bool rowwise, float* const* state) {
+    if (B == 0 || T_ == 0) return DLRM_OK;
+    const int F = T_ + 1;
+    GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
+    const StepUpdate su{ix.single, ix.cap, lr, ctx_error_word(ctx)};
+#define DLRM_AG(TY, RW_)                                                                                           \
+    return launch_step_bwd_ag<TY, RW_>(ctx, ga, F, d, B, (const TY*)x, x_ld, (const TY*)dout, dout_ld, dx, dx_ld, dt, \
+                                       dt_ld, AdagradStepUpdate<RW_>{su, state, eps})
+    if (dtype == DLRM_F32) {
+        if (rowwise) DLRM_AG(float, true); else DLRM_AG(float, false);
+    } else {
+        if (rowwise) DLRM_AG(uint16_t, true); else DLRM_AG(uint16_t, false);
+    }
+#undef DLRM_AG
 }
 
 }  // namespace dlrm

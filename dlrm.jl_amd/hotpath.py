@@ -36,6 +36,12 @@ dlrm_split_sgd_update(PREBUILT) -- three launches, no host synchronisation, grap
 the backward from the gathered rows and their low halves, only the repeated rows' dt rows are written, and
 `pipeline` "apply" / "side" work as they do for Descent.  Both halves of every row end up bit for bit what
 the operator path gives.  Opt-in: without the keyword `opt=SplitDescent` keeps the operator path.
+
+`adagrad_step=True` with `opt=ADAGrad(η, ε)` or `opt=RowwiseADAGrad(η, ε)`, fp32 or bfloat16 tables: the fused
+step pair with that rule (dlrm_step_fwd, then dlrm_adagrad_step_bwd / dlrm_adagrad_step_bwd_prepare): once-hit
+rows and their state are stepped inside the backward, only the repeated rows' dt rows are written, and
+`pipeline` "apply" / "side" work as they do for Descent.  Tables and state end up bit for bit what the
+operator path gives.  Opt-in again: without the keyword the Adagrad rules keep the operator path.
 """
 import torch
 
@@ -44,13 +50,13 @@ from .embedding import EmbeddingTableSet, PackedIndices
 from .interact import interaction_sizes
 from .runtime import dtype_code, ptr, require_device
 from .shapes import APPLY_MAX_N
-from .update import SparseIndexer, SplitDescent, _StatefulOpt
+from .update import SparseIndexer, SplitDescent, _AdagradBase, _StatefulOpt
 
 
 class HotPath:
     def __init__(self, tables, batch, lookups=1, *, lr=0.1, index_base=0, deterministic=True,
                  overlap_indexer=None, pad_to=1, fused=True, materialize_ys=None, pipeline=False, chunk=None,
-                 parts=None, opt=None, fused_step=False):
+                 parts=None, opt=None, fused_step=False, adagrad_step=False):
         if opt is not None and not isinstance(opt, _StatefulOpt):
             raise TypeError("HotPath: opt is an ADAGrad, RowwiseADAGrad or SplitDescent (None: Descent(lr))")
         if opt is not None and not deterministic:
@@ -64,6 +70,13 @@ class HotPath:
                              "Descent(lr) is fused without it, the Adagrad rules have no fused step")
         if self.split_step and self.ts.dtype != torch.bfloat16:
             raise ValueError(f"HotPath: fused_step=True needs bfloat16 tables (the high halves), not {self.ts.dtype}")
+        # the fused step pair with an Adagrad rule (dlrm_adagrad_step_bwd); a keyword of its own
+        self.adagrad_step = bool(adagrad_step)
+        self.rule_params = None
+        if self.adagrad_step and not isinstance(opt, _AdagradBase):
+            raise ValueError("HotPath: adagrad_step=True is the Adagrad rules' fused step (opt=ADAGrad(eta, eps) or "
+                             "opt=RowwiseADAGrad(eta, eps)); the split rule's is fused_step=True, Descent(lr) is fused "
+                             "without a keyword")
         self.B, self.L = int(batch), int(lookups)
         self.T, self.D = len(self.ts), self.ts.D
         self.d = self.D  # dense vector length == feature size (model.jl:220)
@@ -108,9 +121,13 @@ class HotPath:
         # the training-step pair (dlrm_step_fwd / dlrm_step_bwd): indexer built inside the forward's
         # launch, once-hit rows updated inside the backward's, the rest by the apply launch
         self.step_api = ((not self.materialize_ys) and self.indexer is not None and not self.overlap_indexer and
-                         (opt is None or self.split_step))  # (dlrm_step_bwd: Descent; dlrm_split_step_bwd: the split rule)
+                         (opt is None or self.split_step or self.adagrad_step))  # (dlrm_step_bwd: Descent;
+        # dlrm_split_step_bwd: the split rule; dlrm_adagrad_step_bwd: the Adagrad rules)
         if self.split_step and not self.step_api:
             raise ValueError("HotPath: fused_step=True needs the step kernels (one-hot lookups, ys not materialized, "
+                             "no side-stream indexer)")
+        if self.adagrad_step and not self.step_api:
+            raise ValueError("HotPath: adagrad_step=True needs the step kernels (one-hot lookups, ys not materialized, "
                              "no side-stream indexer)")
         # pipelined steps: the NEXT batch's split indexer is built during this step, so the
         # step's forward launch only gathers; two indexers alternate.
@@ -123,9 +140,10 @@ class HotPath:
         if mode not in (None, "side", "apply"):
             raise ValueError(f"pipeline must be None, 'side' or 'apply', not {pipeline!r}")
         if opt is not None:
-            if mode is not None and not self.split_step:
+            if mode is not None and not (self.split_step or self.adagrad_step):
                 raise ValueError("HotPath: the pipelined steps need the fused step (pipeline must be None with opt, "
-                                 "unless opt=SplitDescent with fused_step=True)")
+                                 "unless opt=SplitDescent with fused_step=True or an Adagrad rule with "
+                                 "adagrad_step=True)")
             opt.handle_of(self.ts)  # the state, allocated before any graph capture
         # (pooled bags: "side" only -- the next batch's build beside this step's apply, `step_next`)
         self.pipeline = mode if (mode and ((self.step_api and self.L == 1) or (mode == "side" and self.L > 1))) else None
@@ -221,21 +239,30 @@ class HotPath:
     def step_bwd(self, dout, x=None, idx=None, flags=0, prepare=None):
         """dlrm_step_bwd: dot_back + update!(Descent(lr)) with the indexer of step_fwd
         (flags: _lib.STEP_BWD_ONLY / STEP_APPLY_ONLY run one of its two launches).  fused_step:
-        dlrm_split_step_bwd, the same with the split rule and the optimizer's eta."""
+        dlrm_split_step_bwd, the same with the split rule and the optimizer's eta; adagrad_step:
+        dlrm_adagrad_step_bwd, with the optimizer's rule, eta and eps."""
         h = self.ctx.bind()
         x = self._fwd_x if x is None else x
         idx = self._fwd_idx if idx is None else idx
-        if self.split_step:
+        if self.split_step or self.adagrad_step:
             args = (h, self.ts.handle, self.opt.handle_of(self.ts), self.indexer.handle, ptr(idx.data), idx.itype,
                     idx.stride, self.index_base, self.B, ptr(x), x.stride(0), ptr(dout), dout.stride(0), self.padding,
                     ptr(self.dx), self.dx.stride(0), ptr(self.dt), self.dt.stride(0), self.opt.eta)
+            if self.adagrad_step:
+                # (rule_params: the (eta, eps) an owner fixed for both launches of a step, HipTables' deferred
+                # apply among them; None: the optimizer's own, read at the call)
+                eta, eps = self.rule_params or (self.opt.eta, self.opt.eps)
+                args = args[:-1] + (eta, eps)
+                one, two = self.lib.dlrm_adagrad_step_bwd, self.lib.dlrm_adagrad_step_bwd_prepare
+            else:
+                one, two = self.lib.dlrm_split_step_bwd, self.lib.dlrm_split_step_bwd_prepare
             if prepare is not None:
                 nix, nidx = prepare
                 if (nidx.itype, nidx.stride, nidx.B, nidx.L) != (idx.itype, idx.stride, idx.B, idx.L):
                     raise ValueError("the next batch's indices must have this batch's layout")
-                self._check(self.lib.dlrm_split_step_bwd_prepare(*args, nix.handle, ptr(nidx.data), flags))
+                self._check(two(*args, nix.handle, ptr(nidx.data), flags))
             else:
-                self._check(self.lib.dlrm_split_step_bwd(*args, flags))
+                self._check(one(*args, flags))
             return
         if prepare is not None:  # (next indexer, next indices): built by this step's apply launch
             nix, nidx = prepare

@@ -17,7 +17,8 @@
 #
 # (`Context(0; fused = true, lr = η)` runs that chain on the fused training-step kernels;
 # `Context(0; fused = true, split = HipSplitDescent(η))` does so on split-bf16 tables, through
-# dlrm_split_step_bwd / dlrm_split_step_bwd_prepare.)
+# dlrm_split_step_bwd / dlrm_split_step_bwd_prepare; `Context(0; fused = true, adagrad = HipADAGrad(η, ϵ))` or
+# `adagrad = HipRowwiseADAGrad(η, ϵ)` with that Adagrad rule, through dlrm_adagrad_step_bwd / _prepare.)
 #
 # and `_Train.train!` / `DLRMModel` stay unchanged.  Dense inputs x (bottom-MLP output) and the
 # interaction output cross PCIe here because the MLPs stay on the CPU in the reference; the
@@ -57,15 +58,25 @@ mutable struct Context
     # split (fused): a HipSplitDescent -- the split analogue of lr on 2-byte tables: the pullback runs the
     # split rule's backward (dlrm_split_step_bwd) and update! with that same optimizer its apply
     split::Any
+    # adagrad (fused): a HipADAGrad or HipRowwiseADAGrad likewise (dlrm_adagrad_step_bwd): the pullback steps
+    # the once-hit rows and their state with that rule, update! with that same optimizer runs or defers its apply
+    adagrad::Any
+    eps::Union{Nothing,Float32}   # ... and its ϵ as given here: the pullback's and a deferred apply's alike
     function Context(device::Integer; stream::Ptr{Cvoid} = C_NULL, fused::Bool = false, lr = nothing,
-                     defer_update::Bool = true, split = nothing)
+                     defer_update::Bool = true, split = nothing, adagrad = nothing)
         out = Ref{Ptr{Cvoid}}(C_NULL)
         rc = ccall((:dlrm_ctx_create, libdlrm), Cint, (Cint, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), device, stream, out)
         rc == 0 || throw(DLRMError(rc, "dlrm_ctx_create"))
         split === nothing || lr === nothing || Float32(lr) == split.eta ||
             throw(ArgumentError("Context: lr = $lr beside split = HipSplitDescent($(split.eta))"))
         split === nothing || (lr = split.eta)
-        ctx = new(out[], fused, lr === nothing ? nothing : Float32(lr), defer_update, split)
+        adagrad === nothing || split === nothing ||
+            throw(ArgumentError("Context: one rule steps the tables, split = or adagrad ="))
+        adagrad === nothing || lr === nothing || Float32(lr) == adagrad.eta ||
+            throw(ArgumentError("Context: lr = $lr beside adagrad = $(nameof(typeof(adagrad)))($(adagrad.eta), …)"))
+        adagrad === nothing || (lr = adagrad.eta)
+        ctx = new(out[], fused, lr === nothing ? nothing : Float32(lr), defer_update, split, adagrad,
+                  adagrad === nothing ? nothing : Float32(adagrad.epsilon))
         finalizer(c -> ccall((:dlrm_ctx_destroy, libdlrm), Cint, (Ptr{Cvoid},), c.ptr), ctx)
         return ctx
     end
@@ -531,7 +542,8 @@ function _rule_update(opt::HipSplitDescent, ctx, tables, ixptr, flags, idxptr, s
 end
 
 # The training step's backward / apply launches of a fused step `st` (dlrm_step_bwd and _prepare), or, on a
-# context built with `split = HipSplitDescent(η)`, the split rule's (dlrm_split_step_bwd and _prepare).
+# context built with `split = HipSplitDescent(η)`, the split rule's (dlrm_split_step_bwd and _prepare), or, with
+# `adagrad = HipADAGrad(η, ϵ) | HipRowwiseADAGrad(η, ϵ)`, that rule's (dlrm_adagrad_step_bwd and _prepare).
 function _step_bwd(ctx, st, delta_ld, flags)
     d, B = size(st.x)
     if ctx.split !== nothing
@@ -542,6 +554,15 @@ function _step_bwd(ctx, st, delta_ld, flags)
                      ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
                      st.x.ptr, d, st.delta.ptr, delta_ld, st.padding, st.dx.ptr, d, st.dt.ptr,
                      size(st.dt, 1), ctx.lr, flags)
+    end
+    if ctx.adagrad !== nothing
+        _, h = adagrad_state(ctx.adagrad, st.tables)
+        return ccall((:dlrm_adagrad_step_bwd, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid}, Int64,
+                      Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cfloat, Cuint),
+                     ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
+                     st.x.ptr, d, st.delta.ptr, delta_ld, st.padding, st.dx.ptr, d, st.dt.ptr,
+                     size(st.dt, 1), ctx.lr, ctx.eps, flags)
     end
     ccall((:dlrm_step_bwd, libdlrm), Cint,
           (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid}, Int64,
@@ -561,6 +582,16 @@ function _step_bwd_prepare(ctx, st, nix, next, flags)
                      ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
                      st.x.ptr, d, st.delta.ptr, size(st.delta, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
                      size(st.dt, 1), ctx.lr, nix.ptr, next.data.ptr, flags)
+    end
+    if ctx.adagrad !== nothing
+        _, h = adagrad_state(ctx.adagrad, st.tables)
+        return ccall((:dlrm_adagrad_step_bwd_prepare, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid},
+                      Int64, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cfloat,
+                      Ptr{Cvoid}, Ptr{Cvoid}, Cuint),
+                     ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
+                     st.x.ptr, d, st.delta.ptr, size(st.delta, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
+                     size(st.dt, 1), ctx.lr, ctx.eps, nix.ptr, next.data.ptr, flags)
     end
     ccall((:dlrm_step_bwd_prepare, libdlrm), Cint,
           (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid},
@@ -869,7 +900,13 @@ function _fused_update!(opt, st, tables)
     ctx.split === nothing || opt === ctx.split ||
         throw(ArgumentError("this context steps its tables with its HipSplitDescent (the pullback ran its backward); " *
                             "update! got $(nameof(typeof(opt)))"))
-    if opt isa Union{AbstractHipADAGrad,HipSplitDescent} && ctx.split === nothing
+    ctx.adagrad === nothing || opt === ctx.adagrad ||
+        throw(ArgumentError("this context steps its tables with its $(nameof(typeof(ctx.adagrad))) (the pullback ran " *
+                            "its backward); update! got $(nameof(typeof(opt)))"))
+    ctx.adagrad === nothing || (opt.eta == ctx.lr && opt.epsilon == ctx.eps) ||
+        throw(ArgumentError("the pullback stepped the once-hit rows with η = $(ctx.lr), ϵ = $(ctx.eps); update! got " *
+                            "$(opt.eta), $(opt.epsilon)"))
+    if opt isa Union{AbstractHipADAGrad,HipSplitDescent} && ctx.split === nothing && ctx.adagrad === nothing
         # every dt row is needed: the forward's split indexer, the once-hit rows as singles items
         st.bwd === :once_hit_applied &&
             throw(ArgumentError("the pullback already stepped the once-hit rows with Descent (η = $(ctx.lr)) and left " *

@@ -23,6 +23,8 @@ DLRMHip.jl's lazy `maplookup` for `HipEmbedding`):
 
 `HipTables(tables, opt=SplitDescent(η))` on bfloat16 tables is the same chain with the split rule: the
 pullback is dlrm_split_step_bwd(DLRM_STEP_BWD_ONLY), update! with that optimizer its APPLY_ONLY launch.
+`HipTables(tables, opt=ADAGrad(η, ε))` or `opt=RowwiseADAGrad(η, ε)` is the same chain with that Adagrad rule
+(dlrm_adagrad_step_bwd).
 
 Three launches per step, bit for bit the result of `HotPath.step` and of the five-launch chain.
 
@@ -45,7 +47,7 @@ import torch
 
 from . import _lib
 from .embedding import EmbeddingTableSet, PackedIndices, PreallocationStrategy, as_table_set
-from .update import Descent, SparseEmbeddingUpdate, SplitDescent, _StatefulOpt
+from .update import Descent, SparseEmbeddingUpdate, SplitDescent, _AdagradBase, _StatefulOpt
 
 
 class HipTables:
@@ -57,17 +59,21 @@ class HipTables:
     runs it at once and synchronises to check bounds, as the reference's update! returns with the
     tables written.  opt: a SplitDescent(η) on bfloat16 tables, the split analogue of lr=η: the pullback
     runs the split rule's backward (dlrm_split_step_bwd) and update! with that same optimizer object runs
-    or defers its apply."""
+    or defers its apply.  opt: an ADAGrad(η, ε) or RowwiseADAGrad(η, ε) likewise (dlrm_adagrad_step_bwd): update!
+    takes that optimizer object, with the η and ε it had here."""
 
     def __init__(self, tables, *, lr=None, index_base=1, defer_update=True, opt=None):
         self._ts = as_table_set(tables) if not isinstance(tables, EmbeddingTableSet) else tables
         if opt is not None:
-            if not isinstance(opt, SplitDescent):
-                raise TypeError("HipTables: opt is a SplitDescent (Descent: lr=eta)")
+            if not isinstance(opt, (SplitDescent, _AdagradBase)):
+                raise TypeError("HipTables: opt is a SplitDescent, an ADAGrad or a RowwiseADAGrad (Descent: lr=eta)")
             if lr is not None and float(lr) != opt.eta:
                 raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}")
             lr = opt.eta
         self.opt = opt
+        # an Adagrad rule's (η, ε) as given here: every launch of these tables' steps uses them (the pullback's
+        # and a deferred apply's alike), and update! refuses the optimizer object once its own differ
+        self._opt_params = (opt.eta, opt.eps) if isinstance(opt, _AdagradBase) else None
         self.lr = None if lr is None else float(lr)
         self.index_base = int(index_base)  # 1: Julia's, as maplookup / update_ default to
         self.defer_update = bool(defer_update)
@@ -142,7 +148,9 @@ class HipTables:
         hp = self._hp.get(batch)
         if hp is None:
             hp = HotPath(self._ts, batch, 1, lr=0.0 if self.lr is None else self.lr, index_base=self.index_base,
-                         opt=self.opt, fused_step=self.opt is not None)
+                         opt=self.opt, fused_step=isinstance(self.opt, SplitDescent),
+                         adagrad_step=isinstance(self.opt, _AdagradBase))
+            hp.rule_params = self._opt_params
             if not hp.step_api:
                 raise ValueError("HipTables: this table set has no training-step kernels (deterministic, one-hot)")
             self._hp[batch] = hp
@@ -270,6 +278,9 @@ def update_lazy(opt, tables, grads, *, check_bounds=None):
     hp = lz.hp
     if tables.opt is not None and opt is not tables.opt:
         raise ValueError(f"these HipTables step with {tables.opt!r} (the pullback ran its backward); update! got {opt!r}")
+    if isinstance(tables.opt, _AdagradBase) and tables._opt_params != (opt.eta, opt.eps):
+        raise ValueError(f"these HipTables were built with {type(opt).__name__} parameters {tables._opt_params} (the "
+                         f"pullback stepped the once-hit rows with them); update! got {opt!r}")
     tables.flush()
     if isinstance(opt, _StatefulOpt) and tables.opt is None:
         # every dt row is needed: the forward's split indexer, the once-hit rows as singles items

@@ -293,9 +293,11 @@ int dlrm_indexer_set_parts(dlrm_ctx* ctx, dlrm_indexer* indexer, int parts);
  * split backward (dlrm_step_bwd or dlrm_split_step_bwd) has stepped this build's once-hit rows, so
  * its dt holds only the repeated rows' gradients; SINGLES_SPLIT, set with it: that backward was
  * dlrm_split_step_bwd's (the split rule on split-bf16 tables), so only the split rule's apply may
- * complete it.  (The Julia shim's pullback state, DLRMHip.jl `st.bwd`.) */
+ * complete it; SINGLES_ADAGRAD / SINGLES_ROWWISE, set with it: that backward was
+ * dlrm_adagrad_step_bwd's with an element-wise / a row-wise handle, and only an Adagrad apply with a
+ * handle of that kind may complete it.  (The Julia shim's pullback state, DLRMHip.jl `st.bwd`.) */
 enum { DLRM_IX_BUILT = 1, DLRM_IX_SPLIT = 2, DLRM_IX_PREPARED = 4, DLRM_IX_SINGLES_DONE = 8,
-       DLRM_IX_SINGLES_SPLIT = 16 };
+       DLRM_IX_SINGLES_SPLIT = 16, DLRM_IX_SINGLES_ADAGRAD = 32, DLRM_IX_SINGLES_ROWWISE = 64 };
 int dlrm_indexer_state(const dlrm_indexer* indexer, unsigned* state);
 
 /* Backward of a training step without a materialized ys (see above). */
@@ -357,7 +359,9 @@ int dlrm_sgd_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_indexer* indexer, u
  * dlrm_adagrad_update: DLRM_UPDATE_PREBUILT is honoured; DLRM_UPDATE_ATOMIC returns
  * DLRM_E_UNSUPPORTED (an atomic add cannot square a sum it never holds).  An indexer in state
  * DLRM_IX_SINGLES_DONE returns DLRM_E_STATE: a split backward has already stepped the once-hit
- * rows with Descent and its dt lacks their rows.  A split indexer whose singles are not done is
+ * rows with Descent and its dt lacks their rows -- unless DLRM_IX_SINGLES_ADAGRAD or
+ * DLRM_IX_SINGLES_ROWWISE says that dlrm_adagrad_step_bwd stepped them with a handle of this
+ * handle's kind: then the repeated rows that are left are applied.  A split indexer whose singles are not done is
  * taken whole, once-hit rows included.  Launches neither allocate nor synchronise beyond what
  * dlrm_sgd_update does (partial rows for dim > 256 on first use), so the call is graph-capturable.
  * dlrm_adagrad_destroy of NULL returns 0. */
@@ -497,6 +501,45 @@ int dlrm_split_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_split_s
                                 const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
                                 float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr,
                                 dlrm_indexer* next_indexer, const void* next_indices, unsigned flags);
+
+/* ---- the training step with sparse Adagrad (see "sparse Adagrad" above): dlrm_step_bwd and
+ * dlrm_step_bwd_prepare with the element-wise or the row-wise rule in place of Descent (the kind is
+ * the handle's), after the same forward.
+ *   dlrm_adagrad_step_bwd = dlrm_interact_bwd_gather + dlrm_adagrad_update(opt, PREBUILT): dx, the
+ *   tables and the state end up bit-identical to that pair's.  A once-hit row is stepped inside the
+ *   backward from its gathered elements and its state with G = 0 + g (element-wise: A += G^2,
+ *   w -= lr G / (sqrt(A) + eps); row-wise: the row's sum of squares in the apply's own order -- a
+ *   lane's four columns in column order, then an xor butterfly over the row's lanes --
+ *   m += ss / dim, w -= lr G / (sqrt(m) + eps)); its dt row is never written.  The apply launch
+ *   steps the repeated rows from their dt rows with the same rule.
+ * Arguments, flags, alignment rules and argument errors are dlrm_step_bwd's and
+ * dlrm_adagrad_update's.  A shape without a split backward (F > 32, x or rows not 16-B aligned),
+ * element-wise state pointers that are not 16-B aligned, and a feature size whose backward has no
+ * Adagrad form (dim other than 128 and not <= 64; row-wise: also any dim that is not a power of
+ * two >= 8, where the apply itself sums a row's squares in column order) run
+ * dlrm_interact_bwd_gather and let the rule's apply take the once-hit rows.  So do the shapes
+ * whose backward form would run below dlrm_step_bwd's occupancy and is not built: the row-wise
+ * rule with up to 16 features (every dim), and the element-wise rule on DLRM_F32 tables with up to
+ * 16 features and dim <= 64.  dlrm_adagrad_step_bwd_prepare on a shape without an in-apply
+ * build, every one of these fallback shapes included, runs the plain step (the next dlrm_step_fwd
+ * then builds its indexer).  A set
+ * bounds flag leaves tables and state unwritten.
+ * Only the same rule completes a backward: every other pairing of dlrm_step_bwd,
+ * dlrm_split_step_bwd and dlrm_adagrad_step_bwd (element-wise / row-wise handle) with another's
+ * (APPLY_ONLY), or with another rule's dlrm_*_update(PREBUILT), returns DLRM_E_STATE and launches
+ * nothing.  dlrm_adagrad_update(PREBUILT) with a handle of the same kind after
+ * dlrm_adagrad_step_bwd(BWD_ONLY) applies the repeated rows. */
+int dlrm_adagrad_step_bwd(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagrad* opt, dlrm_indexer* indexer,
+                          const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                          const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
+                          float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr, float eps,
+                          unsigned flags);
+int dlrm_adagrad_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagrad* opt,
+                                  dlrm_indexer* indexer,
+                                  const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                                  const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
+                                  float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr, float eps,
+                                  dlrm_indexer* next_indexer, const void* next_indices, unsigned flags);
 
 /* ---- table-sharded exchange over RCCL ------------------------------------
  * DLRM.jl is one process: maplookup hands its output straight to the interaction (model.jl:161-163).
