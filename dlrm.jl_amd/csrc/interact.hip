@@ -24,6 +24,7 @@
 // The interaction's arithmetic intensity (~11-24 flop/B) is far below the MFMA ridge, so
 // these kernels are HBM-bound; MFMA just keeps the VALU free and the operand traffic low.
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 
 #include "common.hpp"
@@ -339,7 +340,13 @@ struct StepUpdate {
     int64_t cap;
     float lr;
     const unsigned* err;    // the ctx's bounds flag: set -> no table row is written (the row goes to dt)
+    // What differs between the rules is theirs: the kind (kSplit; kAdagrad 1: element-wise, 2: row-wise), and for a
+    // rule whose rows have a second stream (low halves, Adagrad state) that stream's element type State and the
+    // tables' pointers to it, a member `state`; kName heads the launch errors.
     static constexpr bool kSplit = false;
+    static constexpr int kAdagrad = 0;
+    typedef void State;
+    static constexpr const char* kName = "step_bwd";
 };
 // The same for split-bf16 tables (apply.hpp SplitDescent; dlrm_split_step_bwd): the table holds the high
 // halves of fp32 master weights, lo[t] their low halves.  A once-hit row's master weight is merged from
@@ -347,19 +354,11 @@ struct StepUpdate {
 // its low half, stepped in fp32 and written back as two halves.  A struct of its own, so the Descent
 // kernels keep their arguments.
 struct SplitStepUpdate : StepUpdate {
-    uint16_t* const* lo;    // [T] device pointers, uint16 [nrows][d]
+    uint16_t* const* state;  // [T] device pointers to the low halves, uint16 [nrows][d]
     static constexpr bool kSplit = true;
+    typedef uint16_t State;
+    static constexpr const char* kName = "split_step_bwd";
 };
-
-// (the kernels' shared text names the low halves of either argument struct)
-__device__ __forceinline__ uint16_t* const* step_lo(const StepUpdate&) { return nullptr; }
-__device__ __forceinline__ uint16_t* const* step_lo(const SplitStepUpdate& su) { return su.lo; }
-
-// the d = 128 split kernels' per-table low-half pointers in LDS (a function-local array: only their instantiations hold it)
-template <int N> __device__ __forceinline__ uint16_t** lo_tab() {
-    __shared__ uint16_t* t[N];
-    return t;
-}
 
 // The same for the sparse Adagrad rules (apply.hpp Adagrad / RowwiseAdagrad; dlrm_adagrad_step_bwd): a once-hit
 // row's fp32 state (RW: one word per row, else a row of d) is loaded after the MFMAs, stepped with the apply's
@@ -368,23 +367,22 @@ template <bool RW>
 struct AdagradStepUpdate : StepUpdate {
     float* const* state;    // [T] device pointers, fp32 [nrows][d] or (RW) [nrows]
     float eps;
+    static constexpr int kAdagrad = RW ? 2 : 1;
+    typedef float State;
+    static constexpr const char* kName = "adagrad_step_bwd";
 };
 
-// (the shared text's rule of an argument struct: 0 Descent or split, 1 element-wise Adagrad, 2 row-wise)
-constexpr int step_adagrad_kind(const StepUpdate*) { return 0; }
-constexpr int step_adagrad_kind(const AdagradStepUpdate<false>*) { return 1; }
-constexpr int step_adagrad_kind(const AdagradStepUpdate<true>*) { return 2; }
-__device__ __forceinline__ float* const* step_state(const StepUpdate&) { return nullptr; }
-template <bool RW> __device__ __forceinline__ float* const* step_state(const AdagradStepUpdate<RW>& su) { return su.state; }
-__device__ __forceinline__ float step_eps(const StepUpdate&) { return 0.0f; }
-template <bool RW> __device__ __forceinline__ float step_eps(const AdagradStepUpdate<RW>& su) { return su.eps; }
-
-// the d = 128 Adagrad kernels' per-table state pointers in LDS, and the row-wise two-wave form's exchange of
-// each wave's sums of squares (function-local arrays again)
-template <int N> __device__ __forceinline__ float** state_tab() {
-    __shared__ float* t[N];
+// the d = 128 rule kernels' per-table pointers to the second stream in LDS, and the row-wise two-wave form's
+// exchange of each wave's sums of squares (function-local arrays: only their instantiations hold them)
+template <typename E, int N> __device__ __forceinline__ E** rule_tab() {
+    __shared__ E* t[N];
     return t;
 }
+// interact_bwd_split_kernel reads a rule's pointer array through this call by reference, not as su.state in its own
+// text: read there, every rule kernel kept its instruction count and resource figures, but one scalar `and` of each
+// had its operands the other way round and the 8-column forms ordered a few instructions differently
+// (DESIGN.md section 16).
+template <typename SU> __device__ __forceinline__ typename SU::State* const* rule_state(const SU& su) { return su.state; }
 template <int N> __device__ __forceinline__ float* row_ss_tab() {
     __shared__ float t[N];
     return t;
@@ -424,11 +422,12 @@ __device__ __forceinline__ void bwd_body(int bid, int nblocks, float* smem, int 
     // used instead of held in registers across the index loads
     TableDesc* tds = (TableDesc*)(smem + G::WPB * G::template lds_floats<UPD>());
     int64_t* dmap = (int64_t*)(tds + (F - 1));  // GATHER + ga.dtb: [2][F-1] row bases / strides of dt
-    uint16_t** lop = (uint16_t**)(tds + (F - 1));  // the split step (no dtb): [F-1] low-half pointers
+    typedef typename SU::State SE;
+    SE** sop = (SE**)(tds + (F - 1));  // the split step (no dtb): [F-1] low-half pointers
     if (GATHER) {
         for (int t = threadIdx.x; t < F - 1; t += blockDim.x) {
             tds[t] = load_table(ga.tabs, t);
-            if constexpr (SU::kSplit) lop[t] = ldg<uint16_t*>(su.lo + t);
+            if constexpr (SU::kSplit) sop[t] = ldg<SE*>(su.state + t);
             if (ga.dtb) {
                 dmap[t] = ga.dtb[t];
                 dmap[F - 1 + t] = ga.dtl[t];
@@ -605,8 +604,8 @@ __device__ __forceinline__ void bwd_body(int bid, int nblocks, float* smem, int 
                                         const float g4[4] = {v[0], v[1], v[2], v[3]};
                                         const uint32_t hb[4] = {__float_as_uint(tw[0]), __float_as_uint(tw[1]),
                                                                 __float_as_uint(tw[2]), __float_as_uint(tw[3])};
-                                        split_once_hit<4>(su.lr, g4, hb, load_halves<4>(lop[f - 1] + ro),
-                                                          (uint16_t*)tds[f - 1].data + ro, lop[f - 1] + ro);
+                                        split_once_hit<4>(su.lr, g4, hb, load_halves<4>(sop[f - 1] + ro),
+                                                          (uint16_t*)tds[f - 1].data + ro, sop[f - 1] + ro);
                                     } else {
                                     float wv[4];
 #pragma unroll
@@ -666,16 +665,16 @@ __global__ __launch_bounds__(256, 3) void interact_bwd_index_kernel(int d, int F
 
 // The backward of a training step after interact_fwd_index_kernel: re-gathers T, writes dx
 // and the dt rows of positions whose row is hit more than once, and applies the SGD step to
-// once-hit rows itself (the apply launch that follows handles the rest).
-template <typename T, int NB, int SBU, int DC = 0>
+// once-hit rows itself (the apply launch that follows handles the rest).  SU: Descent's rule or the split rule's.
+template <typename T, int NB, int SBU, int DC = 0, typename SU = StepUpdate>
 __global__ __launch_bounds__(256, 2) void interact_bwd_update_kernel(int d, int F, int B, const T* __restrict__ dout,
                                                                   int64_t dout_ld, float* __restrict__ dx,
                                                                   int64_t dx_ld, float* __restrict__ dt, int64_t dt_ld,
                                                                   GatherArgs ga, const T* __restrict__ x, int64_t x_ld,
-                                                                  StepUpdate su) {
+                                                                  SU su) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    bwd_body<T, NB, true, true, SBU, DC>(blockIdx.x, gridDim.x, smem, d, F, B, dout, dout_ld, nullptr, 0, dx, dx_ld,
-                                         dt, dt_ld, ga, x, x_ld, su);
+    bwd_body<T, NB, true, true, SBU, DC, SU>(blockIdx.x, gridDim.x, smem, d, F, B, dout, dout_ld, nullptr, 0, dx, dx_ld,
+                                             dt, dt_ld, ga, x, x_ld, su);
 }
 
 // The training step's backward with each sample split over TWO waves by column halves (wave h
@@ -712,54 +711,462 @@ __global__ __launch_bounds__(256, 2) void interact_bwd_update_kernel(int d, int 
 // x + b * x_ld + kk * d (x / x_ld carry ys / ys_ld), no index, flag or once-hit update; every dt row
 // is written.  Up to 96 features (NB <= 6): the gather-free backward of the pooled workload
 // (F = 65), one wave per 64-column super-block.
-// (SU: the once-hit rule's arguments, StepUpdate or SplitStepUpdate.  The body is text shared by the two
-// kernels below, bwd_split_body.inc: as an inlined function template it no longer compiled to the same code.)
-template <typename T, int NB, int DC, int SPB, int WPS = 2, bool MAPPED = false, int CPL = 4, bool YS = false>
-__global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) void interact_bwd_split_kernel(int d_, int F, int B, const T* __restrict__ dout,
-                                                                   int64_t dout_ld, float* __restrict__ dx,
-                                                                   int64_t dx_ld, float* __restrict__ dt,
-                                                                   int64_t dt_ld, GatherArgs ga,
-                                                                   const T* __restrict__ x, int64_t x_ld,
-                                                                   StepUpdate su) {
-    typedef StepUpdate SU;
-#include "bwd_split_body.inc"
-}
-
-// The training step's backward on split-bf16 tables (dlrm_split_step_bwd): the same kernel with the split
-// rule's once-hit write, in the step's three default geometries (d = 128: two waves per sample, or 8
-// columns per lane for B > 2048 and more than 16 features; d <= 64: one wave per sample), NB = 1 and 2.
-template <int NB, int DC, int SPB, int WPS, int CPL>
-__global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : 4) void interact_bwd_split_lo_kernel(
-    int d_, int F, int B, const uint16_t* __restrict__ dout, int64_t dout_ld, float* __restrict__ dx, int64_t dx_ld,
-    float* __restrict__ dt, int64_t dt_ld, GatherArgs ga, const uint16_t* __restrict__ x, int64_t x_ld,
-    SplitStepUpdate su) {
-    typedef uint16_t T;
-    typedef SplitStepUpdate SU;
-    constexpr bool MAPPED = false, YS = false;
-#include "bwd_split_body.inc"
-}
-// ... and interact_bwd_update_kernel's (any other d with F <= 32)
-template <int NB>
-__global__ __launch_bounds__(256, 2) void interact_bwd_update_lo_kernel(
-    int d, int F, int B, const uint16_t* __restrict__ dout, int64_t dout_ld, float* __restrict__ dx, int64_t dx_ld,
-    float* __restrict__ dt, int64_t dt_ld, GatherArgs ga, const uint16_t* __restrict__ x, int64_t x_ld,
-    SplitStepUpdate su) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    bwd_body<uint16_t, NB, true, true, 1, 0, SplitStepUpdate>(blockIdx.x, gridDim.x, smem, d, F, B, dout, dout_ld, nullptr, 0,
-                                                              dx, dx_ld, dt, dt_ld, ga, x, x_ld, su);
-}
-
-// The training step's backward with a sparse Adagrad rule (dlrm_adagrad_step_bwd): the same kernel with the
-// rule's once-hit write (RW: row-wise), fp32 and bf16 tables, in the step's default geometries, NB = 1 and 2.
-// Other shapes take the gather backward and the rule's apply with once-hit items.
-template <typename T, int NB, int DC, int SPB, int WPS, int CPL, bool RW>
-__global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : 4) void interact_bwd_split_ag_kernel(
+// SU: the once-hit rule and its arguments.  StepUpdate is Descent's write.  SplitStepUpdate (dlrm_split_step_bwd) is
+// the split rule's on bf16 tables, its branches `if constexpr (SU::kSplit)`; AdagradStepUpdate (dlrm_adagrad_step_bwd)
+// the sparse Adagrad rules' on fp32 and bf16 tables, `if constexpr (AG == 1)` the element-wise rule and `(AG == 2)`
+// the row-wise one.  The rules other than Descent exist in the step's default geometries only, NB = 1 and 2
+// (step_bwd_form below).  (The body stays the kernel's own text: as an inlined function template it no longer
+// compiled to the same code.)
+template <typename T, int NB, int DC, int SPB, int WPS = 2, bool MAPPED = false, int CPL = 4, bool YS = false,
+          typename SU = StepUpdate>
+__global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) void interact_bwd_split_kernel(
     int d_, int F, int B, const T* __restrict__ dout, int64_t dout_ld, float* __restrict__ dx, int64_t dx_ld,
-    float* __restrict__ dt, int64_t dt_ld, GatherArgs ga, const T* __restrict__ x, int64_t x_ld,
-    AdagradStepUpdate<RW> su) {
-    typedef AdagradStepUpdate<RW> SU;
-    constexpr bool MAPPED = false, YS = false;
-#include "bwd_split_body.inc"
+    float* __restrict__ dt, int64_t dt_ld, GatherArgs ga, const T* __restrict__ x, int64_t x_ld, SU su) {
+    static_assert(CPL == 4 || (CPL == 8 && sizeof(T) == 2), "8 columns per lane: bf16 rows");
+    static_assert(!SU::kSplit || (sizeof(T) == 2 && !YS && !MAPPED), "split rows live in bf16 tables");
+    constexpr int AG = SU::kAdagrad;
+    constexpr bool RULE = SU::kSplit || AG != 0;  // a rule whose rows have a second stream
+    typedef typename SU::State SE;
+    static_assert(AG == 0 || (!YS && !MAPPED), "the Adagrad rules step the training step's tables");
+    // the row-wise sum of squares crosses the sample's two waves once: one super-block per wave, so the block
+    // barrier of that exchange sits in uniform control flow
+    static_assert(AG != 2 || WPS == 1 || DC == 128, "row-wise over two waves: d = 128");
+    constexpr int NS = 16 * NB;
+    constexpr int KS = 4 * NB;
+    constexpr int PMAX = NS * (NS - 1) / 2;
+    constexpr int SBC = 16 * CPL;  // columns per super-block
+    // the wave's tile of T: fp32 (CPL = 4) or the rows' own bf16 (CPL = 8)
+    typedef typename std::conditional<CPL == 8, uint16_t, float>::type TileT;
+    const int d = DC > 0 ? DC : d_;
+    __shared__ float pk_all[SPB][PMAX];  // each sample's packed gradient row
+    // each wave's tile of T (the once-hit update reads it; YS has none)
+    __shared__ __attribute__((aligned(16))) TileT tt_all[YS ? 1 : WPS * SPB][YS ? 4 : NS * SBC];
+    __shared__ TableDesc tds[YS ? 1 : NS];
+    __shared__ int64_t dmap[MAPPED ? 2 * NS : 1];  // table t's dt rows at dt + dmap[t] + b * dmap[F - 1 + t]
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int pair = w / WPS, h = w % WPS;
+    constexpr bool mapped = MAPPED;
+    const int c = lane & 15, q = lane >> 4;
+    const int64_t b = (int64_t)blockIdx.x * SPB + pair;
+    const bool live = b < B;
+    const int64_t bb = live ? b : 0;  // a padding sample reads sample 0 (and stores nothing)
+    const int ksteps = (F + 3) / 4;
+    const int P = F * (F - 1) / 2;
+    const T* ob = dout + bb * dout_ld;
+    float* pk = pk_all[pair];
+    TileT* Tt = tt_all[YS ? 0 : w];
+    if (h == 0) WT(1, 0, b);
+    // the table descriptors (F - 1 <= NS <= 32 < blockDim: one per thread), held in registers and
+    // written to LDS after the other independent loads are issued, so no wave waits for them alone
+    const bool tdl_ok = !YS && (int)threadIdx.x < F - 1;
+    const TableDesc tdl = YS ? TableDesc{nullptr, 0} : load_table(ga.tabs, tdl_ok ? (int)threadIdx.x : 0);
+    int64_t dm0 = 0, dm1 = 0;
+    if constexpr (MAPPED) {
+        dm0 = ldg<int64_t>(ga.dtb + (tdl_ok ? threadIdx.x : 0));
+        dm1 = ldg<int64_t>(ga.dtl + (tdl_ok ? threadIdx.x : 0));
+    }
+    // ---- every independent load first: table `lane`'s index and flag, the packed gradients, x part
+    const bool tl = !YS && lane < F - 1;
+    const int64_t myidx = YS ? 0 : load_index_if(tl, ga.idx, ga.itype, (int64_t)(tl ? lane : 0) * ga.tstride + bb);
+    // su.single NULL (dlrm_interact_bwd_blocked, YS): no once-hit update, every table row goes to dt
+    const uint8_t myfl = su.single ? ldg<uint8_t>(su.single + (tl ? (int64_t)lane * su.cap + bb : 0)) : (uint8_t)0;
+    // split, Adagrad: the tables' pointers to the low halves / the state reach the writing lanes through LDS, beside
+    // tds (d = 128: the forms with 256 B of LDS to spare at their occupancy), else as the rows do, by shuffle
+    // from lane t
+    constexpr bool ST_LDS = DC == 128;
+    long long myst = 0;
+    SE** sop = nullptr;
+    if constexpr (RULE) {
+        if constexpr (ST_LDS) {
+            sop = rule_tab<SE, NS>();
+            myst = (long long)ldg<SE*>(rule_state(su) + (tdl_ok ? threadIdx.x : 0));
+        } else {
+            myst = (long long)ldg<SE*>(rule_state(su) + (tl ? lane : 0));
+        }
+    }
+    constexpr int PPW = (PMAX + 64 * WPS - 1) / (64 * WPS);  // packed values staged per lane
+    float pv[PPW];
+#pragma unroll
+    for (int k = 0; k < PPW; ++k) {
+        const int p = h * 64 + lane + 64 * WPS * k;
+        const float v = to_f32(ldg<T>(ob + d + (p < P ? p : 0)));
+        pv[k] = p < P ? v : 0.0f;
+    }
+    // super-blocks per wave (CPL = 4, WPS = 2: d <= 512 when not fixed; WPS = 1: d <= 64;
+    // CPL = 8: d <= 128, one wave)
+    // (DC = 0: WPS = 1 / 2 cover d <= 64 / 512; YS: d = 64 * WPS, one super-block per wave)
+    constexpr int SBW = YS ? 1
+                           : DC > 0 ? ((DC / SBC + WPS - 1) / WPS > 0 ? (DC / SBC + WPS - 1) / WPS : 1)
+                                    : (WPS == 2 ? 4 : 1);
+    constexpr int XV = SBC / 64;  // dout x-part values per lane and super-block
+    float xv[SBW][XV];
+#pragma unroll
+    for (int sbi = 0; sbi < SBW; ++sbi)
+#pragma unroll
+        for (int k = 0; k < XV; ++k) {
+            const int n = SBC * h + SBC * WPS * sbi + 64 * k + lane;
+            xv[sbi][k] = to_f32(ldg<T>(ob + (n < d ? n : 0)));
+        }
+    const bool frozen = su.single ? *su.err != 0 : true;  // a bounds error this step: no table row is written
+    if (su.single && blockIdx.x == 0 && threadIdx.x == 0) snapshot_error(su.err, frozen ? 1u : 0u);
+    if (tdl_ok) {
+        tds[threadIdx.x] = tdl;
+        if constexpr (RULE && ST_LDS) sop[threadIdx.x] = (SE*)myst;
+        if constexpr (MAPPED) {
+            dmap[threadIdx.x] = dm0;
+            dmap[F - 1 + threadIdx.x] = dm1;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PPW; ++k) {
+        const int p = h * 64 + lane + 64 * WPS * k;
+        if (p < PMAX) pk[p] = pv[k];
+    }
+    __syncthreads();  // tds, pk
+    // validate this lane's table index; rows travel as 32-bit (~0u = invalid / no table)
+    uint32_t myrow = ~0u;
+    if (tl) {
+        const int64_t r = myidx - ga.base;
+        if (r >= 0 && r < tds[lane].nrows) myrow = (uint32_t)r;
+        else if (h == 0 && live) raise_index_error(ga.err);
+    }
+    const T* rowp[KS];
+    unsigned livek = 0;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        const int kk = 4 * s + q;
+        const uint32_t r = (uint32_t)__shfl((int)myrow, kk >= 1 ? kk - 1 : 0, 64);
+        const bool tab = s < ksteps && kk >= 1 && kk < F && r != ~0u;
+        const T* src = YS ? ((s < ksteps && kk < F) ? x + bb * x_ld + (int64_t)kk * d : nullptr)
+                   : (s < ksteps && kk == 0) ? x + bb * x_ld
+                                             : (tab ? (const T*)tds[kk - 1].data + (int64_t)r * d : nullptr);
+        livek |= src ? (1u << s) : 0u;
+        // (CPL = 8: a masked row reads the zero row -- a 16-B aligned source whatever dout's layout)
+        rowp[s] = src ? src : (CPL == 8 ? (const T*)g_zero_row : ob);
+    }
+    uint32_t urow[NB][4];
+#pragma unroll
+    for (int I = 0; I < NB; ++I)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int f = I * 16 + 4 * q + r;
+            const int src = (f >= 1 && f < F) ? f - 1 : 0;
+            const uint32_t row = (uint32_t)__shfl((int)myrow, src, 64);
+            const int fl = __shfl((int)myfl, src, 64);
+            urow[I][r] = (f >= 1 && f < F && !frozen && fl != 0) ? row : ~0u;
+        }
+    if (h == 0) WT(1, 1, b);
+#pragma unroll
+    for (int sbi = 0; sbi < SBW; ++sbi) {
+        const int sb = SBC * h + SBC * WPS * sbi;
+        if (sb >= d) break;
+        const int n0 = sb + CPL * c;  // this lane's CPL output columns
+        const bool colok = n0 < d;
+        const int nc = colok ? n0 : 0;
+        f32x4_t acc[NB][CPL];
+#pragma unroll
+        for (int I = 0; I < NB; ++I)
+#pragma unroll
+            for (int e = 0; e < CPL; ++e) acc[I][e] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        if constexpr (CPL == 4) {
+            f32x4_t bv[KS];
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const f32x4_t v = load4_f32(rowp[s] + nc);
+                bv[s] = ((livek >> s) & 1u) && colok ? v : f32x4_t{0.f, 0.f, 0.f, 0.f};
+            }
+            if (sbi > 0) wave_lds_sync();  // the previous super-block's tile reads are done
+#pragma unroll
+            for (int s = 0; s < KS; ++s)
+                if (s < ksteps) *(f32x4_t*)(Tt + (4 * s + q) * SBC + 4 * c) = bv[s];
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                if (s < ksteps) {
+                    const int kk = 4 * s + q;
+#pragma unroll
+                    for (int I = 0; I < NB; ++I) {
+                        // S[16I+c][kk]: the symmetric zero-diagonal unpack of the pair row
+                        const int i = I * 16 + c;
+                        const int hi = i > kk ? i : kk, lo = i > kk ? kk : i;
+                        const float av = (i != kk && hi < F) ? pk[hi * (hi - 1) / 2 + lo] : 0.0f;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            acc[I][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[s][e], acc[I][e], 0, 0, 0);
+                    }
+                }
+            }
+        } else {
+            typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+            u32x4_t bv[KS];  // 8 bf16 columns of row 4s+q, packed
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const u32x4_t v = ldg<u32x4_t>(rowp[s] + nc);
+                bv[s] = ((livek >> s) & 1u) && colok ? v : u32x4_t{0u, 0u, 0u, 0u};
+            }
+            if (sbi > 0) wave_lds_sync();  // the previous super-block's tile reads are done
+#pragma unroll
+            for (int s = 0; s < KS; ++s)
+                if (s < ksteps) *(u32x4_t*)(Tt + (4 * s + q) * SBC + 8 * c) = bv[s];
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                if (s < ksteps) {
+                    const int kk = 4 * s + q;
+#pragma unroll
+                    for (int I = 0; I < NB; ++I) {
+                        const int i = I * 16 + c;
+                        const int hi = i > kk ? i : kk, lo = i > kk ? kk : i;
+                        const float av = (i != kk && hi < F) ? pk[hi * (hi - 1) / 2 + lo] : 0.0f;
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            const uint32_t wd = bv[s][e >> 1];
+                            const float bvf = __uint_as_float((e & 1) ? (wd & 0xffff0000u) : (wd << 16));
+                            acc[I][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bvf, acc[I][e], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+        if (h == 0 && sbi == 0) WT(1, 2, b);
+        // dout's x part for this lane's columns (lanes 0..15 hold output row 0)
+        float xo[CPL];
+#pragma unroll
+        for (int e = 0; e < CPL; ++e) {
+            const int n = CPL * c + e;  // column within the super-block: lane n & 63 of xv[sbi][n >> 6]
+            float xs = __shfl(xv[sbi][0], n & 63, 64);
+#pragma unroll
+            for (int k = 1; k < XV; ++k) {
+                const float t = __shfl(xv[sbi][k], n & 63, 64);
+                xs = (n >> 6) == k ? t : xs;
+            }
+            xo[e] = xs;
+        }
+        wave_lds_sync();  // the tile of T (written before the MFMAs)
+        // split, element-wise Adagrad: pointers by shuffle here, in uniform control flow and after the MFMAs (held
+        // through them, with the gathered rows in flight, they cost the one-wave form registers it does not have
+        // at 32 features)
+        SE* ust[NB][4];
+        if constexpr ((SU::kSplit || AG == 1) && !ST_LDS) {
+#pragma unroll
+            for (int I = 0; I < NB; ++I)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int f = I * 16 + 4 * q + r;
+                    ust[I][r] = (SE*)__shfl(myst, (f >= 1 && f < F) ? f - 1 : 0, 64);
+                }
+        }
+        // (row-wise: its shuffles and its block barrier need uniform control flow, so padding samples and lanes
+        // past the row come along into the loop and leave it per tile row, after the row sums)
+        if constexpr (AG != 2) {
+            if (!live || !colok) continue;
+        }
+#pragma unroll
+        for (int I = 0; I < NB; ++I) {
+            // the second stream of the four rows of tile row I: each one's table pointer (st_base; by shuffle: usr,
+            // which the row-wise rule fills below) and the lane's CPL columns of its row (st_row)
+            SE* usr[4];
+            if constexpr ((SU::kSplit || AG == 1) && !ST_LDS) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) usr[r] = ust[I][r];
+            }
+            auto st_base = [&](int r) {
+                const int f = I * 16 + 4 * q + r;
+                SE* base;
+                if constexpr (ST_LDS) base = sop[f - 1];
+                else base = usr[r];
+                return base;
+            };
+            auto st_row = [&](auto r) { return st_base(r) + (int64_t)urow[I][r] * d + n0; };  // (generic: State may be void)
+            // split: the low halves of this lane's once-hit rows among the four of tile row I (its CPL columns),
+            // loaded together before the first of them is written (8 columns per lane: each at its write --
+            // four 16-B vectors would take that form from 6 to 4 waves per SIMD at 16 features).  Issued
+            // behind the gathered rows they would travel beside the gather, but waiting as bits through the
+            // MFMAs they took the two-wave form from 8 to 6 waves per SIMD at 16 features and spilt at 32.
+            typename Halves<CPL>::type lov[4];
+            if constexpr (SU::kSplit && CPL == 4) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (I * 16 + 4 * q + r < F && urow[I][r] != ~0u) lov[r] = load_halves<CPL>(st_row(r));
+            }
+            // Adagrad: the state of this lane's once-hit rows, loaded here as the low halves are (after the
+            // MFMAs, the four of a tile row together) -- the element-wise rule's fp32 state row at the lane's
+            // columns (8 columns per lane: each at its write), the row-wise rule's word
+            // (with up to 16 features the state is loaded at each row's write instead: four in flight took the
+            // NB = 1 forms below Descent's 8 waves per SIMD)
+            constexpr bool ST4 = NB > 1 && CPL == 4;
+            // row-wise: the four tile rows' sums of squares of G = 0 + g, in the order of the apply's once-hit item
+            // (apply.hpp run_singles, fp32 gradient rows: apply lane v holds columns 4v..4v+3) -- a lane's fma
+            // chain from 0 over four columns in column order, then the xor butterfly over the row's lanes from
+            // distance 1 up.  Lane c holds apply lane 16h + c's columns (8 columns per lane: lanes 2c and 2c + 1,
+            // so its two chains' sum is level 1 and the butterfly over c levels 2..16); a lane past the row
+            // (!colok: its accumulators are 0) adds +0, which keeps the bits of a sum >= 0.  d = 128 over two
+            // waves: each wave's 64 columns over c, then the last level, one commutative add of the two waves'
+            // totals, through LDS (a slot per tile row I: one barrier each, nothing is overwritten).
+            // The state word m of a row is one address for both waves, and wave 0 stores m' there: so only wave 0
+            // ever loads it (its c == 0 lanes, before the barrier) and hands it to both waves through the same LDS
+            // exchange.  Wave 1 never reads a word that wave 0 writes.
+            float rs[4];
+            float mx[4];  // two waves: the rows' state words, out of LDS
+            if constexpr (AG == 2) {
+                float m0w[4];
+                if constexpr (WPS == 2) {
+                    if (h == 0 && c == 0 && live) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int f = I * 16 + 4 * q + r;
+                            if (f < F && urow[I][r] != ~0u) m0w[r] = ldg<float>(sop[f - 1] + urow[I][r]);
+                        }
+                    }
+                }
+                if constexpr (!ST_LDS) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int f = I * 16 + 4 * q + r;
+                        usr[r] = (SE*)__shfl(myst, (f >= 1 && f < F) ? f - 1 : 0, 64);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float g[CPL];
+#pragma unroll
+                    for (int e = 0; e < CPL; ++e) g[e] = 0.0f + acc[I][e][r];
+                    float ss = sum_squares<4>(g, 0.0f);
+                    if constexpr (CPL == 8) ss += sum_squares<4>(g + 4, 0.0f);
+#pragma unroll
+                    for (int o = 1; o < 16; o <<= 1) ss += __shfl_xor(ss, o, 64);
+                    rs[r] = ss;
+                }
+                if constexpr (WPS == 2) {
+                    float* sx = row_ss_tab<SPB * 3 * NS>();  // [SPB][wave 0's sums, wave 1's sums, m][NS]
+                    if (c == 0) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) sx[(pair * 3 + h) * NS + I * 16 + 4 * q + r] = rs[r];
+                        if (h == 0 && live) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const int f = I * 16 + 4 * q + r;
+                                if (f < F && urow[I][r] != ~0u) sx[(pair * 3 + 2) * NS + f] = m0w[r];
+                            }
+                        }
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        rs[r] += sx[(pair * 3 + (h ^ 1)) * NS + I * 16 + 4 * q + r];
+                        mx[r] = sx[(pair * 3 + 2) * NS + I * 16 + 4 * q + r];
+                    }
+                }
+                if (!live || !colok) continue;
+            }
+            f32x4_t sv[AG == 1 && ST4 ? 4 : 1];
+            float mv[AG == 2 && ST4 && WPS == 1 ? 4 : 1];
+            if constexpr (AG == 1 && ST4) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (I * 16 + 4 * q + r < F && urow[I][r] != ~0u)
+                        sv[r] = ldg<f32x4_t>(st_row(r));
+            }
+            if constexpr (AG == 2 && ST4 && WPS == 1) {  // (one wave holds the row: its own loads, then its store)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (I * 16 + 4 * q + r < F && urow[I][r] != ~0u) mv[r] = ldg<float>(st_base(r) + urow[I][r]);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = I * 16 + 4 * q + r;
+                if (f < F) {
+                    float v[CPL];
+#pragma unroll
+                    for (int e = 0; e < CPL; ++e) v[e] = acc[I][e][r];
+                    if (urow[I][r] != ~0u) {
+                        float wv[CPL];
+                        float tw[CPL];  // the row as gathered
+                        if constexpr (CPL == 4) {
+                            const f32x4_t t4 = *(const f32x4_t*)(Tt + f * SBC + 4 * c);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) tw[e] = t4[e];
+                        } else {
+                            typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+                            const u32x4_t t8 = *(const u32x4_t*)(Tt + f * SBC + 8 * c);
+#pragma unroll
+                            for (int e = 0; e < 8; ++e)
+                                tw[e] = __uint_as_float((e & 1) ? (t8[e >> 1] & 0xffff0000u) : (t8[e >> 1] << 16));
+                        }
+                        if constexpr (SU::kSplit) {
+                            // (either tile layout gives the element's bf16 bits << 16 exactly)
+                            const int64_t ro = (int64_t)urow[I][r] * d + n0;
+                            uint32_t hb[CPL];
+#pragma unroll
+                            for (int e = 0; e < CPL; ++e) hb[e] = __float_as_uint(tw[e]);
+                            if constexpr (CPL == 8) lov[r] = load_halves<CPL>(st_row(r));
+                            split_once_hit<CPL>(su.lr, v, hb, lov[r], (uint16_t*)tds[f - 1].data + ro, st_row(r));
+                        } else if constexpr (AG == 1) {
+                            // A += G^2, w -= lr G / (sqrt(A) + eps) with G = 0 + g: apply.hpp's adagrad_step
+                            float* srow = st_row(r);
+                            float gg[CPL], av[CPL];
+#pragma unroll
+                            for (int e = 0; e < CPL; e += 4) {
+                                f32x4_t a4;
+                                if constexpr (ST4) a4 = sv[r];
+                                else a4 = ldg<f32x4_t>(srow + e);
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    av[e + k] = a4[k];
+                                    gg[e + k] = 0.0f + v[e + k];
+                                }
+                            }
+                            adagrad_step<CPL>(su.lr, su.eps, gg, av, tw);
+#pragma unroll
+                            for (int e = 0; e < CPL; e += 4)
+                                stg_nt<f32x4_t>(srow + e, f32x4_t{av[e], av[e + 1], av[e + 2], av[e + 3]});
+                            store_row<T, CPL, true>((T*)tds[f - 1].data + (int64_t)urow[I][r] * d, n0, tw);
+                        } else if constexpr (AG == 2) {
+                            // m += ss / D, w -= (lr / (sqrt(m) + eps)) G: apply.hpp's helpers, one lane stores m
+                            float m0;
+                            if constexpr (WPS == 2) m0 = mx[r];
+                            else if constexpr (ST4) m0 = mv[r];
+                            else m0 = ldg<float>(st_base(r) + urow[I][r]);
+                            const float m = rowwise_m(m0, rs[r], d);
+                            const float sc = rowwise_scale(su.lr, su.eps, m);
+#pragma unroll
+                            for (int e = 0; e < CPL; ++e) wv[e] = __builtin_fmaf(-sc, 0.0f + v[e], tw[e]);
+                            store_row<T, CPL, true>((T*)tds[f - 1].data + (int64_t)urow[I][r] * d, n0, wv);
+                            if (c == 0 && h == 0) stg<float>(st_base(r) + urow[I][r], m);
+                        } else {
+#pragma unroll
+                        for (int e = 0; e < CPL; ++e) wv[e] = __builtin_fmaf(-su.lr, 0.0f + v[e], tw[e]);
+                        store_row<T, CPL, true>((T*)tds[f - 1].data + (int64_t)urow[I][r] * d, n0, wv);
+                        }
+                    } else if (!mapped && (f > 0 || !su.single)) {
+                        // (the training step (su.single set) leaves dt's x row alone: dx carries it)
+                        // (CPL = 8: a lane's two 16-B pieces are 32 B apart, so each store instruction
+                        // covers half of every line: plain stores let L2 merge the halves, where
+                        // non-temporal ones left as partial-line writes, 95 -> 117 MB per launch)
+#pragma unroll
+                        for (int e = 0; e < CPL; e += 4) {
+                            const f32x4_t pv4 = f32x4_t{v[e], v[e + 1], v[e + 2], v[e + 3]};
+                            if constexpr (CPL == 8) stg<f32x4_t>(dt + b * dt_ld + (int64_t)f * d + n0 + e, pv4);
+                            else stg_nt<f32x4_t>(dt + b * dt_ld + (int64_t)f * d + n0 + e, pv4);
+                        }
+                    } else if (f > 0) {
+#pragma unroll
+                        for (int e = 0; e < CPL; e += 4)
+                            stg_nt<f32x4_t>(dt + dmap[f - 1] + b * dmap[F - 2 + f] + n0 + e,
+                                            f32x4_t{v[e], v[e + 1], v[e + 2], v[e + 3]});
+                    }
+                    if (f == 0)
+#pragma unroll
+                        for (int e = 0; e < CPL; e += 4)
+                            stg<f32x4_t>(dx + b * dx_ld + n0 + e, f32x4_t{xo[e] + v[e], xo[e + 1] + v[e + 1],
+                                                                         xo[e + 2] + v[e + 2], xo[e + 3] + v[e + 3]});
+                }
+            }
+        }
+        if (h == 0 && sbi == 0) {
+            WT(1, 3, b);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            WT(1, 4, b);
+        }
+    }
 }
 
 // ------------------------------------------------------------------ scalar fallbacks
@@ -1160,215 +1567,144 @@ int launch_step_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, i
     return ctx_hip(ctx, hipGetLastError(), "step_fwd launch");
 }
 
-// Training-step backward after launch_step_fwd: once-hit rows updated in place, dt rows of the
-// others written for the apply.  The caller checked the shape (launch_step_fwd accepted it)
-// and the 16-B alignment of dx / dt.
-// The same on split-bf16 tables (lo = the device array of low-half pointers, 16-B aligned rows): the default
-// geometries only (the DLRM_BWD_SPB / DLRM_BWD_CPL / DLRM_UPD_SBU overrides are the Descent kernels').
-static int launch_step_bwd_lo(dlrm_ctx* ctx, const GatherArgs& ga, int F, int d, int B, const uint16_t* x, int64_t x_ld,
-                              const uint16_t* dout, int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
-                              const SplitStepUpdate& su) {
-    const int NB = (F + 15) / 16;
-    hipStream_t s = ctx_stream(ctx);
-#define DLRM_LAUNCH_LO(N_, DC_, S_, W_, C_)                                                                        \
-    hipLaunchKernelGGL((interact_bwd_split_lo_kernel<N_, DC_, S_, W_, C_>), dim3((unsigned)((B + S_ - 1) / S_)),    \
-                       dim3(64 * W_ * S_), 0, s, d, F, B, dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, x, x_ld, su)
-    if (!knobs().bwd_nosplit && d == 128) {
-        // 8 columns per lane (B > 2048), one wave per sample, 2 samples per block: with 17..32 features.  With
-        // up to 16 the split write took that form from 6 to 5 waves per SIMD (96 VGPRs against Descent's 80),
-        // so those shapes keep the two-wave form, which holds Descent's 8.
-        if (B > 2048 && NB == 2) {
-            DLRM_LAUNCH_LO(2, 128, 2, 1, 8);
-        } else {         // two waves per sample, 4 samples per block
-            if (NB == 1) DLRM_LAUNCH_LO(1, 128, 4, 2, 4); else DLRM_LAUNCH_LO(2, 128, 4, 2, 4);
-        }
-        return ctx_hip(ctx, hipGetLastError(), "split_step_bwd(split) launch");
-    }
-    if (!knobs().bwd_nosplit && d <= 64) {  // one wave per sample, 8 samples per block
-        if (NB == 1) DLRM_LAUNCH_LO(1, 0, 8, 1, 4); else DLRM_LAUNCH_LO(2, 0, 8, 1, 4);
-        return ctx_hip(ctx, hipGetLastError(), "split_step_bwd(one wave per sample) launch");
-    }
-#undef DLRM_LAUNCH_LO
-#define DLRM_LAUNCH_LOUP(N_)                                                                                       \
-    {                                                                                                              \
-        typedef BwdGeom<N_> G;                                                                                     \
-        const size_t lds = sizeof(float) * G::template lds_floats<true>() * G::WPB +                               \
-                           (sizeof(TableDesc) + sizeof(uint16_t*)) * (F - 1);                                      \
-        hipLaunchKernelGGL((interact_bwd_update_lo_kernel<N_>), dim3(grid_for(B, G::WPB, ctx_num_cus(ctx))),        \
-                           dim3(64 * G::WPB), lds, s, d, F, B, dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, x, x_ld, su); \
-    }
-    if (NB == 1) DLRM_LAUNCH_LOUP(1) else DLRM_LAUNCH_LOUP(2)
-#undef DLRM_LAUNCH_LOUP
-    return ctx_hip(ctx, hipGetLastError(), "split_step_bwd launch");
+// The forms <NB, WPS, CPL, SPB> of interact_bwd_split_kernel that exist for a rule (split; adagrad 1: element-wise,
+// 2: row-wise; neither: Descent) and an element type.  d = 128: two waves per sample (WPS 2, 4 samples per block),
+// or 8 columns per lane (bf16 rows, one wave per sample, 2 samples per block); d <= 64: one wave per sample, 8
+// samples per block.  Descent has them all, with 2, 4 or 8 samples per block at d = 128 (DLRM_BWD_SPB).  The other
+// rules have the default samples per block only, and no form that would run below Descent's occupancy
+// (DESIGN.md sections 14 and 15):
+//  - 8 columns per lane with up to 16 features (NB = 1): the split write took that form from 6 to 5 waves per SIMD
+//    (96 VGPRs against Descent's 80), so those shapes keep the two-wave form, which holds Descent's 8;
+//  - with up to 16 features Descent's forms hold 8 waves per SIMD at 56..59 VGPRs, and the row-wise forms need
+//    77..87, the element-wise one-wave form on fp32 tables 66.
+// The split rule's rows live in bf16 tables.
+constexpr bool step_bwd_form(bool split, int adagrad, bool f32, int NB, int WPS, int CPL, int SPB) {
+    const bool d128 = WPS == 2 || CPL == 8;
+    if ((CPL == 8 && (f32 || WPS != 1)) || !(SPB == 2 || SPB == 4 || SPB == 8)) return false;
+    if (SPB != (CPL == 8 ? 2 : (d128 ? 4 : 8))) return !split && !adagrad && d128;
+    if (!split && !adagrad) return true;
+    if (CPL == 8 && NB == 1) return false;
+    if (split) return !f32;
+    return adagrad == 2 ? NB == 2 : !(NB == 1 && WPS == 1 && f32);
+}
+// Shapes whose step backward has an Adagrad form (among step_split_supported's): d = 128 and d <= 64, the forms
+// of interact_bwd_split_kernel.  The row-wise rule also needs the vector apply's summation order to exist for
+// the shape (fp32 dt rows of d / 4 vectors, d / 4 a power of two: apply_kernel.hpp dispatch_apply); the any-D
+// kernels sum a row's squares in column order, which no lane layout here reproduces.  Any other d (the
+// interact_bwd_update_kernel shapes) and the DLRM_BWD_NOSPLIT override take the gather backward.
+bool adagrad_step_bwd_supported(bool rowwise, int dtype, int T_, int d) {
+    if (knobs().bwd_nosplit || !(d == 128 || d <= 64)) return false;
+    if (rowwise && !(d >= 8 && (d & (d - 1)) == 0)) return false;
+    return step_bwd_form(false, rowwise ? 2 : 1, dtype == DLRM_F32, (T_ + 1 + 15) / 16, d == 128 ? 2 : 1, 4,
+                         d == 128 ? 4 : 8);
 }
 
+// Training-step backward after launch_step_fwd under the rule SU: once-hit rows updated in place, dt rows of the
+// others written for the apply.  The caller checked the shape (launch_step_fwd accepted it), the 16-B alignment of
+// dx / dt and of the rule's second stream, and for an Adagrad rule adagrad_step_bwd_supported.  The DLRM_BWD_SPB /
+// DLRM_BWD_CPL / DLRM_UPD_SBU overrides are Descent's.
+template <typename T, typename SU>
+static int launch_step_bwd_rule(dlrm_ctx* ctx, const GatherArgs& ga, int F, int d, int B, const void* x_, int64_t x_ld,
+                                const void* dout_, int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
+                                const SU& su) {
+    constexpr bool f32 = sizeof(T) == 4, descent = !SU::kSplit && !SU::kAdagrad;
+    const T* x = (const T*)x_;
+    const T* dout = (const T*)dout_;
+    const int NB = (F + 15) / 16;
+    hipStream_t s = ctx_stream(ctx);
+    auto launched = [&](const char* form) {
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? DLRM_OK : ctx_hip(ctx, e, (std::string(SU::kName) + form + " launch").c_str());
+    };
+    // (a form step_bwd_form leaves out is not instantiated)
+#define DLRM_FORM(N_, DC_, W_, C_, S_, WHAT_)                                                                       \
+    if constexpr (step_bwd_form(SU::kSplit, SU::kAdagrad, f32, N_, W_, C_, S_))                                     \
+        if (NB == N_ && spb == S_) {                                                                                \
+            hipLaunchKernelGGL((interact_bwd_split_kernel<T, N_, DC_, S_, W_, false, C_, false, SU>),                \
+                               dim3((unsigned)((B + S_ - 1) / S_)), dim3(64 * W_ * S_), 0, s, d, F, B, dout, dout_ld, \
+                               dx, dx_ld, dt, dt_ld, ga, x, x_ld, su);                                               \
+            return launched(WHAT_);                                                                                 \
+        }
+#define DLRM_FORMS(DC_, W_, C_, WHAT_)                                                                  \
+    DLRM_FORM(1, DC_, W_, C_, 8, WHAT_) DLRM_FORM(1, DC_, W_, C_, 4, WHAT_) DLRM_FORM(1, DC_, W_, C_, 2, WHAT_) \
+    DLRM_FORM(2, DC_, W_, C_, 8, WHAT_) DLRM_FORM(2, DC_, W_, C_, 4, WHAT_) DLRM_FORM(2, DC_, W_, C_, 2, WHAT_)
+    if (!knobs().bwd_nosplit && (d == 128 || d <= 64)) {
+        // bf16, B > 2048: 8 columns per lane, one wave per sample, 2 samples per block
+        // (kaggle-d128-b8192-bf16: backward 52.2 -> 48.4 us, step 110.9 -> 103.3 us, r6q; at B = 2048
+        // the two-wave form keeps the step shorter: Terabyte rows 50.6 vs 48.7 M samples/s, r6s).
+        // DLRM_BWD_CPL = 4 / 8 forces either form.
+        const int cpl_env = descent ? knobs().bwd_cpl : 0;
+        const bool cpl8 = d == 128 && !f32 && (cpl_env ? cpl_env == 8 : B > 2048) &&
+                          step_bwd_form(SU::kSplit, SU::kAdagrad, f32, NB, 1, 8, 2);
+        // samples per block (DLRM_BWD_SPB = 2, 4 or 8 overrides)
+        const int spb_env = !(descent && d == 128) ? 0
+                            : knobs().bwd_spb >= 8 ? 8 : (knobs().bwd_spb >= 4 ? 4 : (knobs().bwd_spb > 0 ? 2 : 0));
+        const int spb = spb_env ? spb_env : (cpl8 ? 2 : (d == 128 ? 4 : 8));
+        if (cpl8) {
+            DLRM_FORMS(128, 1, 8, SU::kAdagrad ? "(8 columns per lane)" : "(split)")
+        } else if (d == 128) {  // (two 64-column super-blocks): two waves per sample
+            DLRM_FORMS(128, 2, 4, "(split)")
+        } else {  // d <= 64: the same kernel with one wave per sample
+            DLRM_FORMS(0, 1, 4, "(one wave per sample)")
+        }
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no kernel for this shape", SU::kName);
+    }
+#undef DLRM_FORMS
+#undef DLRM_FORM
+    // any other d: interact_bwd_update_kernel (Descent and the split rule; an Adagrad rule's caller took the gather
+    // backward).  One super-block of T rows in flight: two (the gather backward's choice) spill here
+    if constexpr (SU::kAdagrad != 0) {
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no kernel for this shape", SU::kName);
+    } else {
+        const int dc = descent && d == 128 ? 128 : 0, sbu = dc == 128 && knobs().upd_sbu == 2 ? 2 : 1;
+#define DLRM_UPD(N_, SBU_, DC_)                                                                                     \
+    if constexpr (descent || (SBU_ == 1 && DC_ == 0))                                                               \
+        if (NB == N_ && sbu == SBU_ && dc == DC_) {                                                                 \
+            typedef BwdGeom<N_> G;                                                                                  \
+            const size_t lds = sizeof(float) * G::template lds_floats<true>() * G::WPB +                            \
+                               (sizeof(TableDesc) + (SU::kSplit ? sizeof(void*) : 0)) * (F - 1);                    \
+            hipLaunchKernelGGL((interact_bwd_update_kernel<T, N_, SBU_, DC_, SU>),                                   \
+                               dim3(grid_for(B, G::WPB, ctx_num_cus(ctx))), dim3(64 * G::WPB), lds, s, d, F, B, dout, \
+                               dout_ld, dx, dx_ld, dt, dt_ld, ga, x, x_ld, su);                                      \
+            return launched("");                                                                                    \
+        }
+        DLRM_UPD(1, 2, 128) DLRM_UPD(1, 1, 128) DLRM_UPD(1, 1, 0) DLRM_UPD(2, 2, 128) DLRM_UPD(2, 1, 128) DLRM_UPD(2, 1, 0)
+#undef DLRM_UPD
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no kernel for this shape", SU::kName);
+    }
+}
+
+// (lo: the device array of a split-bf16 table set's low-half pointers, 16-B aligned rows; the caller checked the dtype)
 int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, const void* idx, int itype,
                     int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
                     int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
                     float lr,
                     const TableDesc* htabs, uint16_t* const* lo) {
     if (B == 0 || T_ == 0) return DLRM_OK;
-    const int F = T_ + 1;
-    const int NB = (F + 15) / 16;
-    hipStream_t s = ctx_stream(ctx);
-    const int cus = ctx_num_cus(ctx);
-    GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
-    StepUpdate su{ix.single, ix.cap, lr, ctx_error_word(ctx)};
-    if (lo) {  // split-bf16 tables (the caller checked the dtype and the low halves' alignment)
-        const SplitStepUpdate sl{su, lo};
-        return launch_step_bwd_lo(ctx, ga, F, d, B, (const uint16_t*)x, x_ld, (const uint16_t*)dout, dout_ld, dx, dx_ld,
-                                  dt, dt_ld, sl);
-    }
-    // one super-block of T rows in flight: two (the gather backward's choice) spill here
-    const int sbu = knobs().upd_sbu;
-    // d = 128 (two 64-column super-blocks): two waves per sample (interact_bwd_split_kernel)
-    const bool split = !knobs().bwd_nosplit;
-    if (split && d == 128) {
-        // samples per block (DLRM_BWD_SPB = 2, 4 or 8 overrides)
-        const int spb_env = knobs().bwd_spb >= 8 ? 8 : (knobs().bwd_spb >= 4 ? 4 : (knobs().bwd_spb > 0 ? 2 : 0));
-#define DLRM_LAUNCH_SPLIT(TY, N_, S_)                                                                              \
-    hipLaunchKernelGGL((interact_bwd_split_kernel<TY, N_, 128, S_>), dim3((unsigned)((B + S_ - 1) / S_)),            \
-                       dim3(128 * S_), 0, s, d, F, B, (const TY*)dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, (const TY*)x,  \
-                       x_ld, su)
-#define DLRM_LAUNCH_SPLIT_S(TY, N_)                 \
-    if (spb == 8) DLRM_LAUNCH_SPLIT(TY, N_, 8);     \
-    else if (spb == 4) DLRM_LAUNCH_SPLIT(TY, N_, 4); \
-    else DLRM_LAUNCH_SPLIT(TY, N_, 2);
-        // bf16, B > 2048: 8 columns per lane, one wave per sample, 2 samples per block
-        // (kaggle-d128-b8192-bf16: backward 52.2 -> 48.4 us, step 110.9 -> 103.3 us, r6q; at B = 2048
-        // the two-wave form keeps the step shorter: Terabyte rows 50.6 vs 48.7 M samples/s, r6s).
-        // DLRM_BWD_CPL = 4 / 8 forces either form.
-        const int cpl_env = knobs().bwd_cpl;
-        const bool cpl8 = dtype != DLRM_F32 && (cpl_env ? cpl_env == 8 : B > 2048);
-        const int spb = spb_env ? spb_env : (cpl8 ? 2 : 4);
-#define DLRM_LAUNCH_SPLIT8(N_, S_)                                                                                 \
-    hipLaunchKernelGGL((interact_bwd_split_kernel<uint16_t, N_, 128, S_, 1, false, 8>),                             \
-                       dim3((unsigned)((B + S_ - 1) / S_)), dim3(64 * S_), 0, s, d, F, B, (const uint16_t*)dout,    \
-                       dout_ld, dx, dx_ld, dt, dt_ld, ga, (const uint16_t*)x, x_ld, su)
-#define DLRM_LAUNCH_SPLIT8_S(N_)                 \
-    if (spb == 8) DLRM_LAUNCH_SPLIT8(N_, 8);     \
-    else if (spb == 4) DLRM_LAUNCH_SPLIT8(N_, 4); \
-    else DLRM_LAUNCH_SPLIT8(N_, 2);
-        if (dtype == DLRM_F32) {
-            if (NB == 1) { DLRM_LAUNCH_SPLIT_S(float, 1) } else { DLRM_LAUNCH_SPLIT_S(float, 2) }
-        } else if (cpl8) {
-            if (NB == 1) { DLRM_LAUNCH_SPLIT8_S(1) } else { DLRM_LAUNCH_SPLIT8_S(2) }
-        } else {
-            if (NB == 1) { DLRM_LAUNCH_SPLIT_S(uint16_t, 1) } else { DLRM_LAUNCH_SPLIT_S(uint16_t, 2) }
-        }
-#undef DLRM_LAUNCH_SPLIT8_S
-#undef DLRM_LAUNCH_SPLIT8
-#undef DLRM_LAUNCH_SPLIT_S
-#undef DLRM_LAUNCH_SPLIT
-        return ctx_hip(ctx, hipGetLastError(), "step_bwd(split) launch");
-    }
-    // d <= 64: the same kernel with one wave per sample, 8 samples per block
-    if (split && d <= 64) {
-#define DLRM_LAUNCH_ONE(TY, N_)                                                                                    \
-    hipLaunchKernelGGL((interact_bwd_split_kernel<TY, N_, 0, 8, 1>), dim3((unsigned)((B + 7) / 8)), dim3(64 * 8), 0, \
-                       s, d, F, B, (const TY*)dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, (const TY*)x, x_ld, su)
-        if (dtype == DLRM_F32) {
-            if (NB == 1) DLRM_LAUNCH_ONE(float, 1); else DLRM_LAUNCH_ONE(float, 2);
-        } else {
-            if (NB == 1) DLRM_LAUNCH_ONE(uint16_t, 1); else DLRM_LAUNCH_ONE(uint16_t, 2);
-        }
-#undef DLRM_LAUNCH_ONE
-        return ctx_hip(ctx, hipGetLastError(), "step_bwd(one wave per sample) launch");
-    }
-#define DLRM_LAUNCH_BWDUP(TY, N_)                                                                                  \
-    {                                                                                                              \
-        typedef BwdGeom<N_> G;                                                                                     \
-        const size_t lds = sizeof(float) * G::template lds_floats<true>() * G::WPB + sizeof(TableDesc) * T_;       \
-        const dim3 grid(grid_for(B, G::WPB, cus)), blk(64 * G::WPB);                                               \
-        if (d == 128 && sbu == 2)                                                                                  \
-            hipLaunchKernelGGL((interact_bwd_update_kernel<TY, N_, 2, 128>), grid, blk, lds, s, d, F, B,             \
-                               (const TY*)dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, (const TY*)x, x_ld, su);         \
-        else if (d == 128)                                                                                         \
-            hipLaunchKernelGGL((interact_bwd_update_kernel<TY, N_, 1, 128>), grid, blk, lds, s, d, F, B,             \
-                               (const TY*)dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, (const TY*)x, x_ld, su);         \
-        else                                                                                                       \
-            hipLaunchKernelGGL((interact_bwd_update_kernel<TY, N_, 1>), grid, blk, lds, s, d, F, B, (const TY*)dout, \
-                               dout_ld, dx, dx_ld, dt, dt_ld, ga, (const TY*)x, x_ld, su);                          \
-    }
-    if (dtype == DLRM_F32) {
-        if (NB == 1) DLRM_LAUNCH_BWDUP(float, 1) else DLRM_LAUNCH_BWDUP(float, 2)
-    } else {
-        if (NB == 1) DLRM_LAUNCH_BWDUP(uint16_t, 1) else DLRM_LAUNCH_BWDUP(uint16_t, 2)
-    }
-#undef DLRM_LAUNCH_BWDUP
-    return ctx_hip(ctx, hipGetLastError(), "step_bwd launch");
+    const GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
+    const StepUpdate su{ix.single, ix.cap, lr, ctx_error_word(ctx)};
+#define DLRM_RULE(TY, ...) \
+    return launch_step_bwd_rule<TY>(ctx, ga, T_ + 1, d, B, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, __VA_ARGS__)
+    if (lo) DLRM_RULE(uint16_t, SplitStepUpdate{su, lo});
+    if (dtype == DLRM_F32) DLRM_RULE(float, su);
+    DLRM_RULE(uint16_t, su);
 }
 
-// (The Adagrad step's launchers come last in this unit: its kernels are then instantiated, and emitted into the
-// code object, after every other kernel, whose offsets in it stay what they were.)
-// Shapes whose step backward has an Adagrad form (among step_split_supported's): d = 128 and d <= 64, the forms
-// of interact_bwd_split_kernel.  The row-wise rule also needs the vector apply's summation order to exist for
-// the shape (fp32 dt rows of d / 4 vectors, d / 4 a power of two: apply_kernel.hpp dispatch_apply); the any-D
-// kernels sum a row's squares in column order, which no lane layout here reproduces.  Any other d (the
-// interact_bwd_update_kernel shapes) and the DLRM_BWD_NOSPLIT override take the gather backward.
-// Forms that would run below Descent's occupancy are not instantiated either: with up to 16
-// features (NB = 1) Descent's forms hold 8 waves per SIMD at 56..59 VGPRs, and the row-wise forms need 77..87, the
-// element-wise one-wave form on fp32 tables 66.
-constexpr bool adagrad_form(bool rowwise, bool f32, int NB, int WPS) {
-    return rowwise ? NB == 2 : !(NB == 1 && WPS == 1 && f32);
-}
-bool adagrad_step_bwd_supported(bool rowwise, int dtype, int T_, int d) {
-    if (knobs().bwd_nosplit || !(d == 128 || d <= 64)) return false;
-    if (rowwise && !(d >= 8 && (d & (d - 1)) == 0)) return false;
-    return adagrad_form(rowwise, dtype == DLRM_F32, (T_ + 1 + 15) / 16, d == 128 ? 2 : 1);
-}
-
-// Training-step backward with a sparse Adagrad rule (state = the device array of state pointers; the
-// element-wise rule's rows 16-B aligned): the default geometries only, as launch_step_bwd_lo.
-template <typename T, bool RW>
-static int launch_step_bwd_ag(dlrm_ctx* ctx, const GatherArgs& ga, int F, int d, int B, const T* x, int64_t x_ld,
-                              const T* dout, int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
-                              const AdagradStepUpdate<RW>& su) {
-    const int NB = (F + 15) / 16;
-    hipStream_t s = ctx_stream(ctx);
-    // (a form adagrad_form leaves out is not instantiated: the caller asked adagrad_step_bwd_supported)
-#define DLRM_LAUNCH_AG(N_, DC_, S_, W_, C_)                                                                        \
-    if constexpr (adagrad_form(RW, sizeof(T) == 4, N_, W_))                                                        \
-        hipLaunchKernelGGL((interact_bwd_split_ag_kernel<T, N_, DC_, S_, W_, C_, RW>),                              \
-                           dim3((unsigned)((B + S_ - 1) / S_)), dim3(64 * W_ * S_), 0, s, d, F, B, dout, dout_ld,   \
-                           dx, dx_ld, dt, dt_ld, ga, x, x_ld, su);                                                  \
-    else                                                                                                           \
-        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "adagrad_step_bwd: no kernel for this shape")
-    if (d == 128) {
-        if constexpr (sizeof(T) == 2) {
-            // 8 columns per lane (bf16, B > 2048), one wave per sample, 2 samples per block: with 17..32 features,
-            // as the split rule (with up to 16 the two-wave form)
-            if (B > 2048 && NB == 2) {
-                DLRM_LAUNCH_AG(2, 128, 2, 1, 8);
-                return ctx_hip(ctx, hipGetLastError(), "adagrad_step_bwd(8 columns per lane) launch");
-            }
-        }
-        if (NB == 1) { DLRM_LAUNCH_AG(1, 128, 4, 2, 4); } else { DLRM_LAUNCH_AG(2, 128, 4, 2, 4); }
-        return ctx_hip(ctx, hipGetLastError(), "adagrad_step_bwd(split) launch");
-    }
-    // d <= 64: one wave per sample, 8 samples per block
-    if (NB == 1) { DLRM_LAUNCH_AG(1, 0, 8, 1, 4); } else { DLRM_LAUNCH_AG(2, 0, 8, 1, 4); }
-#undef DLRM_LAUNCH_AG
-    return ctx_hip(ctx, hipGetLastError(), "adagrad_step_bwd(one wave per sample) launch");
-}
-
+// (state: the device array of the rule's state pointers; the element-wise rule's rows 16-B aligned)
 int launch_adagrad_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, const void* idx, int itype,
                             int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
                             int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
                             float lr, float eps, bool rowwise, float* const* state) {
     if (B == 0 || T_ == 0) return DLRM_OK;
-    const int F = T_ + 1;
-    GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
+    const GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
     const StepUpdate su{ix.single, ix.cap, lr, ctx_error_word(ctx)};
-#define DLRM_AG(TY, RW_)                                                                                           \
-    return launch_step_bwd_ag<TY, RW_>(ctx, ga, F, d, B, (const TY*)x, x_ld, (const TY*)dout, dout_ld, dx, dx_ld, dt, \
-                                       dt_ld, AdagradStepUpdate<RW_>{su, state, eps})
     if (dtype == DLRM_F32) {
-        if (rowwise) DLRM_AG(float, true); else DLRM_AG(float, false);
-    } else {
-        if (rowwise) DLRM_AG(uint16_t, true); else DLRM_AG(uint16_t, false);
+        if (rowwise) DLRM_RULE(float, AdagradStepUpdate<true>{su, state, eps});
+        DLRM_RULE(float, AdagradStepUpdate<false>{su, state, eps});
     }
-#undef DLRM_AG
+    if (rowwise) DLRM_RULE(uint16_t, AdagradStepUpdate<true>{su, state, eps});
+    DLRM_RULE(uint16_t, AdagradStepUpdate<false>{su, state, eps});
+#undef DLRM_RULE
 }
 
 }  // namespace dlrm
