@@ -49,12 +49,15 @@ extern "C" int dlrm_debug_phase_fwd_reset(void) {
 // Per-sample wave timestamps (wall_clock64, 100 MHz) of the forward (kind 0) and backward
 // (kind 1) bodies; only in the tracing build (tools/wave_trace.sh).  Forward slots: 0 start,
 // 1 indices returned, 2 first column step landed, 3 last column step landed, 4 MFMAs done,
-// 5 output stores issued (the one-hot body stamps all six, fwd_onehot.hpp; the pooled body 0, 4, 5).
-__device__ unsigned long long g_wt[2][6][8192];
+// 5 output stores issued (the one-hot body stamps all six, fwd_onehot.hpp; the pooled body 0, 4, 5).  Backward
+// slots: the kernels' text 0..4 (start, S barrier, MFMAs done, stores issued, stores drained), bwd_split_tracked
+// its seven (BWTS_FLUSH).
+__device__ unsigned long long g_wt[2][7][8192];
 #define WT(kind, slot, b) do { if ((threadIdx.x & 63) == 0 && (b) < 8192) g_wt[kind][slot][b] = wall_clock64(); } while (0)
 extern "C" int dlrm_debug_wtrace(unsigned long long* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wt), sizeof(g_wt));
 }
+extern "C" int dlrm_debug_wtrace_slots(void) { return 7; }
 #else
 #define WT(kind, slot, b) do {} while (0)
 #endif
@@ -677,6 +680,205 @@ __global__ __launch_bounds__(256, 2) void interact_bwd_update_kernel(int d, int 
                                              dt, dt_ld, ga, x, x_ld, su);
 }
 
+// The instantiations of interact_bwd_split_kernel (below) that run bwd_split_tracked's schedule: Descent on fp32
+// tables at d = 128, two waves per sample, the step's own dt layout (the metric step's backward, 1 or 2 row blocks).
+// Every other instantiation keeps the kernel's text.
+template <typename T, int DC, int WPS, bool MAPPED, int CPL, bool YS, typename SU> constexpr bool bwd_tracked() {
+    return std::is_same<T, float>::value && DC == 128 && WPS == 2 && CPL == 4 && !MAPPED && !YS && !SU::kSplit &&
+           SU::kAdagrad == 0;
+}
+
+#ifdef DLRM_WTRACE
+// Backward stamps: held in registers and written after the wave's last store, so no stamp's store sits in the
+// in-order vmcnt queue of the row loads.  Slots: 0 start, 1 indices back, 2 first row load issued, 3 first step
+// landed, 4 last step landed, 5 MFMAs done, 6 last store issued.
+#define BWTS_FLUSH(b) do { if ((threadIdx.x & 63) == 0 && (b) < 8192) { _Pragma("unroll") for (int s_ = 0; s_ < 7; ++s_) g_wt[1][s_][b] = wts_[s_]; } } while (0)
+#else
+#define BWTS_FLUSH(b) do {} while (0)
+#endif
+
+// interact_bwd_split_kernel's work for the bwd_tracked forms (one 64-column super-block per wave, wave h of a
+// sample the columns 64h ..), with the dependent chains between its phases cut:
+//  - lane t loads table t's descriptor itself, beside its index and flag, validates its index and forms its row's
+//    address in-lane; the row addresses (and later the once-hit rows' store addresses) reach their lanes by
+//    shuffles of that address, issued together.  The row loads wait for neither LDS nor a barrier: the barrier
+//    that publishes the packed pair gradients comes behind their issue;
+//  - the pair gradients (the MFMA A operands) are read from LDS without a branch (clamped index, select), all
+//    of them before the first MFMA, so the MFMAs of a step issue back to back;
+//  - per column step s in ascending order: wait for its row, write its tile row, its MFMAs -- the MFMAs track
+//    the arrivals;
+//  - tile row 0 (features 0..15) is accumulated over every step first and stored, then tile row 1: row 0's stores
+//    drain while row 1's MFMAs run on rows that have landed.
+// Every accumulator sums its steps in ascending order, as in the kernel's text: dx, dt and the table rows keep
+// every bit.  Bounds behaviour, zero rows for invalid indices and `frozen` are the kernel's.
+template <int NB, int SPB>
+__device__ __forceinline__ void bwd_split_tracked(int F, int B, const float* __restrict__ dout, int64_t dout_ld,
+                                                  float* __restrict__ dx, int64_t dx_ld, float* __restrict__ dt,
+                                                  int64_t dt_ld, const GatherArgs& ga, const float* __restrict__ x,
+                                                  int64_t x_ld, const StepUpdate& su) {
+    constexpr int NS = 16 * NB, KS = 4 * NB, PMAX = NS * (NS - 1) / 2, d = 128;
+    __shared__ float pk_all[SPB][PMAX];                                      // each sample's packed gradient row
+    __shared__ __attribute__((aligned(16))) float tt_all[2 * SPB][NS * 64];  // each wave's tile of T
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int pair = w >> 1, h = w & 1;
+    const int c = lane & 15, q = lane >> 4;
+    const int64_t b = (int64_t)blockIdx.x * SPB + pair;
+    const bool live = b < B;
+    const int64_t bb = live ? b : 0;  // a padding sample reads sample 0 (and stores nothing)
+    const int ksteps = (F + 3) / 4;
+    const int P = F * (F - 1) / 2;
+    const float* ob = dout + bb * dout_ld;
+    float* pk = pk_all[pair];
+    float* Tt = tt_all[w];
+    const int n0 = 64 * h + 4 * c;  // this lane's 4 output columns
+#ifdef DLRM_WTRACE
+    unsigned long long wts_[7] = {0, 0, 0, 0, 0, 0, 0};
+#endif
+    WTS(0);
+    // ---- every independent load first: table `lane`'s descriptor, index and flag, the packed gradients, x part
+    const bool tl = lane < F - 1;
+    const TableDesc tdl = load_table(ga.tabs, tl ? lane : 0);
+    const int64_t myidx = load_index_if(tl, ga.idx, ga.itype, (int64_t)(tl ? lane : 0) * ga.tstride + bb);
+    // (su.single NULL: no once-hit update, every table row goes to dt; the load executes either way, so no branch
+    // joins behind it with a wait for every load before it)
+    const uint8_t* flp = su.single ? su.single + (tl ? (int64_t)lane * su.cap + bb : 0) : (const uint8_t*)ga.tabs;
+    const uint8_t myfl0 = ldg<uint8_t>(flp);
+    const uint8_t myfl = su.single ? myfl0 : (uint8_t)0;
+    constexpr int PPW = (PMAX + 127) / 128;  // packed values staged per lane
+    float pv[PPW];
+#pragma unroll
+    for (int k = 0; k < PPW; ++k) {
+        const int p = h * 64 + lane + 128 * k;
+        pv[k] = ldg<float>(ob + d + (p < P ? p : 0));  // (masked where it is staged: no wait for it before the rows)
+    }
+    const f32x4_t xo = load4_f32(ob + n0);  // dout's x part at this lane's columns (lanes 0..15 hold output row 0)
+    const bool frozen = su.single ? *su.err != 0 : true;  // a bounds error this step: no table row is written
+    // ---- this lane's row: validated here, its address (0: invalid / no table) and its address as a once-hit row
+    const int64_t myr = myidx - ga.base;
+    const bool myok = tl && myr >= 0 && myr < tdl.nrows;
+    if (tl && !myok && h == 0 && live) raise_index_error(ga.err);
+    const long long myad = myok ? (long long)tdl.data + myr * (int64_t)(d * sizeof(float)) : 0ll;
+    const long long myua = (myfl != 0 && !frozen) ? myad : 0ll;
+    WTS_USE(myad);
+    WTS(1);
+    const float* rowp[KS];
+    unsigned livek = 0;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        const int kk = 4 * s + q;  // (kk >= F: lane kk - 1 holds no table, its address is 0)
+        const long long a = __shfl(myad, kk >= 1 ? kk - 1 : 0, 64);
+        const float* src = kk == 0 ? x + bb * x_ld : (const float*)a;
+        livek |= src ? (1u << s) : 0u;
+        rowp[s] = src ? src : ob;
+    }
+    // the row loads in step order (the steps' waits count on it), every address formed before the first
+    __builtin_amdgcn_sched_barrier(0);
+    f32x4_t bv[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        bv[s] = load4_f32(rowp[s] + n0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (s == 0) WTS(2);
+    }
+    // ---- behind the row loads' issue: the packed gradients to LDS, the block's barrier, the A operands
+#pragma unroll
+    for (int k = 0; k < PPW; ++k) {
+        const int p = h * 64 + lane + 128 * k;
+        if (p < PMAX) pk[p] = p < P ? pv[k] : 0.0f;
+    }
+    __syncthreads();  // pk
+    float av[KS][NB];  // S[16I+c][4s+q]: the symmetric zero-diagonal unpack of the pair row
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int I = 0; I < NB; ++I) {
+            const int i = I * 16 + c, kk = 4 * s + q;
+            const int hi = i > kk ? i : kk, lo = i > kk ? kk : i;
+            const bool on = i != kk && hi < F;
+            const float v = pk[on ? hi * (hi - 1) / 2 + lo : 0];
+            av[s][I] = on ? v : 0.0f;
+        }
+    f32x4_t acc[NB][4];
+#pragma unroll
+    for (int I = 0; I < NB; ++I)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[I][e] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    __builtin_amdgcn_sched_barrier(0);
+    // step s's row has landed: its tile row (the once-hit update reads the tile)
+    auto land = [&](int s) {
+        bv[s] = ((livek >> s) & 1u) ? bv[s] : f32x4_t{0.f, 0.f, 0.f, 0.f};
+        *(f32x4_t*)(Tt + (4 * s + q) * 64 + 4 * c) = bv[s];
+    };
+    auto mfma = [&](int s, int I) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            acc[I][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s][I], bv[s][e], acc[I][e], 0, 0, 0);
+    };
+    // tile row I's four output rows per lane, f = 16I + 4q + r: the table row itself when once-hit, else its dt row
+    // (the training step (su.single set) leaves dt's x row alone: dx carries it)
+    auto store = [&](int I) {
+        long long ua[4];
+        f32x4_t tw[4];  // the rows as gathered
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int f = I * 16 + 4 * q + r;  // (f >= F: lane f - 1 holds no table)
+            const long long a = __shfl(myua, f >= 1 ? f - 1 : 0, 64);
+            ua[r] = f >= 1 ? a : 0ll;
+            tw[r] = *(const f32x4_t*)(Tt + f * 64 + 4 * c);
+        }
+        if (!live) return;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int f = I * 16 + 4 * q + r;
+            if (f < F) {
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = acc[I][e][r];
+                if (ua[r]) {
+                    float wv[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) wv[e] = __builtin_fmaf(-su.lr, 0.0f + v[e], tw[r][e]);
+                    store_row<float, 4, true>((float*)ua[r], n0, wv);
+                } else if (f > 0 || !su.single) {
+                    stg_nt<f32x4_t>(dt + b * dt_ld + (int64_t)f * d + n0, f32x4_t{v[0], v[1], v[2], v[3]});
+                }
+                if (f == 0)
+                    stg<f32x4_t>(dx + b * dx_ld + n0,
+                                 f32x4_t{xo[0] + v[0], xo[1] + v[1], xo[2] + v[2], xo[3] + v[3]});
+            }
+        }
+    };
+    // tile row 0 (features 0..15) over every step first, then its stores, which drain under tile row 1's MFMAs
+    // (on landed rows), then tile row 1's stores
+#pragma unroll
+    for (int I = 0; I < NB; ++I) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            if (s < ksteps) {
+                if (I == 0) {
+                    if (s == 0 || s == ksteps - 1) WTS_USE(bv[s]);
+                    if (s == 0) WTS(3);
+                    if (s == ksteps - 1) WTS(4);
+                    land(s);
+                }
+                mfma(s, I);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (I == 0) wave_lds_sync();  // the tile of T
+        if (I == NB - 1) {
+            WTS_USE(acc[I][3]);
+            WTS(5);
+        }
+        store(I);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    WTS(6);
+    if (h == 0) BWTS_FLUSH(b);
+    // (a flat store: behind the last wait on a load, so that every such wait keeps its count)
+    if (su.single && blockIdx.x == 0 && threadIdx.x == 0) snapshot_error(su.err, frozen ? 1u : 0u);
+}
+
 // The training step's backward with each sample split over TWO waves by column halves (wave h
 // takes the 64-column super-blocks sb = h, h + 2, ...): every wave's dependent chain (indices ->
 // rows -> MFMA -> stores) is half as long and needs about half the registers, so four waves per
@@ -731,6 +933,10 @@ __global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) vo
     // the row-wise sum of squares crosses the sample's two waves once: one super-block per wave, so the block
     // barrier of that exchange sits in uniform control flow
     static_assert(AG != 2 || WPS == 1 || DC == 128, "row-wise over two waves: d = 128");
+    if constexpr (bwd_tracked<T, DC, WPS, MAPPED, CPL, YS, SU>()) {
+        bwd_split_tracked<NB, SPB>(F, B, dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, x, x_ld, su);
+        return;
+    }
     constexpr int NS = 16 * NB;
     constexpr int KS = 4 * NB;
     constexpr int PMAX = NS * (NS - 1) / 2;

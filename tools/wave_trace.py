@@ -5,10 +5,13 @@ of each phase.  fwd slots: 0 start, 1 indices returned, 2 first column step land
 step landed, 4 MFMAs done, 5 output stores issued; printed overall and for the first / second
 workgroup of a CU (samples < B/2 / >= B/2), with each wave's landing spread (last landed - first
 landed) and MFMA tail (MFMAs done - last landed).  bwd slots: 0 start, 1 S built, 2 super-block 0
-MFMA done, 3 super-block 1 MFMA done, 4 stores issued.
+MFMA done, 3 super-block 1 MFMA done, 4 stores issued.  The split step backward: 0 start, 1 S barrier,
+2 MFMAs done, 3 stores issued, 4 stores drained; its tracked schedule (bwd_split_tracked) stamps seven
+slots from registers after the wave's last store: 0 start, 1 indices back, 2 first row load issued,
+3 first step landed, 4 last step landed, 5 MFMAs done, 6 last store issued.
 Modes (arguments): ops (lone operator launches), step (lone step_fwd / step_bwd launches),
-metric (the forward inside the metric step: a graph of 8 consecutive training steps as bench.py
-runs them, the stamps of the last step's forward)."""
+metric (the forward and the backward inside the metric step: a graph of 8 consecutive training steps
+as bench.py runs them, the stamps of the last step's launches)."""
 import ctypes
 import os
 import sys
@@ -32,11 +35,16 @@ packs = [pkg.PackedIndices(torch.stack([torch.randint(0, n, (B,), device=dev, ge
 hp = pkg.HotPath(ts, B, 1, lr=0.01, index_base=0)
 x = torch.randn((B, D), device=dev, generator=g)
 dout = torch.randn((B, hp.width), device=dev, generator=g) * 1e-3
-buf = (ctypes.c_ulonglong * (2 * 6 * 8192))()
+# (a library from before the backward's seven stamps has six slots per kind and no slot count to ask for)
+NSLOT = lib.dlrm_debug_wtrace_slots() if hasattr(lib, "dlrm_debug_wtrace_slots") else 6
+buf = (ctypes.c_ulonglong * (2 * NSLOT * 8192))()
 lib.dlrm_debug_wtrace.restype = ctypes.c_int
 
 
 FWD = ["start", "indices returned", "first step landed", "last step landed", "mfma done", "stores issued"]
+BWD_SPLIT = ["start", "S barrier", "mfma done", "stores issued", "stores drained"]
+BWD_TRACKED = ["start", "indices back", "first row load issued", "first step landed", "last step landed", "mfma done",
+               "last store issued"]
 
 
 def pcts(d):
@@ -45,7 +53,7 @@ def pcts(d):
 
 def show(kind, slots, names, sel=None):
     lib.dlrm_debug_wtrace(buf)
-    a = np.array(buf, dtype=np.int64).reshape(2, 6, 8192)[kind][:, :B]
+    a = np.array(buf, dtype=np.int64).reshape(2, NSLOT, 8192)[kind][:, :B]
     t0 = a[0].min()
     rel = (a - t0) / 100.0  # us
     if sel is not None:
@@ -60,6 +68,21 @@ def show(kind, slots, names, sel=None):
     if kind == 0 and a[3].max() > 0:
         print(f"  {'landing spread (last-first)':28s} {pcts(rel[3] - rel[2])}")
         print(f"  {'mfma tail (done-last landed)':28s} {pcts(rel[4] - rel[3])}")
+
+
+def show_bwd():
+    """The step backward's phases: the tracked schedule's seven slots where the launch stamped them, else
+    the kernel text's five."""
+    lib.dlrm_debug_wtrace(buf)
+    a = np.array(buf, dtype=np.int64).reshape(2, NSLOT, 8192)[1][:, :B] / 100.0
+    if NSLOT > 6 and a[6].max() > 0:
+        show(1, 7, BWD_TRACKED)
+        print(f"  {'landing spread (last-first)':28s} {pcts(a[4] - a[3])}")
+        print(f"  {'mfma tail (done-last landed)':28s} {pcts(a[5] - a[4])}")
+        print(f"  {'wave life (last store-start)':28s} {pcts(a[6] - a[0])}")
+    else:
+        show(1, 5, BWD_SPLIT)
+        print(f"  {'wave life (stores issued-start)':28s} {pcts(a[3] - a[0])}")
 
 
 def show_fwd():
@@ -120,6 +143,8 @@ for mode in sys.argv[1:] or ["ops"]:
         torch.cuda.synchronize()
         print(f"forward inside the metric step (pipeline {eng.pipeline}; graph of 8 steps, last step's forward):")
         show_fwd()
+        print("backward inside the metric step (last step's backward):")
+        show_bwd()
     else:
         print("step_fwd:")
         hp.step_fwd(x, packs[2]); torch.cuda.synchronize()
