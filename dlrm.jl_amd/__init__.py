@@ -19,8 +19,8 @@ from .interact import (POST_INTERACTION_PAD_TO_MUL, DotInteraction, cdiv, dot_ba
                        self_batched_mul, triangular_slice, triangular_slice_back, up_to_mul_of)
 from .shapes import (KAGGLE_EMBEDDING_SIZES, TERABYTE_EMBEDDING_SIZES, WORKLOADS, step_chunk, step_parts, step_pipeline, zipf_perm,
                      zipf_rows)
-from .update import (ADAGrad, Descent, RowwiseADAGrad, SparseEmbeddingUpdate, SparseIndexer, SplitDescent, maplookup_pullback,
-                     merge_split, split_f32, update_)
+from .update import (ADAGrad, Descent, RowwiseADAGrad, SparseEmbeddingUpdate, SparseIndexer, SplitDescent, StochasticDescent,
+                     maplookup_pullback, merge_split, philox4x32_10, split_f32, sr_bits, sr_round, update_)
 
 __all__ = [
     "BoundsError", "DLRMError", "LibraryMissing", "DefaultStrategy", "EmbeddingTableSet", "PackedIndices",
@@ -32,4 +32,5 @@ __all__ = [
     "dot_interaction", "rrule_dot_interaction", "triangular_slice", "triangular_slice_back", "rrule_triangular_slice",
     "self_batched_mul", "rrule_self_batched_mul", "step_pipeline", "step_chunk", "step_parts", "zipf_perm", "HipTables", "LazyLookup",
     "LazyGrad", "DeferredUpdate", "ADAGrad", "RowwiseADAGrad", "SplitDescent", "split_f32", "merge_split",
+    "StochasticDescent", "sr_round", "sr_bits", "philox4x32_10",
 ]

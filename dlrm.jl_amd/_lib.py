@@ -100,6 +100,12 @@ SIGNATURES = {
     "dlrm_split_sgd_destroy": (_i32, [_vp]),
     "dlrm_split_sgd_update": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _i64, _i64,
                                      _f32]),
+    "dlrm_sr_sgd_create": (_i32, [_vp, _vp, _i64, _pp]),
+    "dlrm_sr_sgd_destroy": (_i32, [_vp]),
+    "dlrm_sr_sgd_update": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _i64, _i64,
+                                  _f32]),
+    "dlrm_sr_sgd_seek": (_i32, [_vp, _vp, _i64]),
+    "dlrm_sr_sgd_step": (_i32, [_vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),
     "dlrm_bce_head":(_i32, [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dlrm_relu_bwd_bias_workspace": (_i32, [_i32, _i32, _pi64, _pi64]),
     "dlrm_relu_bwd_bias": (_i32, [_vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),

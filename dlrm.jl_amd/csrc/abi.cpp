@@ -61,9 +61,15 @@ struct dlrm_adagrad : StatePtrs<float> {
 };
 // The low halves of split-bf16 tables
 struct dlrm_split_sgd : StatePtrs<uint16_t> {};
+// Stochastically rounded SGD on bf16 tables: no per-row state, a seed and one device word, the step
+struct dlrm_sr_sgd : StateDims {
+    uint64_t seed = 0;
+    uint64_t* d_step = nullptr;
+};
 
 // The rule that stepped a split build's once-hit rows inside the step backward, and its bit of dlrm_indexer_state
-enum { kRuleDescent = 0, kRuleSplit = 1, kRuleAdagrad = 2, kRuleRowwise = 3 };
+enum { kRuleDescent = 0, kRuleSplit = 1, kRuleAdagrad = 2, kRuleRowwise = 3,
+       kRuleStochastic = 4 /* (an update rule only: no step backward carries it) */ };
 static const unsigned kRuleBits[4] = {0u, DLRM_IX_SINGLES_SPLIT, DLRM_IX_SINGLES_ADAGRAD, DLRM_IX_SINGLES_ROWWISE};
 
 struct dlrm_indexer {
@@ -1160,6 +1166,71 @@ int dlrm_split_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dl
     if (rc) return rc;
     return launch_split_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_ptr, tb->T, tb->D, lookups,
                                   (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr, sa);
+}
+
+// (an atomic add rounds every addend, not the row's step; a step backward's once-hit rows were rounded to nearest,
+// whatever its rule, and this rule completes none)
+static const UpdateRule kSrUpdate = {"dlrm_sr_sgd_update", false, "the optimizer was",
+                                     "the rule rounds each row's complete step once", "another rule", kRuleStochastic};
+
+int dlrm_sr_sgd_create(dlrm_ctx* ctx, const dlrm_tables* tb, int64_t seed, dlrm_sr_sgd** out) {
+    CHECK_ARG(ctx && tb && out, "dlrm_sr_sgd_create: null argument");
+    *out = nullptr;
+    CHECK_ARG(tb->dtype == DLRM_BF16, "dlrm_sr_sgd_create: stochastic rounding is of bf16 tables (fp32: nothing to round)");
+    // the Philox counter holds the table in 16 bits and the column's block of four in 16 bits
+    CHECK_ARG(tb->T <= 65536 && (tb->D + 3) / 4 <= 65536, "dlrm_sr_sgd_create: %d tables of dim %d (at most 65536 tables, "
+              "dim / 4 at most 65536)", tb->T, tb->D);
+    dlrm_sr_sgd* op = new (std::nothrow) dlrm_sr_sgd();
+    if (!op) return DLRM_E_NOMEM;
+    op->T = tb->T;
+    op->D = tb->D;
+    op->seed = (uint64_t)seed;
+    int rc = hip_set(ctx);
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMalloc((void**)&op->d_step, sizeof(uint64_t)), "hipMalloc(sr step)");
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMemset(op->d_step, 0, sizeof(uint64_t)), "hipMemset(sr step)");
+    if (rc != DLRM_OK) {
+        if (op->d_step) (void)hipFree(op->d_step);
+        delete op;
+        return rc;
+    }
+    *out = op;
+    return DLRM_OK;
+}
+
+int dlrm_sr_sgd_destroy(dlrm_sr_sgd* op) {
+    if (!op) return DLRM_OK;
+    if (op->d_step) (void)hipFree(op->d_step);
+    delete op;
+    return DLRM_OK;
+}
+
+int dlrm_sr_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_sr_sgd* op, dlrm_indexer* ix, unsigned flags,
+                       const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
+                       const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset, float lr) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_sr_sgd_update: null ctx/tables/optimizer/indexer");
+    CHECK_ARG(tb->dtype == DLRM_BF16, "dlrm_sr_sgd_update: stochastic rounding is of bf16 tables (fp32: nothing to round)");
+    SinglesArgs sa;
+    bool atomic;
+    const int rc = update_prologue(ctx, tb, ix, kSrUpdate, op, flags, indices, itype, table_stride, index_base, batch,
+                                   lookups, grad, grad_dtype, grad_ld, grad_offset, &sa, &atomic);
+    if (rc) return rc;
+    return launch_sr_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, op->seed, op->d_step, tb->T, tb->D, lookups,
+                               (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr, sa);
+}
+
+int dlrm_sr_sgd_seek(dlrm_ctx* ctx, dlrm_sr_sgd* op, int64_t step) {
+    CHECK_ARG(ctx && op, "dlrm_sr_sgd_seek: null ctx/optimizer");
+    const int rc = hip_set(ctx);
+    if (rc) return rc;
+    return launch_sr_step_set(ctx, op->d_step, (uint64_t)step);
+}
+
+int dlrm_sr_sgd_step(dlrm_ctx* ctx, dlrm_sr_sgd* op, uint64_t* out) {
+    CHECK_ARG(ctx && op && out, "dlrm_sr_sgd_step: null ctx/optimizer/out");
+    int rc = hip_set(ctx);
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMemcpy(out, op->d_step, sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy(sr step)");
+    return rc;
 }
 
 // ----------------------------------------------------------------------- training step

@@ -88,10 +88,13 @@ __device__ __forceinline__ void add_vec(float* acc, const typename Vec<GT>::type
 //   SplitDescent    W = bits(hi << 16 | lo);  W' = fmaf(-lr, G, W);  hi' = bits(W') >> 16, lo' = bits(W') & 0xffff
 //                   (hi = the bf16 table's element, lo = a uint16 [nrows][D] state row: the table holds
 //                   the truncated high half of an fp32 master weight, the step is Descent's on fp32)
+//   StochasticDescent  W' = fmaf(-lr, G, w);  w = sr_bf16(W', R): Descent on bf16 tables whose store rounds W' up
+//                   or down with probability proportional to its distance to each bf16 neighbour (no state; R =
+//                   16 Philox bits of (seed, step, table, row, column), below)
 // A rule holds its parameters, its state's row address (state_row), its once-hit positions per lane group
 // (singles_ppg), the any-D kernels' write of one column (scalar_write) and the MODEs and table element types
 // it is instantiated for (kCarriesBuild, kBuildWithApply, kF32Tables).  The vector items below still branch on kState (0 none,
-// 1 a state row per table row, 2 a state word, 3 a row of low halves): written once over a per-rule row type
+// 1 a state row per table row, 2 a state word, 3 a row of low halves, 4 none and a stochastic store): written once over a per-rule row type
 // they no longer compiled to the same code.  The state is loaded where the table row
 // is (beside the grad rows: these items are bound by dependent round trips) and written once, with the row.
 
@@ -182,7 +185,7 @@ struct Descent {
     template <typename G> static constexpr int singles_ppg() { return G::SPPG; }
     static constexpr int scalar_threads(int D) { return D; }  // any-D kernels: threads per row
     template <typename TT, typename F>
-    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float*, int64_t, int, int c, F&& colsum) const {
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float*, int64_t, int, int c, int, F&& colsum) const {
         row[c] = from_f32<TT>(__builtin_fmaf(-lr, colsum(c), to_f32(row[c])));
     }
 };
@@ -203,7 +206,7 @@ struct Adagrad {
     template <typename G> static constexpr int singles_ppg() { return fewer_singles(G::SPPG, G::NE == 4 ? 4 : 2); }
     static constexpr int scalar_threads(int D) { return D; }
     template <typename TT, typename F>
-    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float* __restrict__ st, int64_t r, int D, int c,
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float* __restrict__ st, int64_t r, int D, int c, int,
                                                  F&& colsum) const {
         const float g = colsum(c);
         float a = st[r * D + c], w = to_f32(row[c]);
@@ -232,7 +235,7 @@ struct RowwiseAdagrad {
     static constexpr int scalar_threads(int) { return 1; }  // (two passes over the row's sums)
     // (c = 0: the thread has the whole row; the squares in column order, then the step)
     template <typename TT, typename F>
-    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float* __restrict__ st, int64_t r, int D, int,
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float* __restrict__ st, int64_t r, int D, int, int,
                                                  F&& colsum) const {
         float ss = 0.0f;
         for (int k = 0; k < D; ++k) {
@@ -264,7 +267,7 @@ struct SplitDescent {
     template <typename G> static constexpr int singles_ppg() { return G::NE == 4 && G::LPR == 16 ? G::SPPG / 2 : G::SPPG; }
     static constexpr int scalar_threads(int D) { return D; }
     template <typename TT, typename F>
-    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, uint16_t* __restrict__ st, int64_t r, int D, int c,
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, uint16_t* __restrict__ st, int64_t r, int D, int c, int,
                                                  F&& colsum) const {
         static_assert(sizeof(TT) == 2, "split rows live in bf16 tables");
         const float g = colsum(c);
@@ -275,12 +278,103 @@ struct SplitDescent {
     }
 };
 
-// ---- a chunk, by one lane group (lane v of LPR; gl0 = the group's first lane in the wave)
+// ---- stochastic rounding (StochasticDescent).  sr_bf16(W', R), u = bits(W'): an Inf or a NaN goes through
+// f32_to_bf16 (NaN keeps its quiet bit), anything else is (u + R) >> 16 with R uniform in [0, 65536): the
+// magnitude rounds away from zero with probability (u & 0xffff) / 65536 exactly, a W' that is a bf16 value is
+// kept, and a finite W' above the largest finite bf16 can reach Inf, its upper neighbour.
+__device__ __forceinline__ uint16_t sr_bf16(float w, uint32_t R) {
+    const uint32_t u = __float_as_uint(w);
+    if ((u & 0x7f800000u) == 0x7f800000u) return f32_to_bf16(w);
+    return (uint16_t)((u + R) >> 16);
+}
+// Philox4x32-10 (Salmon et al., SC'11): counter c[4], key (k0, k1); c becomes the output block
+__device__ __forceinline__ void philox4x32_10(uint32_t* c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c[0]), l0 = 0xD2511F53u * c[0];
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c[2]), l1 = 0xCD9E8D57u * c[2];
+        c[0] = h1 ^ c[1] ^ k0;
+        c[1] = l1;
+        c[2] = h0 ^ c[3] ^ k1;
+        c[3] = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// R of element (table t, row r, column c) at step s under the seed is a function of those alone -- not of the
+// indexer's form, its chunk limit or parts, or the launch or lane that writes the row: key = (seed lo, seed hi),
+// counter = (r, t << 16 | c >> 2, s lo, s hi), and column c takes the low 16 bits of output word c & 3.  One block
+// serves four consecutive columns, generated at the write (after the loads: nothing is held across the gather).
+// The step is one device word the optimizer handle owns: every launch of an update call reads it (load_step, once
+// per workgroup into scalars) and a one-thread launch after the call's last adds one, in stream order.  No per-row
+// state, so the rule alternates freely with Descent on the same tables.
+struct StochasticDescent {
+    float lr;
+    uint32_t k0, k1;       // the seed's halves
+    const uint64_t* step;  // the handle's step word
+    uint32_t s0, s1;       // its value, by load_step
+    typedef float State;
+    static constexpr int kState = 4;
+    static constexpr bool kCarriesBuild = false;  // MODE 0 / 1 only (sr_sgd.hip): no fused step with this rule
+    static constexpr bool kBuildWithApply = false;
+    static constexpr bool kF32Tables = false;  // fp32 tables: nothing to round
+    __device__ __forceinline__ float* base(int) const { return nullptr; }
+    template <int D> __device__ static __forceinline__ float* state_row(float*, uint32_t) { return nullptr; }
+    // Descent's SPPG -- but for fp32 gradient rows of 16 vectors (D = 64), whose MODE 1 kernel spilt 2 registers
+    // at SPPG = 8 with the Philox rounds at the write: half as many there (as the split rule)
+    template <typename G> static constexpr int singles_ppg() { return fewer_singles(G::SPPG, G::NE == 4 && G::LPR == 16 ? 2 : 1); }
+    static constexpr int scalar_threads(int D) { return D; }
+    __device__ __forceinline__ void load_step() {
+        const uint64_t s = ldg<uint64_t>(step);
+#if defined(__HIP_DEVICE_COMPILE__)
+        s0 = __builtin_amdgcn_readfirstlane((uint32_t)s);
+        s1 = __builtin_amdgcn_readfirstlane((uint32_t)(s >> 32));
+#else  // host pass of the device code: never executed
+        s0 = (uint32_t)s;
+        s1 = (uint32_t)(s >> 32);
+#endif
+    }
+    // the store of NE (4 or 8) elements f from column c0 (a multiple of 4) of row r of table t, at dst
+    template <int NE>
+    __device__ __forceinline__ void store(uint16_t* dst, int t, uint32_t r, int c0, const float* f) const {
+        typename Halves<NE>::type o;
+#pragma unroll
+        for (int k = 0; k < NE / 4; ++k) {
+            uint32_t x[4] = {r, ((uint32_t)t << 16) | (uint32_t)((c0 >> 2) + k), s0, s1};
+            philox4x32_10(x, k0, k1);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[k * 4 + e] = sr_bf16(f[k * 4 + e], x[e] & 0xffffu);
+        }
+        stg<typename Halves<NE>::type>(dst, o);
+    }
+    template <typename TT, typename F>
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float*, int64_t r, int, int c, int t,
+                                                 F&& colsum) const {
+        static_assert(sizeof(TT) == 2, "stochastic rounding is of bf16 tables");
+        const float w = __builtin_fmaf(-lr, colsum(c), to_f32(row[c]));
+        uint32_t x[4] = {(uint32_t)r, ((uint32_t)t << 16) | (uint32_t)(c >> 2), s0, s1};
+        philox4x32_10(x, k0, k1);
+        stg<uint16_t>(row + c, sr_bf16(w, x[c & 3] & 0xffffu));
+    }
+};
+// a rule's write of NE weights f at column c0 of row r (at `row`) of table t
+template <typename TT, int NE, typename R>
+__device__ __forceinline__ void rule_store(const R& rule, TT* row, int t, uint32_t r, int c0, const float* f) {
+    if constexpr (R::kState == 4) {
+        static_assert(sizeof(TT) == 2, "stochastic rounding is of bf16 tables");
+        rule.template store<NE>((uint16_t*)row + c0, t, r, c0, f);
+    } else {
+        store_row<TT, NE>(row, c0, f);
+    }
+}
+
+// ---- a chunk, by one lane group (lane v of LPR; gl0 = the group's first lane in the wave; t = the table)
 template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_chunk(const int32_t* __restrict__ perm, const int4& a, const int4& b,
                                           TT* __restrict__ table, typename R::State* __restrict__ st,
                                           const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L,
-                                          const R& rule, int v, int gl0) {
+                                          const R& rule, int v, int gl0, int t) {
     typedef ApplyGeom<GT, VPR> G;
     constexpr int NE = G::NE, D = G::D, LPR = G::LPR;
     constexpr int KX = (kChunk - kChunkInline + LPR - 1) / LPR;  // perm loads per lane (long chunks)
@@ -372,7 +466,7 @@ __device__ __forceinline__ void run_chunk(const int32_t* __restrict__ perm, cons
     for (int j = 0; j < G::VPL; ++j) {
 #pragma unroll
         for (int e = 0; e < NE; ++e) tv[j][e] = __builtin_fmaf(-lr, acc[j][e], tv[j][e]);
-        store_row<TT, NE>(row, (v + j * 64) * NE, tv[j]);
+        rule_store<TT, NE>(rule, row, t, (uint32_t)a.z, (v + j * 64) * NE, tv[j]);
     }
 }
 
@@ -464,7 +558,7 @@ __device__ __forceinline__ void run_singles(const SinglesArgs& sa, int64_t cap, 
 #pragma unroll
                             for (int e = 0; e < NE; ++e) tv[u][j][e] = __builtin_fmaf(-lr, g[j][e], tv[u][j][e]);
                         }
-                        store_row<TT, NE>(table + (int64_t)ru[u] * D, (v + j * 64) * NE, tv[u][j]);
+                        rule_store<TT, NE>(rule, table + (int64_t)ru[u] * D, t, ru[u], (v + j * 64) * NE, tv[u][j]);
                     }
                 }
             }
@@ -509,15 +603,15 @@ struct SliceLds {
 // ---- a slice of a hot segment, by the whole workgroup: pos = its positions (perm entries),
 // len of them, `row` the table row, `ns` the slices of its segment, its partial row at
 // part_me, the segment's first at part_first (slot spacing pdim), `cnt` the segment's arrival
-// counter (zero at rest).
-// The row's write by the first D/4 threads (G = the thread's four sums, rw its four weights, sw its
+// counter (zero at rest); (t, r) = the table and the row's index, for a rule whose store depends on them.
+// The row's write by the first D/4 threads (row r of table t; G = the thread's four sums, rw its four weights, sw its
 // four accumulators or the row's word); every thread of the workgroup calls it.  wsum_read: other
 // waves may still be reading sm.wsum (the row-wise wave totals of D > 256 reuse it).
 // (The split rule: rh / rl = the thread's four high and low halves, as bits, in place of rw / sw.)
 template <typename TT, typename R, int D>
 __device__ __forceinline__ void slice_write(const R& rule, const f32x4& G, float* rw, float* sw, u16x4& rh, u16x4& rl,
                                             TT* __restrict__ row, typename R::State* __restrict__ srow, SliceLds<D>& sm,
-                                            bool wsum_read) {
+                                            bool wsum_read, int t, uint32_t r) {
     const int tid = threadIdx.x;
     const bool mine = tid < D / 4;
     const float g[4] = {G[0], G[1], G[2], G[3]};
@@ -554,7 +648,7 @@ __device__ __forceinline__ void slice_write(const R& rule, const f32x4& G, float
     if (mine) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) rw[e] = __builtin_fmaf(-lr, g[e], rw[e]);
-        store_row<TT, 4>(row, tid * 4, rw);
+        rule_store<TT, 4>(rule, row, t, r, tid * 4, rw);
     }
 }
 
@@ -562,7 +656,8 @@ template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int len, TT* __restrict__ row,
                                            typename R::State* __restrict__ srow, int ns, float* part_me, const float* part_first,
                                            int64_t pdim, int32_t* cnt_p, const GT* __restrict__ gbase, int64_t grad_ld,
-                                           const FastDiv& L, const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
+                                           const FastDiv& L, const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm, int t,
+                                           uint32_t r) {
     typedef ApplyGeom<GT, VPR> G;
     constexpr int NE = G::NE, D = G::D, LPR = G::LPR, NG = G::NG;
     constexpr int SPG = (kHotSlice + NG - 1) / NG;  // positions per lane group
@@ -651,7 +746,7 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
                 store_row<TT, 4>(row, tid * 4, rw);
             }
         } else {
-            slice_write<TT, R, D>(rule, sum, rw, sw, rh, rl, row, srow, sm, true);
+            slice_write<TT, R, D>(rule, sum, rw, sw, rh, rl, row, srow, sm, true, t, r);
         }
         __syncthreads();  // sm reused by this workgroup's next item
         return;
@@ -696,7 +791,7 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
                     if (k0 + u < ns) s += q[u];
             }
         }
-        slice_write<TT, R, D>(rule, s, rw, sw, rh, rl, row, srow, sm, false);  // (sm.wsum: read before the barriers above)
+        slice_write<TT, R, D>(rule, s, rw, sw, rh, rl, row, srow, sm, false, t, r);  // (sm.wsum: read before the barriers above)
         if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();  // sm reused by this workgroup's next item
@@ -707,7 +802,7 @@ __device__ __forceinline__ void slice_body(const int32_t* __restrict__ pos, int 
 template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_slice(const IndexerDev& ix, int vt, int sl, const int4& sd, TT* __restrict__ table,
                                           typename R::State* __restrict__ st, const GT* __restrict__ gbase, int64_t grad_ld,
-                                          const FastDiv& L, const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
+                                          const FastDiv& L, const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm, int t) {
     constexpr int D = ApplyGeom<GT, VPR>::D;
     const int64_t off = (int64_t)vt * ix.cap;
     const int4 hd = ix.hot[off + sd.w];
@@ -716,7 +811,7 @@ __device__ __forceinline__ void run_slice(const IndexerDev& ix, int vt, int sl, 
     slice_body<TT, GT, VPR, R>(ix.perm + off + sd.x, sd.y - sd.x, table + (int64_t)(uint32_t)sd.z * D,
                                R::template state_row<D>(st, (uint32_t)sd.z), ns, pbase + (int64_t)sl * ix.pdim,
                                pbase + (int64_t)hd.w * ix.pdim, ix.pdim, ix.hot_cnt + off + sd.w, gbase, grad_ld, L,
-                               rule, sm);
+                               rule, sm, t, (uint32_t)sd.z);
 }
 
 // ---- hot slice k of the item map (one 32-B record: IndexerDev::slice_rec); k and its segment's
@@ -725,12 +820,12 @@ template <typename TT, typename GT, int VPR, typename R>
 __device__ __forceinline__ void run_slice_rec(const IndexerDev& ix, int k, int first, const int4& r0, const int4& r1,
                                               TT* __restrict__ table, typename R::State* __restrict__ st,
                                               const GT* __restrict__ gbase, int64_t grad_ld, const FastDiv& L,
-                                              const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm) {
+                                              const R& rule, SliceLds<ApplyGeom<GT, VPR>::D>& sm, int t) {
     constexpr int D = ApplyGeom<GT, VPR>::D;
     slice_body<TT, GT, VPR, R>(ix.perm + r0.x, r0.y - r0.x, table + (int64_t)(uint32_t)r0.z * D,
                                R::template state_row<D>(st, (uint32_t)r0.z), r1.x, ix.partial + (int64_t)k * ix.pdim,
                                ix.partial + (int64_t)first * ix.pdim, ix.pdim, ix.hot_cnt + first, gbase, grad_ld, L,
-                               rule, sm);
+                               rule, sm, t, (uint32_t)r0.z);
 }
 
 }  // namespace dlrm

@@ -1,7 +1,7 @@
 // apply_kernel.hpp -- the apply launch of update! (sgd_apply_kernel over apply.hpp's work items), its
 // any-D fallback kernels and their launchers, by update rule.  update.hip instantiates Descent
-// (every MODE), adagrad.hip and adagrad_rowwise.hip the Adagrad rules, split_sgd.hip the split rule (MODE 0
-// and 1), and split_step.hip, adagrad_step.hip and adagrad_rowwise_step.hip those three rules' build-carrying
+// (every MODE), adagrad.hip and adagrad_rowwise.hip the Adagrad rules, split_sgd.hip the split rule and sr_sgd.hip
+// the stochastic rule (MODE 0 and 1), and split_step.hip, adagrad_step.hip and adagrad_rowwise_step.hip those three rules' build-carrying
 // launches (MODE 2 / 3 / 5): they compile side by side.
 #pragma once
 #include "apply.hpp"
@@ -46,7 +46,7 @@ static inline int wave_big_kind(const PrepArgs& pa) {
 // workgroups of a build (4 parts each)
 __host__ __device__ __forceinline__ int prep_groups(const PrepArgs& pa) { return (pa.T << pa.ix.vshift) / kWaveParts; }
 
-// R: the update rule (apply.hpp: Descent, Adagrad, RowwiseAdagrad, SplitDescent).
+// R: the update rule (apply.hpp: Descent, Adagrad, RowwiseAdagrad, SplitDescent, StochasticDescent).
 template <typename TT, typename GT, int VPR, int MODE, typename R = Descent>
 __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev ix, TableDesc* __restrict__ tabs, int T_,
                                                                   int L, const GT* __restrict__ grad, int64_t grad_ld,
@@ -82,6 +82,7 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
         return;
 #endif
     }
+    if constexpr (R::kState == 4) rule.load_step();  // (the stochastic rule's step word, once per workgroup)
     // a bounds error raised since the last dlrm_check_bounds (the lookup or the indexer build of
     // this step): the reference's gather throws before update!, so no table row is written.  (The
     // error word is loaded with the item counts, one round trip for both.)
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
                 t = tc >> ix.vshift;
             }
             run_chunk<TT, GT, VPR, R>(pbase, ca, cb, (TT*)tabs[t].data, rule.base(t), grad + grad_offset + (int64_t)t * D,
-                                      grad_ld, Ld, rule, v, lane - v);
+                                      grad_ld, Ld, rule, v, lane - v, t);
             APPLY_END();
             continue;
         }
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
             const int4 r0 = ix.slice_rec[2 * (int64_t)r], r1 = ix.slice_rec[2 * (int64_t)r + 1];
             const int t = r0.w >> ix.vshift;
             run_slice_rec<TT, GT, VPR, R>(ix, item, item - (r - r1.y), r0, r1, (TT*)tabs[t].data, rule.base(t),
-                                          grad + grad_offset + (int64_t)t * D, grad_ld, Ld, rule, sm);
+                                          grad + grad_offset + (int64_t)t * D, grad_ld, Ld, rule, sm, t);
             APPLY_END();
             continue;
         }
@@ -217,7 +218,7 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
         const int4 sd = ix.hot_slice[(int64_t)th * ix.cap + sl];
         const int t = th >> ix.vshift;
         run_slice<TT, GT, VPR, R>(ix, th, sl, sd, (TT*)tabs[t].data, rule.base(t), grad + grad_offset + (int64_t)t * D,
-                                  grad_ld, Ld, rule, sm);
+                                  grad_ld, Ld, rule, sm, t);
         APPLY_END();
     }
 #ifdef DLRM_PHASE
@@ -238,6 +239,7 @@ __global__ __launch_bounds__(256) void sgd_chunks_scalar(IndexerDev ix, TableDes
         return;
     }
     if (*err) return;
+    if constexpr (R::kState == 4) rule.load_step();
     const int t = blockIdx.y;
     const int nchunks = ix.counts[(int64_t)t * 8 + CNT_C];
     const int64_t off = ix.part_off(t);
@@ -248,7 +250,7 @@ __global__ __launch_bounds__(256) void sgd_chunks_scalar(IndexerDev ix, TableDes
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int cid = (int)(e / W);
         const int4 cd = ix.chunks[2 * (off + cid)];
-        rule.scalar_write(table + (int64_t)(uint32_t)cd.z * D, st, (int64_t)(uint32_t)cd.z, D, (int)(e % W), [&](int c) {
+        rule.scalar_write(table + (int64_t)(uint32_t)cd.z * D, st, (int64_t)(uint32_t)cd.z, D, (int)(e % W), t >> ix.vshift, [&](int c) {
             float acc = 0.0f;
             for (int i = cd.x; i < cd.y; ++i)
                 acc += to_f32(grad[(int64_t)(ix.perm[off + i] / L) * grad_ld + grad_offset + (int64_t)(t >> ix.vshift) * D + c]);
@@ -262,6 +264,7 @@ __global__ __launch_bounds__(256) void sgd_hot_scalar(IndexerDev ix, TableDesc* 
                                                       const GT* __restrict__ grad, int64_t grad_ld,
                                                       int64_t grad_offset, R rule, const unsigned* __restrict__ err) {
     if (*err) return;
+    if constexpr (R::kState == 4) rule.load_step();
     const int t = blockIdx.y;
     const int nhot = ix.counts[(int64_t)t * 8 + CNT_H];
     const int64_t off = ix.part_off(t);
@@ -272,7 +275,7 @@ __global__ __launch_bounds__(256) void sgd_hot_scalar(IndexerDev ix, TableDesc* 
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int h = (int)(e / W);
         const int4 hd = ix.hot[off + h];
-        rule.scalar_write(table + (int64_t)(uint32_t)hd.z * D, st, (int64_t)(uint32_t)hd.z, D, (int)(e % W), [&](int c) {
+        rule.scalar_write(table + (int64_t)(uint32_t)hd.z * D, st, (int64_t)(uint32_t)hd.z, D, (int)(e % W), t >> ix.vshift, [&](int c) {
             float acc = 0.0f;
             for (int i = hd.x; i < hd.y; ++i)
                 acc += to_f32(grad[(int64_t)(ix.perm[off + i] / L) * grad_ld + grad_offset + (int64_t)(t >> ix.vshift) * D + c]);
@@ -287,6 +290,7 @@ __global__ __launch_bounds__(256) void sgd_singles_scalar(SinglesArgs sa, int64_
                                                           int64_t grad_offset, R rule,
                                                           const unsigned* __restrict__ err) {
     if (*err) return;
+    if constexpr (R::kState == 4) rule.load_step();
     const int t = blockIdx.y;
     const int W = R::scalar_threads(D);  // threads per position
     const int64_t total = (int64_t)sa.N * W;
@@ -297,7 +301,7 @@ __global__ __launch_bounds__(256) void sgd_singles_scalar(SinglesArgs sa, int64_
         if (!sa.single[(int64_t)t * cap + p]) continue;
         const int64_t r = load_index(sa.idx, sa.itype, (int64_t)t * sa.tstride + p) - sa.base;
         if (r < 0 || r >= tabs[t].nrows) continue;
-        rule.scalar_write(table + r * D, st, r, D, (int)(e % W), [&](int c) {
+        rule.scalar_write(table + r * D, st, r, D, (int)(e % W), t, [&](int c) {
             return 0.0f + to_f32(grad[(int64_t)(p / L) * grad_ld + grad_offset + (int64_t)t * D + c]);
         });
     }

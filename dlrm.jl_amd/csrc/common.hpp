@@ -443,6 +443,13 @@ int launch_rowwise_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc*
 int launch_split_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint16_t* const* lo,
                            int T, int D, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
                            int64_t grad_offset, float lr, const SinglesArgs& singles);
+// the same apply with the stochastic rule (apply.hpp StochasticDescent) on bf16 tables, then the advance of the
+// handle's device step word `step` by a one-thread launch (sr_sgd.hip); launch_sr_step_set: step = value, on the
+// context's stream.
+int launch_sr_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint64_t seed,
+                        uint64_t* step, int T, int D, int L, int64_t N, const void* grad, int gdtype,
+                        int64_t grad_ld, int64_t grad_offset, float lr, const SinglesArgs& singles);
+int launch_sr_step_set(dlrm_ctx* ctx, uint64_t* step, uint64_t value);
 // the training step's split apply over the fp32 dt (split_step.hip): with `prep` and no once-hit items the
 // next batch's build rides on the launch (MODE 2 / 3 / 5), otherwise launch_split_sgd_apply and, with `prep`,
 // the build's own launch.

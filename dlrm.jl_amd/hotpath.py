@@ -25,11 +25,13 @@ forward writes only `out` and the backward rebuilds T from x and the gathered ta
 the update that follows -- which saves ys's write and keeps the step's HBM traffic at what
 the math needs.  Turn it on to read `ys` (e.g. for parity checks against maplookup).
 
-`opt` (an `ADAGrad`, `RowwiseADAGrad` or `SplitDescent`; default None = `Descent(lr)`): the tables are
-stepped with that optimizer.  The fused step pair is Descent-only (on split-bf16 tables it would round
+`opt` (an `ADAGrad`, `RowwiseADAGrad`, `SplitDescent` or `StochasticDescent`; default None = `Descent(lr)`): the
+tables are stepped with that optimizer.  The fused step pair is Descent-only (on split-bf16 tables it would round
 the high halves), so this selects the operator path: the fused forward, the gather backward (which
-writes every dt row and builds the indexer in its launch), then dlrm_adagrad_update(PREBUILT) or
-dlrm_split_sgd_update(PREBUILT) -- three launches, no host synchronisation, graph-capturable.
+writes every dt row and builds the indexer in its launch), then dlrm_adagrad_update(PREBUILT),
+dlrm_split_sgd_update(PREBUILT) or dlrm_sr_sgd_update(PREBUILT) -- three launches (the stochastic rule: and the
+one-thread advance of its step), no host synchronisation, graph-capturable.  `StochasticDescent` has this route
+only: `fused_step`, `adagrad_step` and `pipeline` are refused with it.
 
 `fused_step=True` with `opt=SplitDescent(η)` on bfloat16 tables: the fused step pair with the split rule
 (dlrm_step_fwd, then dlrm_split_step_bwd / dlrm_split_step_bwd_prepare): once-hit rows are stepped inside
@@ -50,7 +52,7 @@ from .embedding import EmbeddingTableSet, PackedIndices
 from .interact import interaction_sizes
 from .runtime import dtype_code, ptr, require_device
 from .shapes import APPLY_MAX_N
-from .update import SparseIndexer, SplitDescent, _AdagradBase, _StatefulOpt
+from .update import SparseIndexer, SplitDescent, StochasticDescent, _AdagradBase, _StatefulOpt
 
 
 class HotPath:
@@ -58,11 +60,23 @@ class HotPath:
                  overlap_indexer=None, pad_to=1, fused=True, materialize_ys=None, pipeline=False, chunk=None,
                  parts=None, opt=None, fused_step=False, adagrad_step=False):
         if opt is not None and not isinstance(opt, _StatefulOpt):
-            raise TypeError("HotPath: opt is an ADAGrad, RowwiseADAGrad or SplitDescent (None: Descent(lr))")
+            raise TypeError("HotPath: opt is an ADAGrad, RowwiseADAGrad, SplitDescent or StochasticDescent "
+                            "(None: Descent(lr))")
         if opt is not None and not deterministic:
             raise ValueError(f"HotPath: {type(opt).__name__} needs the deterministic update")
         self.opt = opt
         self.ts = tables if isinstance(tables, EmbeddingTableSet) else EmbeddingTableSet(tables)
+        if isinstance(opt, StochasticDescent):
+            # the operator route only: dlrm_*_step_bwd has no instantiation with the stochastic store
+            if fused_step or adagrad_step:
+                raise ValueError("HotPath: StochasticDescent has no fused step (fused_step / adagrad_step are the split "
+                                 "and Adagrad rules'): its once-hit rows are rounded in the apply launch, not in the "
+                                 "step backward")
+            if pipeline not in (False, 0, None):
+                raise ValueError("HotPath: pipeline must be None with opt=StochasticDescent: the pipelined steps need "
+                                 "a fused step, which this rule does not have")
+            if self.ts.dtype != torch.bfloat16:
+                raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not {self.ts.dtype}")
         # the fused step pair with the split rule (dlrm_split_step_bwd); without it opt= takes the operator path
         self.split_step = bool(fused_step)
         if self.split_step and not isinstance(opt, SplitDescent):

@@ -523,6 +523,59 @@ function split_state(opt::HipSplitDescent, tables::AbstractVector{<:HipEmbedding
     end
 end
 
+#####
+##### Stochastic rounding: HipStochasticDescent (Flux.Descent on bf16 rows, unbiased, no extra memory).
+#####
+
+"""
+    HipStochasticDescent(η = 0.1; seed = 0)
+
+`Flux.Descent(η)` for 2-byte (bf16) `HipEmbedding` tables whose store rounds stochastically: the fp32 result
+of every touched element's step, `fma(-η, G, w)`, is rounded up or down with probability proportional to its
+distance to each bf16 neighbour, so the stored weight equals the fp32 step in expectation and steps below half
+an ulp accumulate instead of vanishing.  No memory beside the table (`HipSplitDescent` is exact and takes 2
+more bytes per element).  The random bits are Philox4x32-10 of (seed, step, table, row, column) alone; the step
+is a device counter per table vector, 0 at first use and one more after every `update!` (`sr_seek!` sets it,
+`sr_step` reads it).  There is no per-row state, so the rule may be alternated freely with `Descent` on the
+same tables.  The operator route only: a fused context takes it after a pullback that wrote every gradient
+row (a context without a learning rate).
+"""
+mutable struct HipStochasticDescent
+    eta::Float32
+    seed::UInt64
+    state::IdDict{Any,Any}     # tables => dlrm_sr_sgd handle (it owns the step)
+end
+HipStochasticDescent(η = 0.1; seed = 0) = HipStochasticDescent(Float32(η), UInt64(seed), IdDict{Any,Any}())
+
+"The dlrm_sr_sgd handle of `tables` (created at first use, step 0)."
+function sr_state(opt::HipStochasticDescent, tables::AbstractVector{<:HipEmbedding})
+    get!(opt.state, tables) do
+        ctx = first(tables).data.ctx
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ctx, ccall((:dlrm_sr_sgd_create, libdlrm), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}),
+                         ctx.ptr, tableset(tables), reinterpret(Int64, opt.seed), out))
+        out[]
+    end
+end
+
+"The next `update!` of `tables` uses `step` (asynchronous, in stream order)."
+function sr_seek!(opt::HipStochasticDescent, tables::AbstractVector{<:HipEmbedding}, step::Integer)
+    ctx = first(tables).data.ctx
+    check(ctx, ccall((:dlrm_sr_sgd_seek, libdlrm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64),
+                     ctx.ptr, sr_state(opt, tables), reinterpret(Int64, UInt64(step))))
+    return nothing
+end
+
+"The step the next `update!` of `tables` will use (synchronises)."
+function sr_step(opt::HipStochasticDescent, tables::AbstractVector{<:HipEmbedding})
+    ctx = first(tables).data.ctx
+    out = Ref{UInt64}(0)
+    check(ctx, ccall((:dlrm_sr_sgd_step, libdlrm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{UInt64}),
+                     ctx.ptr, sr_state(opt, tables), out))
+    return out[]
+end
+
 # The C update of a rule with state: (ctx, tables, optimizer handle, indexer, flags, indices, gradient).
 function _rule_update(opt::AbstractHipADAGrad, ctx, tables, ixptr, flags, idxptr, stride, batch, lookups, dtptr, ld, off)
     _, h = adagrad_state(opt, tables)
@@ -535,6 +588,15 @@ end
 function _rule_update(opt::HipSplitDescent, ctx, tables, ixptr, flags, idxptr, stride, batch, lookups, dtptr, ld, off)
     _, h = split_state(opt, tables)
     ccall((:dlrm_split_sgd_update, libdlrm), Cint,
+          (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cuint, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint,
+           Ptr{Cvoid}, Cint, Int64, Int64, Cfloat),
+          ctx.ptr, tableset(tables), h, ixptr, flags, idxptr, DLRM_I32, stride, 1,
+          batch, lookups, dtptr, DLRM_F32, ld, off, opt.eta)
+end
+
+function _rule_update(opt::HipStochasticDescent, ctx, tables, ixptr, flags, idxptr, stride, batch, lookups, dtptr, ld, off)
+    h = sr_state(opt, tables)
+    ccall((:dlrm_sr_sgd_update, libdlrm), Cint,
           (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cuint, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint,
            Ptr{Cvoid}, Cint, Int64, Int64, Cfloat),
           ctx.ptr, tableset(tables), h, ixptr, flags, idxptr, DLRM_I32, stride, 1,
@@ -602,11 +664,11 @@ function _step_bwd_prepare(ctx, st, nix, next, flags)
           size(st.dt, 1), ctx.lr, nix.ptr, next.data.ptr, flags)
 end
 
-# update!(HipADAGrad / HipRowwiseADAGrad / HipSplitDescent, tables, grads, indexers): the unfused path
+# update!(HipADAGrad / HipRowwiseADAGrad / HipSplitDescent / HipStochasticDescent, tables, grads, indexers): the unfused path
 # builds the indexer in the call; after a fused step's pullback that wrote every dt row (a fused context
 # without a learning rate) the forward's split indexer is reused (_fused_update!).
 function EmbeddingTables.update!(
-    opt::Union{AbstractHipADAGrad,HipSplitDescent}, tables::AbstractVector{<:HipEmbedding{Static{D}}},
+    opt::Union{AbstractHipADAGrad,HipSplitDescent,HipStochasticDescent}, tables::AbstractVector{<:HipEmbedding{Static{D}}},
     grads::AbstractVector{<:SparseEmbeddingUpdate}, indexers; num_splits = 8, nthreads = Threads.nthreads()
 ) where {D}
     length(grads) == length(tables) || throw(ArgumentError("one SparseEmbeddingUpdate per table"))
@@ -906,7 +968,7 @@ function _fused_update!(opt, st, tables)
     ctx.adagrad === nothing || (opt.eta == ctx.lr && opt.epsilon == ctx.eps) ||
         throw(ArgumentError("the pullback stepped the once-hit rows with η = $(ctx.lr), ϵ = $(ctx.eps); update! got " *
                             "$(opt.eta), $(opt.epsilon)"))
-    if opt isa Union{AbstractHipADAGrad,HipSplitDescent} && ctx.split === nothing && ctx.adagrad === nothing
+    if opt isa Union{AbstractHipADAGrad,HipSplitDescent,HipStochasticDescent} && ctx.split === nothing && ctx.adagrad === nothing
         # every dt row is needed: the forward's split indexer, the once-hit rows as singles items
         st.bwd === :once_hit_applied &&
             throw(ArgumentError("the pullback already stepped the once-hit rows with Descent (η = $(ctx.lr)) and left " *

@@ -47,7 +47,7 @@ import torch
 
 from . import _lib
 from .embedding import EmbeddingTableSet, PackedIndices, PreallocationStrategy, as_table_set
-from .update import Descent, SparseEmbeddingUpdate, SplitDescent, _AdagradBase, _StatefulOpt
+from .update import Descent, SparseEmbeddingUpdate, SplitDescent, StochasticDescent, _AdagradBase, _StatefulOpt
 
 
 class HipTables:
@@ -60,16 +60,28 @@ class HipTables:
     tables written.  opt: a SplitDescent(η) on bfloat16 tables, the split analogue of lr=η: the pullback
     runs the split rule's backward (dlrm_split_step_bwd) and update! with that same optimizer object runs
     or defers its apply.  opt: an ADAGrad(η, ε) or RowwiseADAGrad(η, ε) likewise (dlrm_adagrad_step_bwd): update!
-    takes that optimizer object, with the η and ε it had here."""
+    takes that optimizer object, with the η and ε it had here.  opt: a StochasticDescent(η, seed) on bfloat16
+    tables takes the operator route (the rule has no fused step): the pullback writes every gradient row and
+    update! with that optimizer object steps every row (dlrm_sr_sgd_update), at once."""
 
     def __init__(self, tables, *, lr=None, index_base=1, defer_update=True, opt=None):
         self._ts = as_table_set(tables) if not isinstance(tables, EmbeddingTableSet) else tables
         if opt is not None:
-            if not isinstance(opt, (SplitDescent, _AdagradBase)):
-                raise TypeError("HipTables: opt is a SplitDescent, an ADAGrad or a RowwiseADAGrad (Descent: lr=eta)")
-            if lr is not None and float(lr) != opt.eta:
-                raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}")
-            lr = opt.eta
+            if not isinstance(opt, (SplitDescent, StochasticDescent, _AdagradBase)):
+                raise TypeError("HipTables: opt is a SplitDescent, a StochasticDescent, an ADAGrad or a RowwiseADAGrad "
+                                "(Descent: lr=eta)")
+            if isinstance(opt, StochasticDescent):
+                # the operator route: the pullback writes every dt row and update! steps every row (lr stays None)
+                if lr is not None:
+                    raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}: the stochastic rule has no fused step, "
+                                     "so the pullback steps no row (lr must be None)")
+                if self._ts.dtype != torch.bfloat16:
+                    raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not "
+                                     f"{self._ts.dtype}")
+            else:
+                if lr is not None and float(lr) != opt.eta:
+                    raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}")
+                lr = opt.eta
         self.opt = opt
         # an Adagrad rule's (η, ε) as given here: every launch of these tables' steps uses them (the pullback's
         # and a deferred apply's alike), and update! refuses the optimizer object once its own differ
@@ -147,10 +159,13 @@ class HipTables:
         from .hotpath import HotPath
         hp = self._hp.get(batch)
         if hp is None:
+            stochastic = isinstance(self.opt, StochasticDescent)  # (the operator route: a plain step engine)
             hp = HotPath(self._ts, batch, 1, lr=0.0 if self.lr is None else self.lr, index_base=self.index_base,
-                         opt=self.opt, fused_step=isinstance(self.opt, SplitDescent),
+                         opt=None if stochastic else self.opt, fused_step=isinstance(self.opt, SplitDescent),
                          adagrad_step=isinstance(self.opt, _AdagradBase))
             hp.rule_params = self._opt_params
+            if stochastic:
+                self.opt.handle_of(self._ts)  # the handle and its step word, allocated before any graph capture
             if not hp.step_api:
                 raise ValueError("HipTables: this table set has no training-step kernels (deterministic, one-hot)")
             self._hp[batch] = hp
@@ -269,9 +284,11 @@ def update_lazy(opt, tables, grads, *, check_bounds=None):
     else the launch and a synchronising check; True: run it now and check; False: no check."""
     if not isinstance(opt, (Descent, _StatefulOpt)):
         raise TypeError("update_ implements Descent (plain SGD, the optimizer DLRM.jl trains with), ADAGrad, "
-                        "RowwiseADAGrad and SplitDescent")
+                        "RowwiseADAGrad, SplitDescent and StochasticDescent")
     if isinstance(opt, SplitDescent) and tables._ts.dtype != torch.bfloat16:
         raise ValueError(f"SplitDescent needs bfloat16 tables (the high halves), not {tables._ts.dtype}")
+    if isinstance(opt, StochasticDescent) and tables._ts.dtype != torch.bfloat16:
+        raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not {tables._ts.dtype}")
     lz = grads[0].lazy
     if len(grads) != len(tables) or any(g.lazy is not lz or g.table_index != t for t, g in enumerate(grads)):
         raise ValueError("update_ expects the per-table views of one maplookup pullback")

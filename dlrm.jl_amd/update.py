@@ -66,7 +66,8 @@ class _StatefulOpt:
     def state_of(self, tables):
         """The state tensors of `tables` (a table set), one per table: fp32 [nrows][D] accumulators
         (ADAGrad), fp32 [nrows] row accumulators (RowwiseADAGrad) or int16 [nrows][D] low halves
-        (SplitDescent).  Write into them to preset the state."""
+        (SplitDescent); none for StochasticDescent, whose state is the handle's step.  Write into them to
+        preset the state."""
         return self._entry(tables)[1]
 
     def handle_of(self, tables):
@@ -181,6 +182,126 @@ class SplitDescent(_StatefulOpt):
 
     def __repr__(self):
         return f"SplitDescent({self.eta})"
+
+
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) in numpy: `counter` = four uint32 arrays (or scalars) that
+    broadcast together, `key` = two; returns the four output words as uint32 arrays."""
+    import numpy as np
+    c = [np.asarray(x, dtype=np.uint64) & _M32 for x in counter]
+    k = [int(key[0]) & _M32, int(key[1]) & _M32]
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k[0]), p1 & np.uint64(_M32),
+             (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k[1]), p0 & np.uint64(_M32)]
+        k = [(k[0] + 0x9E3779B9) & _M32, (k[1] + 0xBB67AE85) & _M32]
+    shape = np.broadcast(*c).shape
+    return [np.broadcast_to(x, shape).astype(np.uint32) for x in c]
+
+
+def sr_bits(shape, seed, step, table, row0=0):
+    """The 16 random bits R of every element of rows row0.. of table `table` at `step` under `seed`, as a
+    uint32 array of `shape` = (rows, columns): key = the seed's halves, counter = (row, table << 16 |
+    column >> 2, the step's halves), column c takes the low 16 bits of output word c & 3."""
+    import numpy as np
+    n, d = shape
+    seed, step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+    rows = (np.arange(n, dtype=np.uint64) + np.uint64(row0))[:, None]
+    blocks = np.arange((d + 3) // 4, dtype=np.uint64)[None, :]
+    out = philox4x32_10([rows, (np.uint64(int(table)) << np.uint64(16)) | blocks, step & _M32, step >> 32],
+                        [seed & _M32, seed >> 32])
+    r = np.stack(out, axis=-1).reshape(n, -1)[:, :d]  # (word c & 3 of block c >> 2)
+    return r & np.uint32(0xFFFF)
+
+
+def sr_round(w_f32, seed, step, table, *, row0=0, bits=None):
+    """The stochastic rule's store, restated in numpy: the bfloat16 bit patterns (uint16 array) that
+    StochasticDescent writes for the fp32 results `w_f32` ([rows][D] float32 numpy array or CPU tensor: the
+    W' of every element of rows row0.. of table `table`) at `step` under `seed`.  u = bits(W'): Inf and NaN
+    round to nearest (a NaN keeps its quiet bit), anything else is (u + R) >> 16.  bits: R given instead of
+    drawn (tests)."""
+    import numpy as np
+    w = w_f32.detach().cpu().numpy() if isinstance(w_f32, torch.Tensor) else np.asarray(w_f32)
+    if w.dtype != np.float32 or w.ndim != 2:
+        raise TypeError("sr_round expects a two-dimensional float32 array")
+    u = np.ascontiguousarray(w).view(np.uint32)
+    r = sr_bits(w.shape, seed, step, table, row0) if bits is None else np.asarray(bits, dtype=np.uint32) & np.uint32(0xFFFF)
+    special = (u & np.uint32(0x7F800000)) == np.uint32(0x7F800000)
+    nan = special & ((u & np.uint32(0x007FFFFF)) != 0)
+    sr = ((u.astype(np.uint64) + r) >> np.uint64(16)).astype(np.uint16)
+    nearest = np.where(nan, (u >> np.uint32(16)) | np.uint32(0x40), u >> np.uint32(16)).astype(np.uint16)  # (Inf: exact)
+    return np.where(special, nearest, sr)
+
+
+class StochasticDescent(_StatefulOpt):
+    """Flux.Descent(η) on bfloat16 tables with a stochastically rounded store (dlrm_sr_sgd_*): the fp32 result
+    of every touched element's step is rounded up or down with probability proportional to its distance to
+    each bfloat16 neighbour, so the stored weight equals the fp32 step in expectation and updates below half
+    an ulp accumulate instead of vanishing -- at no memory beside the table (SplitDescent is exact and takes 2
+    more bytes per element).
+
+    The random bits are a function of (seed, step, table, row, column) alone (Philox4x32-10; `sr_round`
+    restates a step on the host).  The step is a counter on the device, per table set: 0 at first use, one
+    more after every update (a captured update advances it on every replay); `seek(tables, step)` sets it and
+    `step_of(tables)` reads it (synchronising).  There is no per-row state, so the rule may be alternated
+    freely with Descent on the same tables.  The operator route only: `HotPath` / `HipTables` take it without
+    the fused step (`pipeline=None`)."""
+
+    def __init__(self, eta=0.1, seed=0):
+        super().__init__()
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise TypeError(f"StochasticDescent: seed is an integer in [0, 2^64), not {type(seed).__name__}")
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("StochasticDescent: seed is an integer in [0, 2^64)")
+        self.eta = float(eta)
+        self.seed = seed
+
+    def _entry(self, tables):
+        ts = as_table_set(tables)
+        key = tuple(t.data.data_ptr() for t in ts)
+        ent = self._state.get(key)
+        if ent is None:
+            if ts.dtype != torch.bfloat16:
+                raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not {ts.dtype}")
+            h = ctypes.c_void_p()
+            ts.ctx.check(ts.ctx.lib.dlrm_sr_sgd_create(ts.ctx.bind(), ts.handle, _as_i64(self.seed), ctypes.byref(h)))
+            ent = self._state[key] = (ts, [], h)  # (no state tensors: the handle holds the step)
+        return ent
+
+    def _destroy(self, lib, handle):
+        lib.dlrm_sr_sgd_destroy(handle)
+
+    def launch(self, ts, indexer, flags, idx, index_base, grad, grad_offset):
+        ctx = ts.ctx
+        return ctx.lib.dlrm_sr_sgd_update(ctx.bind(), ts.handle, self.handle_of(ts), indexer.handle, flags,
+                                          ptr(idx.data), idx.itype, idx.stride, index_base, idx.B, idx.L, ptr(grad),
+                                          dtype_code(grad.dtype), grad.stride(0), grad_offset, self.eta)
+
+    def seek(self, tables, step):
+        """The next update of `tables` uses `step` (asynchronous, in stream order)."""
+        ts, _, h = self._entry(tables)
+        if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
+            raise ValueError("StochasticDescent.seek: step is an integer in [0, 2^64)")
+        ts.ctx.check(ts.ctx.lib.dlrm_sr_sgd_seek(ts.ctx.bind(), h, _as_i64(step)))
+
+    def step_of(self, tables):
+        """The step the next update of `tables` will use (synchronises)."""
+        ts, _, h = self._entry(tables)
+        out = ctypes.c_uint64()
+        ts.ctx.check(ts.ctx.lib.dlrm_sr_sgd_step(ts.ctx.bind(), h, ctypes.byref(out)))
+        return out.value
+
+    def __repr__(self):
+        return f"StochasticDescent({self.eta}, seed={self.seed})"
+
+
+def _as_i64(u):
+    """The 64 bits of an unsigned value as the int64 the C ABI passes them in."""
+    return u - 2 ** 64 if u >= 2 ** 63 else u
 
 
 def _tables_dtype(tables):
@@ -376,7 +497,7 @@ def update_(opt, tables, grads, indexers=None, *, num_splits=8, nthreads=12, ind
         tables = tables.ts
     if not isinstance(opt, (Descent, _StatefulOpt)):
         raise TypeError("update_ implements Descent (plain SGD, the optimizer DLRM.jl trains with), ADAGrad, "
-                        "RowwiseADAGrad and SplitDescent")
+                        "RowwiseADAGrad, SplitDescent and StochasticDescent")
     stateful = isinstance(opt, _StatefulOpt)
     if isinstance(opt, _AdagradBase) and not deterministic:
         raise ValueError("update_ with an Adagrad optimizer is deterministic only: an atomic add never holds the "
@@ -387,6 +508,13 @@ def update_(opt, tables, grads, indexers=None, *, num_splits=8, nthreads=12, ind
                              "weight cannot carry into the other")
         if _tables_dtype(tables) != torch.bfloat16:
             raise ValueError(f"SplitDescent needs bfloat16 tables (the high halves), not {_tables_dtype(tables)}")
+    if isinstance(opt, StochasticDescent):
+        if not deterministic:
+            raise ValueError("update_ with StochasticDescent is deterministic only: the rule rounds each row's "
+                             "complete step once, an atomic add would round every addend")
+        if _tables_dtype(tables) != torch.bfloat16:
+            raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not "
+                             f"{_tables_dtype(tables)}")
     ts = as_table_set(tables)
     if len(grads) != len(ts):
         raise ValueError(f"{len(grads)} gradients for {len(ts)} tables")

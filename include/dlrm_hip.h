@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DLRM_HIP_ABI_VERSION 1
+#define DLRM_HIP_ABI_VERSION 2
 
 typedef enum {
     DLRM_OK = 0,
@@ -422,6 +422,60 @@ int dlrm_split_sgd_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_split_sgd* op
                           int index_base, int batch, int lookups,
                           const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset,
                           float lr);
+
+/* ---- stochastic rounding: update!(Descent(lr), ...) on bf16 tables, unbiased, with no memory
+ * beside the table.  dlrm_sgd_update on bf16 tables rounds every written element to nearest, so a
+ * step below half a bf16 ulp of the weight is dropped every time; the split tables above keep it
+ * at 2 more bytes per element.  Here the fp32 result of the step is rounded up or down with
+ * probability proportional to its distance to each bf16 neighbour: the stored weight equals the
+ * fp32 step in expectation, and small updates accumulate instead of vanishing.
+ *
+ * For a table row r of table t touched by the batch, G[c] is dlrm_sgd_update's fp32 gradient sum
+ * (same indexer form, same order; a once-hit row's is 0.0f + g).  Then
+ *     W'      = fmaf(-lr, G[c], bf16_to_f32(w[r][c]))        (dlrm_sgd_update's expression)
+ *     w[r][c] = sr_bf16(W', R)
+ * sr_bf16(W', R), u = bits(W'): when u's exponent is all ones (Inf, NaN) the round-to-nearest
+ * conversion of dlrm_sgd_update (a NaN keeps its quiet bit); otherwise (u + R) >> 16 with R a
+ * uniform 16-bit integer.  So the magnitude rounds away from zero with probability
+ * (u & 0xffff) / 65536 exactly, a W' that is a bf16 value is kept, and a finite W' above the
+ * largest finite bf16 can round to Inf, its upper neighbour.
+ *
+ * R is a function of (seed, step, t, r, c) and of nothing else -- not of the indexer's form, its
+ * chunk limit or parts per table, or of which launch or lane writes the row: Philox4x32-10 with
+ * key = (seed low 32 bits, seed high 32 bits) and counter = (r as uint32, (t << 16) | (c >> 2),
+ * step low 32 bits, step high 32 bits); column c takes the low 16 bits of output word c & 3.
+ * Tables with more than 65536 tables or dim / 4 > 65536 return DLRM_E_ARG at create.
+ *
+ * The step: the handle owns one 64-bit device word, zero at creation.  Update call number k since
+ * creation (or since the last seek) uses step k in every launch of the call; the word then advances
+ * by one on the device, in stream order, with no host synchronisation -- so a captured update
+ * advances it on every replay.  It advances when the call returned DLRM_OK and launched (also when
+ * a raised bounds flag suppressed the writes), not on an argument or state error.
+ * dlrm_sr_sgd_seek sets it (asynchronous, on the context's stream); dlrm_sr_sgd_step synchronises
+ * the stream and reads it.  seed and step are 64 bits taken as unsigned (passed as int64_t: the
+ * bit pattern is what counts).
+ *
+ * Each touched row is written exactly once, untouched rows keep their bits, the result is bitwise
+ * reproducible for a given (seed, step), and a set bounds flag (the context's, or a prepared
+ * build's) leaves the tables unwritten.  dlrm_sr_sgd_update: DLRM_UPDATE_PREBUILT is honoured;
+ * DLRM_UPDATE_ATOMIC returns DLRM_E_UNSUPPORTED; tables that are not DLRM_BF16 (there is nothing
+ * to round), or a handle created for another table count / dim, return DLRM_E_ARG; an indexer in
+ * state DLRM_IX_SINGLES_DONE, with any rule's mark, returns DLRM_E_STATE and writes nothing (a step
+ * backward has already written the once-hit rows rounded to nearest); a split indexer whose
+ * singles are not done is taken whole, once-hit rows included.  The rule keeps no per-row state,
+ * so it may be alternated freely with dlrm_sgd_update on the same tables.  Launches neither
+ * allocate nor synchronise beyond what dlrm_sgd_update does, so the call is graph-capturable.
+ * dlrm_sr_sgd_destroy of NULL returns 0.  There is no fused training step with this rule yet. */
+typedef struct dlrm_sr_sgd dlrm_sr_sgd; /* the seed and the device step word */
+int dlrm_sr_sgd_create(dlrm_ctx* ctx, const dlrm_tables* tables, int64_t seed, dlrm_sr_sgd** out);
+int dlrm_sr_sgd_destroy(dlrm_sr_sgd* opt);
+int dlrm_sr_sgd_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_sr_sgd* opt, dlrm_indexer* indexer,
+                       unsigned flags, const void* indices, int itype, int64_t table_stride,
+                       int index_base, int batch, int lookups,
+                       const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset,
+                       float lr);
+int dlrm_sr_sgd_seek(dlrm_ctx* ctx, dlrm_sr_sgd* opt, int64_t step);
+int dlrm_sr_sgd_step(dlrm_ctx* ctx, dlrm_sr_sgd* opt, uint64_t* out);
 
 /* ---- training step: fused forms of the four operators --------------------------------
  * One train! iteration of the sparse half of the model (src/train/train.jl:215-227 and

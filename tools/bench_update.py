@@ -1,8 +1,12 @@
 """The embedding update alone, by optimizer: Descent (dlrm_sgd_update), ADAGrad and RowwiseADAGrad
-(dlrm_adagrad_update) and SplitDescent (dlrm_split_sgd_update), each with DLRM_UPDATE_PREBUILT on one
-indexer built once, over a full dt.  SplitDescent runs on a bf16 copy of the tables (the truncated high
-halves, the low halves beside them); on an fp32 workload a Descent-bf16 leg steps a second bf16 copy, so
-the split rule is timed against Descent on fp32 tables and on bf16 tables in the same run.
+(dlrm_adagrad_update), SplitDescent (dlrm_split_sgd_update) and StochasticDescent (dlrm_sr_sgd_update), each with
+DLRM_UPDATE_PREBUILT on one indexer built once, over a full dt.  SplitDescent and StochasticDescent each run on a
+bf16 copy of the tables (the split rule: the truncated high halves, the low halves beside them); on an fp32
+workload a Descent-bf16 leg steps another bf16 copy, so the three rules of bf16 tables -- Descent, StochasticDescent
+and SplitDescent -- are timed side by side in the same run (bf16_ratio: a leg's time to the Descent leg on bf16
+tables).  The stochastic rule moves Descent's bytes: its ratio is the cost of Philox at the write sites plus the
+one-thread launch that advances its step, and the sr-step-launch leg times such a one-thread launch alone
+(dlrm_sr_sgd_seek, the same kernel shape, in the same captured chain of 200).
 
 Each leg is a captured graph of 200 launches, replayed until the timed window exceeds 0.5 s; the
 legs alternate, five repeats.  One JSON line per run: per shape and leg the median / min / max us
@@ -49,10 +53,16 @@ def bench_shape(pkg, dev, name):
     if dtype == torch.float32:
         b16 = pkg.EmbeddingTableSet([t.data.clone() for t in hi])
         opts["Descent-bf16"] = (pkg.Descent(1e-6), b16, pkg.maplookup_pullback(D, b16, p, dt))
+    sr = pkg.EmbeddingTableSet([t.data.clone() for t in hi])
+    sr_opt = pkg.StochasticDescent(1e-6, seed=7)
+    opts["StochasticDescent"] = (sr_opt, sr, pkg.maplookup_pullback(D, sr, p, dt))
+    opts["sr-step-launch"] = (sr_opt, sr, None)  # (no update: the one-thread launch alone)
     graphs = {}
     s = torch.cuda.Stream()
     for leg, (opt, tabs, gr_views) in opts.items():
         def launch(opt=opt, tabs=tabs, gr_views=gr_views):
+            if gr_views is None:
+                return opt.seek(tabs, 0)
             pkg.update_(opt, tabs, gr_views, ix, index_base=0, prebuilt=True, check_bounds=False)
         launch()  # the state and every first-use allocation, before the capture
         torch.cuda.synchronize()
@@ -84,14 +94,15 @@ def bench_shape(pkg, dev, name):
     ts.ctx.check_bounds()
     grad_bytes = T * B * L * D * 4 if L == 1 else T * B * D * 4
     state_bytes = {"Descent": 0, "ADAGrad": 2 * unique * D * 4, "RowwiseADAGrad": 2 * unique * 4,
-                   "SplitDescent": 2 * unique * D * 2, "Descent-bf16": 0}
-    table_esize = {"SplitDescent": 2, "Descent-bf16": 2}
+                   "SplitDescent": 2 * unique * D * 2, "Descent-bf16": 0, "StochasticDescent": 0}
+    table_esize = {"SplitDescent": 2, "Descent-bf16": 2, "StochasticDescent": 2}
     out = {"unique_rows": unique, "legs": {}}
     for leg in opts:
         v = us[leg]
         out["legs"][leg] = {"us_median": round(statistics.median(v), 3), "us_min": round(min(v), 3),
                             "us_max": round(max(v), 3),
-                            "bytes": grad_bytes + 2 * unique * D * table_esize.get(leg, esize) + state_bytes[leg]}
+                            "bytes": 8 if leg == "sr-step-launch" else
+                            grad_bytes + 2 * unique * D * table_esize.get(leg, esize) + state_bytes[leg]}
     base = out["legs"]["Descent"]
     out["descent_spread"] = round((base["us_max"] - base["us_min"]) / base["us_median"], 4)
     for leg in opts:
@@ -99,6 +110,9 @@ def bench_shape(pkg, dev, name):
             continue
         out["legs"][leg]["time_ratio"] = round(out["legs"][leg]["us_median"] / base["us_median"], 4)
         out["legs"][leg]["byte_ratio"] = round(out["legs"][leg]["bytes"] / base["bytes"], 4)
+    b16_base = out["legs"]["Descent-bf16" if dtype == torch.float32 else "Descent"]["us_median"]
+    for leg in ("StochasticDescent", "SplitDescent"):
+        out["legs"][leg]["bf16_ratio"] = round(out["legs"][leg]["us_median"] / b16_base, 4)
     return out
 
 
