@@ -69,8 +69,9 @@ struct dlrm_sr_sgd : StateDims {
 
 // The rule that stepped a split build's once-hit rows inside the step backward, and its bit of dlrm_indexer_state
 enum { kRuleDescent = 0, kRuleSplit = 1, kRuleAdagrad = 2, kRuleRowwise = 3,
-       kRuleStochastic = 4 /* (an update rule only: no step backward carries it) */ };
-static const unsigned kRuleBits[4] = {0u, DLRM_IX_SINGLES_SPLIT, DLRM_IX_SINGLES_ADAGRAD, DLRM_IX_SINGLES_ROWWISE};
+       kRuleStochastic = 4 /* (dlrm_sr_step_bwd: the indexer also remembers the handle, singles_sr) */ };
+static const unsigned kRuleBits[5] = {0u, DLRM_IX_SINGLES_SPLIT, DLRM_IX_SINGLES_ADAGRAD, DLRM_IX_SINGLES_ROWWISE,
+                                      DLRM_IX_SINGLES_STOCHASTIC};
 
 struct dlrm_indexer {
     dlrm_ctx* ctx = nullptr;
@@ -87,6 +88,8 @@ struct dlrm_indexer {
     bool prepared = false;  // built by dlrm_step_bwd_prepare for the next dlrm_step_fwd (not yet consumed)
     bool singles_done = false;  // a split backward has applied this build's once-hit rows already
     int singles_rule = 0;  // ... with this rule (kRule*): Descent, or the rule of dlrm_split_step_bwd / dlrm_adagrad_step_bwd
+                           // / dlrm_sr_step_bwd
+    const dlrm_sr_sgd* singles_sr = nullptr;  // kRuleStochastic: the handle whose seed and step rounded those rows
     // device words for the bounds errors of builds that may run beside a step's write-deciding
     // kernels, which read the ctx's flag to decide whether to write (raising there would be a race,
     // ADVICE r5): [0] dlrm_indexer_prepare (a side-stream build beside the current step; cleared
@@ -168,6 +171,7 @@ static void record_build(dlrm_indexer* ix, bool split, const void* indices, int 
     ix->prepared = false;
     ix->singles_done = false;
     ix->singles_rule = kRuleDescent;
+    ix->singles_sr = nullptr;
     ix->dev.has_map = 0;  // (set by dlrm_step_bwd_prepare, whose wave build writes the item map)
     ix->dev.build_err = nullptr;  // (set by dlrm_indexer_prepare)
     ix->indices = indices;
@@ -751,6 +755,7 @@ static int indexer_carve(dlrm_ctx* ctx, dlrm_indexer* ix, int parts) {
     ix->bytes = total;
     ix->built = ix->prepared = ix->singles_done = false;
     ix->singles_rule = kRuleDescent;
+    ix->singles_sr = nullptr;
     ix->dev.has_map = 0;
     ix->dev.build_err = nullptr;
     return DLRM_OK;
@@ -1085,10 +1090,17 @@ static int update_prologue(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, con
         if (ix->singles_done && ix->singles_rule == kRuleDescent && r.singles_done)
             return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_step_bwd) already stepped this build's "
                             "once-hit rows with %s", r.fn, r.singles_done);
-        if (ix->singles_done && ix->singles_rule >= kRuleAdagrad && r.rule != ix->singles_rule)
+        if (ix->singles_done && (ix->singles_rule == kRuleAdagrad || ix->singles_rule == kRuleRowwise) &&
+            r.rule != ix->singles_rule)
             return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_adagrad_step_bwd) already stepped this build's "
                             "once-hit rows with the %s Adagrad rule", r.fn,
                             ix->singles_rule == kRuleRowwise ? "row-wise" : "element-wise");
+        // (the stochastic rule: the handle too -- another one has another seed or step)
+        if (ix->singles_done && ix->singles_rule == kRuleStochastic &&
+            (r.rule != kRuleStochastic || ix->singles_sr != op))
+            return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_sr_step_bwd) already stepped this build's "
+                            "once-hit rows with the stochastic rule%s", r.fn,
+                            r.rule == kRuleStochastic ? " of another handle" : "");
     } else {
         rc = dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, lookups);
         if (rc) return rc;
@@ -1168,8 +1180,9 @@ int dlrm_split_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dl
                                   (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr, sa);
 }
 
-// (an atomic add rounds every addend, not the row's step; a step backward's once-hit rows were rounded to nearest,
-// whatever its rule, and this rule completes none)
+// (an atomic add rounds every addend, not the row's step; another rule's step backward rounded its once-hit rows to
+// nearest, and this rule completes none of those -- but dlrm_sr_step_bwd's backward stepped them with this rule, and
+// then the update with the same handle takes the repeated rows that are left)
 static const UpdateRule kSrUpdate = {"dlrm_sr_sgd_update", false, "the optimizer was",
                                      "the rule rounds each row's complete step once", "another rule", kRuleStochastic};
 
@@ -1321,8 +1334,9 @@ int dlrm_step_fwd(dlrm_ctx* ctx, const dlrm_tables* tb, dlrm_indexer* ix, const 
 }
 
 // The once-hit rule of a training step's backward and apply: Descent (dlrm_step_bwd), the split rule on
-// split-bf16 tables (dlrm_split_step_bwd) or a sparse Adagrad rule (dlrm_adagrad_step_bwd; element-wise or
-// row-wise by its handle).  An indexer remembers which one stepped its once-hit rows (singles_rule), and only
+// split-bf16 tables (dlrm_split_step_bwd), a sparse Adagrad rule (dlrm_adagrad_step_bwd; element-wise or
+// row-wise by its handle) or the stochastic rule on bf16 tables (dlrm_sr_step_bwd).  An indexer remembers which one
+// stepped its once-hit rows (singles_rule; the stochastic rule: and with which handle, singles_sr), and only
 // the same rule's apply completes that backward.
 struct StepRule {
     const char* fn;              // the entry point, for the messages
@@ -1330,11 +1344,13 @@ struct StepRule {
     dlrm_split_sgd* op = nullptr;   // kRuleSplit: the low halves
     dlrm_adagrad* ada = nullptr;    // kRuleAdagrad / kRuleRowwise: the state
     float eps = 0.0f;               // ... and the rule's epsilon
+    dlrm_sr_sgd* sr = nullptr;      // kRuleStochastic: the seed and the step word
 };
 // who stepped a build's once-hit rows, for the messages
-static const char* const kRuleNames[4] = {"dlrm_step_bwd (Descent)", "dlrm_split_step_bwd (the split rule)",
+static const char* const kRuleNames[5] = {"dlrm_step_bwd (Descent)", "dlrm_split_step_bwd (the split rule)",
                                           "dlrm_adagrad_step_bwd (the element-wise Adagrad rule)",
-                                          "dlrm_adagrad_step_bwd (the row-wise Adagrad rule)"};
+                                          "dlrm_adagrad_step_bwd (the row-wise Adagrad rule)",
+                                          "dlrm_sr_step_bwd (the stochastic rule)"};
 
 static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* indices, int itype,
                          int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
@@ -1344,8 +1360,14 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
     CHECK_ARG(ctx && tb && ix, "%s: null ctx/tables/indexer", rule.fn);
     dlrm_split_sgd* const op = rule.op;
     dlrm_adagrad* const ada = rule.ada;
+    dlrm_sr_sgd* const sr = rule.sr;
     int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, 1);
     if (rc) return rc;
+    if (sr) {  // (dlrm_sr_sgd_update's argument errors)
+        CHECK_ARG(tb->dtype == DLRM_BF16, "%s: stochastic rounding is of bf16 tables (fp32: nothing to round)", rule.fn);
+        CHECK_ARG(sr->T == tb->T && sr->D == tb->D, "%s: the optimizer was created for %d tables of dim %d", rule.fn,
+                  sr->T, sr->D);
+    }
     if (op) {  // (dlrm_split_sgd_update's argument errors)
         CHECK_ARG(tb->dtype == DLRM_BF16, "%s: split tables are bf16 (the high halves)", rule.fn);
         CHECK_ARG(op->T == tb->T && op->D == tb->D, "%s: the low halves were created for %d tables of dim %d", rule.fn,
@@ -1370,7 +1392,8 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
     // state rows as 16-B vectors; an Adagrad rule: the feature sizes whose backward has its once-hit write)
     const bool split_bwd = ix->split && step_split_supported(tb->aligned16, tb->T, tb->dtype, d, x, x_ld) &&
                            (!op || op->aligned16) &&
-                           (!ada || ((ada->rowwise || ada->aligned16) && adagrad_step_bwd_supported(ada->rowwise, tb->dtype, tb->T, d)));
+                           (!ada || ((ada->rowwise || ada->aligned16) && adagrad_step_bwd_supported(ada->rowwise, tb->dtype, tb->T, d))) &&
+                           (!sr || sr_step_bwd_supported(tb->T, d));
     if (flags & DLRM_STEP_APPLY_ONLY) {
         // the apply of a split build only completes a backward that stepped the once-hit rows
         if (split_bwd && !ix->singles_done)
@@ -1379,6 +1402,10 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
         if (ix->singles_done && ix->singles_rule != rule.kind)
             return ctx_fail(ctx, DLRM_E_STATE, "%s(APPLY_ONLY): this build's once-hit rows were stepped by %s", rule.fn,
                             kRuleNames[ix->singles_rule]);
+        // ... and, the stochastic rule, with this handle's seed and step
+        if (ix->singles_done && sr && ix->singles_sr != sr)
+            return ctx_fail(ctx, DLRM_E_STATE, "%s(APPLY_ONLY): this build's once-hit rows were stepped with another "
+                            "dlrm_sr_sgd handle", rule.fn);
         rc = DLRM_OK;
     } else if (split_bwd) {
         // a second backward on one build would step its once-hit rows twice
@@ -1388,7 +1415,10 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
                             "dlrm_step_fwd)", rule.fn);
         CHECK_ARG((uintptr_t)dx % 16 == 0 && (uintptr_t)dt % 16 == 0 && dx_ld % 4 == 0 && dt_ld % 4 == 0,
                   "%s: dx and dt must be 16-B aligned with leading dimensions divisible by 4", rule.fn);
-        if (ada)
+        if (sr)  // (reads the handle's step word; the launch that runs the apply advances it)
+            rc = launch_sr_step_bwd(ctx, tb->d_desc, tb->T, indices, itype, table_stride, index_base, d, batch, x, x_ld,
+                                    dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, lr, sr->seed, sr->d_step);
+        else if (ada)
             rc = launch_adagrad_step_bwd(ctx, tb->d_desc, tb->T, tb->dtype, indices, itype, table_stride, index_base, d,
                                          batch, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, lr, rule.eps,
                                          ada->rowwise, ada->d_ptr);
@@ -1399,6 +1429,7 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
         if (rc == DLRM_OK) {
             ix->singles_done = true;
             ix->singles_rule = rule.kind;
+            ix->singles_sr = sr;
         }
     } else {
         rc = launch_interact_bwd_gather(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
@@ -1409,6 +1440,9 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
     // them as chunks)
     const SinglesArgs sa{(ix->split && !split_bwd) ? ix->dev.single : nullptr, indices, itype, table_stride,
                          index_base, batch};
+    if (sr)  // (... and the one-thread advance of the step word, after the launch that read it)
+        return launch_sr_step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, sr->seed, sr->d_step, tb->T, tb->D,
+                                    (int64_t)batch, dt, dt_ld, d, lr, sa, prep);
     if (op)
         return launch_split_step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_ptr, tb->T, tb->D,
                                        (int64_t)batch, dt, dt_ld, d, lr, sa, prep);
@@ -1448,7 +1482,8 @@ static int step_bwd_prepare_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* i
                          step_split_supported(tb->aligned16, tb->T, tb->dtype, tb->D, x, x_ld) &&
                          (!rule.op || rule.op->aligned16) &&
                          (!rule.ada || ((rule.ada->rowwise || rule.ada->aligned16) &&
-                                        adagrad_step_bwd_supported(rule.ada->rowwise, tb->dtype, tb->T, tb->D)));
+                                        adagrad_step_bwd_supported(rule.ada->rowwise, tb->dtype, tb->T, tb->D))) &&
+                         (!rule.sr || sr_step_bwd_supported(tb->T, tb->D));
     if (!inapply)  // no pipelined form for this shape: the plain step (the next forward builds)
         return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
                              padding, dx, dx_ld, dt, dt_ld, lr, flags, nullptr, rule);
@@ -1525,6 +1560,32 @@ int dlrm_adagrad_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* 
     return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
                                  padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags,
                                  adagrad_step_rule(op, eps));
+}
+
+// ---- the same step with the stochastic rule on bf16 tables in the backward's once-hit write and in the apply; the
+// handle's step word is read by both launches and advanced after the one that runs the apply
+static StepRule sr_step_rule(dlrm_sr_sgd* op) {
+    StepRule r{"dlrm_sr_step_bwd", kRuleStochastic};
+    r.sr = op;
+    return r;
+}
+
+int dlrm_sr_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_sr_sgd* op, dlrm_indexer* ix, const void* indices, int itype,
+                     int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld, const void* dout,
+                     int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr,
+                     unsigned flags) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_sr_step_bwd: null ctx/tables/optimizer/indexer");
+    return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
+                         dx, dx_ld, dt, dt_ld, lr, flags, nullptr, sr_step_rule(op));
+}
+
+int dlrm_sr_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_sr_sgd* op, dlrm_indexer* ix, const void* indices,
+                             int itype, int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
+                             const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
+                             int64_t dt_ld, float lr, dlrm_indexer* next, const void* next_indices, unsigned flags) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_sr_step_bwd_prepare: null ctx/tables/optimizer/indexer");
+    return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
+                                 padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags, sr_step_rule(op));
 }
 
 // ---- diagnostics: a native backtrace on a fatal signal (SIGSEGV / SIGBUS / SIGABRT), written to

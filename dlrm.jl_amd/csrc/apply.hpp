@@ -307,8 +307,10 @@ __device__ __forceinline__ void philox4x32_10(uint32_t* c, uint32_t k0, uint32_t
 // counter = (r, t << 16 | c >> 2, s lo, s hi), and column c takes the low 16 bits of output word c & 3.  One block
 // serves four consecutive columns, generated at the write (after the loads: nothing is held across the gather).
 // The step is one device word the optimizer handle owns: every launch of an update call reads it (load_step, once
-// per workgroup into scalars) and a one-thread launch after the call's last adds one, in stream order.  No per-row
-// state, so the rule alternates freely with Descent on the same tables.
+// per workgroup into scalars) and a one-thread launch after the call's last adds one, in stream order.  The fused
+// training step with the rule (dlrm_sr_step_bwd) is one value of the word: its backward (interact.hip: this struct's
+// load_step and store at the once-hit write) and its apply read the same value, and the advance follows the apply.
+// No per-row state, so the rule alternates freely with Descent on the same tables.
 struct StochasticDescent {
     float lr;
     uint32_t k0, k1;       // the seed's halves
@@ -316,7 +318,9 @@ struct StochasticDescent {
     uint32_t s0, s1;       // its value, by load_step
     typedef float State;
     static constexpr int kState = 4;
-    static constexpr bool kCarriesBuild = false;  // MODE 0 / 1 only (sr_sgd.hip): no fused step with this rule
+    // MODE >= 2 over the training step's fp32 dt, in a unit of its own (sr_step.hip: launch_sr_step_apply), so
+    // sr_sgd.hip stays the MODE 0 / 1 unit it was
+    static constexpr bool kCarriesBuild = true;
     static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = false;  // fp32 tables: nothing to round
     __device__ __forceinline__ float* base(int) const { return nullptr; }

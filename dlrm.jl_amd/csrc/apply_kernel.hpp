@@ -1,8 +1,8 @@
 // apply_kernel.hpp -- the apply launch of update! (sgd_apply_kernel over apply.hpp's work items), its
 // any-D fallback kernels and their launchers, by update rule.  update.hip instantiates Descent
 // (every MODE), adagrad.hip and adagrad_rowwise.hip the Adagrad rules, split_sgd.hip the split rule and sr_sgd.hip
-// the stochastic rule (MODE 0 and 1), and split_step.hip, adagrad_step.hip and adagrad_rowwise_step.hip those three rules' build-carrying
-// launches (MODE 2 / 3 / 5): they compile side by side.
+// the stochastic rule (MODE 0 and 1), and split_step.hip, adagrad_step.hip, adagrad_rowwise_step.hip and sr_step.hip those four
+// rules' build-carrying launches (MODE 2 / 3 / 5): they compile side by side.
 #pragma once
 #include "apply.hpp"
 

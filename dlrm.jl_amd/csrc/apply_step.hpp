@@ -1,17 +1,19 @@
 // apply_step.hpp -- the apply launch of the training step with a sparse Adagrad rule (dlrm_adagrad_step_bwd,
-// dlrm_adagrad_step_bwd_prepare) when it carries the next batch's split indexer build.
+// dlrm_adagrad_step_bwd_prepare) or the stochastic rule (dlrm_sr_step_bwd, dlrm_sr_step_bwd_prepare) when it
+// carries the next batch's split indexer build.
 //
 // apply_kernel.hpp's launch in MODE 2 / 3 / 5 (the build's workgroups first, then chunks and hot slices; no
 // once-hit items: the step backward stepped those rows) with the rule at its write sites.  Only what the step
-// needs is instantiated: fp32 and bf16 tables, the step's fp32 dt rows.  MODE 0 and 1 stay in adagrad.hip and
-// adagrad_rowwise.hip; adagrad_step.hip and adagrad_rowwise_step.hip include this, one rule each, and compile
-// beside update.hip.
+// needs is instantiated: fp32 (a rule with kF32Tables) and bf16 tables, the step's fp32 dt rows.  MODE 0 and 1 stay
+// in adagrad.hip, adagrad_rowwise.hip and sr_sgd.hip; adagrad_step.hip, adagrad_rowwise_step.hip and sr_step.hip
+// include this, one rule each, and compile beside update.hip.
 #pragma once
 #include "apply_kernel.hpp"
 
 namespace dlrm {
 
-// plain(sa): the rule's MODE 0 / 1 launch (its own unit's)
+// plain(sa): the rule's MODE 0 / 1 launch (its own unit's).  (A rule without kF32Tables: the caller checked that the
+// tables are bf16, as by_dtypes' callers do.)
 template <typename R, typename Plain>
 static int launch_step_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T_, int D,
                                   int tdtype, int64_t N, const float* dt, int64_t dt_ld, int64_t dt_offset,
@@ -28,9 +30,11 @@ static int launch_step_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc
         switch (D / 4) {  // 16-B vectors per fp32 gradient row
 #define DLRM_CASE(V)                                                                                                   \
     case V:                                                                                                            \
-        if (tdtype == DLRM_F32)                                                                                        \
-            launch_apply_build_vec<float, float, V, R, 2>(s, ix, tabs, TV, 1, dt, dt_ld, dt_offset, rule, N, err, sa, *pa); \
-        else                                                                                                           \
+        if (tdtype == DLRM_F32) {                                                                                      \
+            if constexpr (R::kF32Tables)                                                                               \
+                launch_apply_build_vec<float, float, V, R, 2>(s, ix, tabs, TV, 1, dt, dt_ld, dt_offset, rule, N, err, sa, \
+                                                              *pa);                                                    \
+        } else                                                                                                         \
             launch_apply_build_vec<uint16_t, float, V, R, 2>(s, ix, tabs, TV, 1, dt, dt_ld, dt_offset, rule, N, err, sa, \
                                                              *pa);                                                     \
         break;
@@ -38,7 +42,7 @@ static int launch_step_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc
 #undef DLRM_CASE
             default: done = false;
         }
-        if (done) return ctx_hip(ctx, hipGetLastError(), "adagrad apply(+build) launch");
+        if (done) return ctx_hip(ctx, hipGetLastError(), "step apply(+build) launch");
     }
     // once-hit items in this launch, or no vector kernel for the shape: the rule's own launches, then the build's
     const int rc = plain(sa);

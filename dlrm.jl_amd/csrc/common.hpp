@@ -450,6 +450,20 @@ int launch_sr_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bo
                         uint64_t* step, int T, int D, int L, int64_t N, const void* grad, int gdtype,
                         int64_t grad_ld, int64_t grad_offset, float lr, const SinglesArgs& singles);
 int launch_sr_step_set(dlrm_ctx* ctx, uint64_t* step, uint64_t value);
+int launch_sr_step_advance(dlrm_ctx* ctx, uint64_t* step);  // step += 1, by one thread, on the context's stream
+// the training step with the stochastic rule (dlrm_sr_step_bwd): whether the step backward has the rule's once-hit
+// write for this shape (interact.hip), that backward (it reads the step word and does not advance it), and the
+// rule's apply over the fp32 dt followed by the advance of the step word (sr_step.hip): with `prep` and no once-hit
+// items the next batch's build rides on the launch (MODE 2 / 3 / 5), otherwise launch_sr_sgd_apply and, with
+// `prep`, the build's own launch.  Either way the word advances once, after the launch that read it.
+bool sr_step_bwd_supported(int T, int d);
+int launch_sr_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T, const void* idx, int itype, int64_t tstride,
+                       int base, int d, int B, const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, float* dx,
+                       int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix, float lr, uint64_t seed,
+                       const uint64_t* step);
+int launch_sr_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint64_t seed,
+                         uint64_t* step, int T, int D, int64_t N, const float* dt, int64_t dt_ld, int64_t dt_offset,
+                         float lr, const SinglesArgs& singles, const PrepArgs* prep);
 // the training step's split apply over the fp32 dt (split_step.hip): with `prep` and no once-hit items the
 // next batch's build rides on the launch (MODE 2 / 3 / 5), otherwise launch_split_sgd_apply and, with `prep`,
 // the build's own launch.

@@ -348,6 +348,7 @@ struct StepUpdate {
     // tables' pointers to it, a member `state`; kName heads the launch errors.
     static constexpr bool kSplit = false;
     static constexpr int kAdagrad = 0;
+    static constexpr bool kStochastic = false;
     typedef void State;
     static constexpr const char* kName = "step_bwd";
 };
@@ -373,6 +374,18 @@ struct AdagradStepUpdate : StepUpdate {
     static constexpr int kAdagrad = RW ? 2 : 1;
     typedef float State;
     static constexpr const char* kName = "adagrad_step_bwd";
+};
+
+// The same for the stochastic rule on bf16 tables (apply.hpp StochasticDescent; dlrm_sr_step_bwd): Descent's write
+// with the rule's store -- w = sr_bf16(fmaf(-lr, 0 + g, w), R), R the 16 Philox bits of (seed, step, table, row,
+// column) that the apply's once-hit item draws for the element, generated at the write, after the MFMAs.  No second
+// stream: the seed's halves and the pointer to the handle's step word, which each workgroup reads once
+// (StochasticDescent::load_step).  A struct of its own again.
+struct StochasticStepUpdate : StepUpdate {
+    uint32_t k0, k1;       // the seed's halves
+    const uint64_t* step;  // the handle's step word
+    static constexpr bool kStochastic = true;
+    static constexpr const char* kName = "sr_step_bwd";
 };
 
 // the d = 128 rule kernels' per-table pointers to the second stream in LDS, and the row-wise two-wave form's
@@ -685,7 +698,7 @@ __global__ __launch_bounds__(256, 2) void interact_bwd_update_kernel(int d, int 
 // Every other instantiation keeps the kernel's text.
 template <typename T, int DC, int WPS, bool MAPPED, int CPL, bool YS, typename SU> constexpr bool bwd_tracked() {
     return std::is_same<T, float>::value && DC == 128 && WPS == 2 && CPL == 4 && !MAPPED && !YS && !SU::kSplit &&
-           SU::kAdagrad == 0;
+           SU::kAdagrad == 0 && !SU::kStochastic;
 }
 
 #ifdef DLRM_WTRACE
@@ -916,7 +929,9 @@ __device__ __forceinline__ void bwd_split_tracked(int F, int B, const float* __r
 // SU: the once-hit rule and its arguments.  StepUpdate is Descent's write.  SplitStepUpdate (dlrm_split_step_bwd) is
 // the split rule's on bf16 tables, its branches `if constexpr (SU::kSplit)`; AdagradStepUpdate (dlrm_adagrad_step_bwd)
 // the sparse Adagrad rules' on fp32 and bf16 tables, `if constexpr (AG == 1)` the element-wise rule and `(AG == 2)`
-// the row-wise one.  The rules other than Descent exist in the step's default geometries only, NB = 1 and 2
+// the row-wise one; StochasticStepUpdate (dlrm_sr_step_bwd) the stochastic rule's on bf16 tables, `if constexpr
+// (SU::kStochastic)`: Descent's write with the rule's store.  The rules other than Descent exist in the step's
+// default geometries only, NB = 1 and 2
 // (step_bwd_form below).  (The body stays the kernel's own text: as an inlined function template it no longer
 // compiled to the same code.)
 template <typename T, int NB, int DC, int SPB, int WPS = 2, bool MAPPED = false, int CPL = 4, bool YS = false,
@@ -930,6 +945,7 @@ __global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) vo
     constexpr bool RULE = SU::kSplit || AG != 0;  // a rule whose rows have a second stream
     typedef typename SU::State SE;
     static_assert(AG == 0 || (!YS && !MAPPED), "the Adagrad rules step the training step's tables");
+    static_assert(!SU::kStochastic || (sizeof(T) == 2 && !YS && !MAPPED), "stochastic rounding is of bf16 tables");
     // the row-wise sum of squares crosses the sample's two waves once: one super-block per wave, so the block
     // barrier of that exchange sits in uniform control flow
     static_assert(AG != 2 || WPS == 1 || DC == 128, "row-wise over two waves: d = 128");
@@ -1015,6 +1031,12 @@ __global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) vo
         }
     const bool frozen = su.single ? *su.err != 0 : true;  // a bounds error this step: no table row is written
     if (su.single && blockIdx.x == 0 && threadIdx.x == 0) snapshot_error(su.err, frozen ? 1u : 0u);
+    // the stochastic rule with the step word's value: read once per workgroup, into two scalars
+    StochasticDescent sr{};
+    if constexpr (SU::kStochastic) {
+        sr = StochasticDescent{su.lr, su.k0, su.k1, su.step, 0u, 0u};
+        sr.load_step();
+    }
     if (tdl_ok) {
         tds[threadIdx.x] = tdl;
         if constexpr (RULE && ST_LDS) sop[threadIdx.x] = (SE*)myst;
@@ -1337,6 +1359,13 @@ __global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) vo
                             for (int e = 0; e < CPL; ++e) wv[e] = __builtin_fmaf(-sc, 0.0f + v[e], tw[e]);
                             store_row<T, CPL, true>((T*)tds[f - 1].data + (int64_t)urow[I][r] * d, n0, wv);
                             if (c == 0 && h == 0) stg<float>(st_base(r) + urow[I][r], m);
+                        } else if constexpr (SU::kStochastic) {
+                            // Descent's step, stored by the apply's own store: one Philox block per four columns
+                            // from column n0 of row urow of table f - 1
+#pragma unroll
+                            for (int e = 0; e < CPL; ++e) wv[e] = __builtin_fmaf(-su.lr, 0.0f + v[e], tw[e]);
+                            sr.template store<CPL>((uint16_t*)tds[f - 1].data + (int64_t)urow[I][r] * d + n0, f - 1,
+                                                   urow[I][r], n0, wv);
                         } else {
 #pragma unroll
                         for (int e = 0; e < CPL; ++e) wv[e] = __builtin_fmaf(-su.lr, 0.0f + v[e], tw[e]);
@@ -1783,14 +1812,16 @@ int launch_step_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, i
 //    (96 VGPRs against Descent's 80), so those shapes keep the two-wave form, which holds Descent's 8;
 //  - with up to 16 features Descent's forms hold 8 waves per SIMD at 56..59 VGPRs, and the row-wise forms need
 //    77..87, the element-wise one-wave form on fp32 tables 66.
-// The split rule's rows live in bf16 tables.
-constexpr bool step_bwd_form(bool split, int adagrad, bool f32, int NB, int WPS, int CPL, int SPB) {
+// The split rule's rows live in bf16 tables, and so do the stochastic rule's: that rule has
+// every default-geometry form of Descent on bf16 tables but the 8-column one with up to 16 features, as the split rule.
+constexpr bool step_bwd_form(bool split, int adagrad, bool f32, int NB, int WPS, int CPL, int SPB,
+                             bool stochastic = false) {
     const bool d128 = WPS == 2 || CPL == 8;
     if ((CPL == 8 && (f32 || WPS != 1)) || !(SPB == 2 || SPB == 4 || SPB == 8)) return false;
-    if (SPB != (CPL == 8 ? 2 : (d128 ? 4 : 8))) return !split && !adagrad && d128;
-    if (!split && !adagrad) return true;
+    if (SPB != (CPL == 8 ? 2 : (d128 ? 4 : 8))) return !split && !adagrad && !stochastic && d128;
+    if (!split && !adagrad && !stochastic) return true;
     if (CPL == 8 && NB == 1) return false;
-    if (split) return !f32;
+    if (split || stochastic) return !f32;
     return adagrad == 2 ? NB == 2 : !(NB == 1 && WPS == 1 && f32);
 }
 // Shapes whose step backward has an Adagrad form (among step_split_supported's): d = 128 and d <= 64, the forms
@@ -1805,6 +1836,13 @@ bool adagrad_step_bwd_supported(bool rowwise, int dtype, int T_, int d) {
                          d == 128 ? 4 : 8);
 }
 
+// Shapes whose step backward has the stochastic rule's once-hit write (among step_split_supported's, bf16 tables):
+// d = 128 and d <= 64.  Any other d and the DLRM_BWD_NOSPLIT override take the gather backward.
+bool sr_step_bwd_supported(int T_, int d) {
+    if (knobs().bwd_nosplit || !(d == 128 || d <= 64)) return false;
+    return step_bwd_form(false, 0, false, (T_ + 1 + 15) / 16, d == 128 ? 2 : 1, 4, d == 128 ? 4 : 8, true);
+}
+
 // Training-step backward after launch_step_fwd under the rule SU: once-hit rows updated in place, dt rows of the
 // others written for the apply.  The caller checked the shape (launch_step_fwd accepted it), the 16-B alignment of
 // dx / dt and of the rule's second stream, and for an Adagrad rule adagrad_step_bwd_supported.  The DLRM_BWD_SPB /
@@ -1813,7 +1851,7 @@ template <typename T, typename SU>
 static int launch_step_bwd_rule(dlrm_ctx* ctx, const GatherArgs& ga, int F, int d, int B, const void* x_, int64_t x_ld,
                                 const void* dout_, int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
                                 const SU& su) {
-    constexpr bool f32 = sizeof(T) == 4, descent = !SU::kSplit && !SU::kAdagrad;
+    constexpr bool f32 = sizeof(T) == 4, descent = !SU::kSplit && !SU::kAdagrad && !SU::kStochastic;
     const T* x = (const T*)x_;
     const T* dout = (const T*)dout_;
     const int NB = (F + 15) / 16;
@@ -1824,7 +1862,7 @@ static int launch_step_bwd_rule(dlrm_ctx* ctx, const GatherArgs& ga, int F, int 
     };
     // (a form step_bwd_form leaves out is not instantiated)
 #define DLRM_FORM(N_, DC_, W_, C_, S_, WHAT_)                                                                       \
-    if constexpr (step_bwd_form(SU::kSplit, SU::kAdagrad, f32, N_, W_, C_, S_))                                     \
+    if constexpr (step_bwd_form(SU::kSplit, SU::kAdagrad, f32, N_, W_, C_, S_, SU::kStochastic))                    \
         if (NB == N_ && spb == S_) {                                                                                \
             hipLaunchKernelGGL((interact_bwd_split_kernel<T, N_, DC_, S_, W_, false, C_, false, SU>),                \
                                dim3((unsigned)((B + S_ - 1) / S_)), dim3(64 * W_ * S_), 0, s, d, F, B, dout, dout_ld, \
@@ -1841,7 +1879,7 @@ static int launch_step_bwd_rule(dlrm_ctx* ctx, const GatherArgs& ga, int F, int 
         // DLRM_BWD_CPL = 4 / 8 forces either form.
         const int cpl_env = descent ? knobs().bwd_cpl : 0;
         const bool cpl8 = d == 128 && !f32 && (cpl_env ? cpl_env == 8 : B > 2048) &&
-                          step_bwd_form(SU::kSplit, SU::kAdagrad, f32, NB, 1, 8, 2);
+                          step_bwd_form(SU::kSplit, SU::kAdagrad, f32, NB, 1, 8, 2, SU::kStochastic);
         // samples per block (DLRM_BWD_SPB = 2, 4 or 8 overrides)
         const int spb_env = !(descent && d == 128) ? 0
                             : knobs().bwd_spb >= 8 ? 8 : (knobs().bwd_spb >= 4 ? 4 : (knobs().bwd_spb > 0 ? 2 : 0));
@@ -1857,9 +1895,9 @@ static int launch_step_bwd_rule(dlrm_ctx* ctx, const GatherArgs& ga, int F, int 
     }
 #undef DLRM_FORMS
 #undef DLRM_FORM
-    // any other d: interact_bwd_update_kernel (Descent and the split rule; an Adagrad rule's caller took the gather
-    // backward).  One super-block of T rows in flight: two (the gather backward's choice) spill here
-    if constexpr (SU::kAdagrad != 0) {
+    // any other d: interact_bwd_update_kernel (Descent and the split rule; an Adagrad or the stochastic rule's caller
+    // took the gather backward).  One super-block of T rows in flight: two (the gather backward's choice) spill here
+    if constexpr (SU::kAdagrad != 0 || SU::kStochastic) {
         return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no kernel for this shape", SU::kName);
     } else {
         const int dc = descent && d == 128 ? 128 : 0, sbu = dc == 128 && knobs().upd_sbu == 2 ? 2 : 1;
@@ -1910,6 +1948,17 @@ int launch_adagrad_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dt
     }
     if (rowwise) DLRM_RULE(uint16_t, AdagradStepUpdate<true>{su, state, eps});
     DLRM_RULE(uint16_t, AdagradStepUpdate<false>{su, state, eps});
+}
+
+// (bf16 tables and sr_step_bwd_supported: the caller checked; step: the handle's device step word)
+int launch_sr_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, const void* idx, int itype, int64_t tstride,
+                       int base, int d, int B, const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, float* dx,
+                       int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix, float lr, uint64_t seed,
+                       const uint64_t* step) {
+    if (B == 0 || T_ == 0) return DLRM_OK;
+    const GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
+    const StepUpdate su{ix.single, ix.cap, lr, ctx_error_word(ctx)};
+    DLRM_RULE(uint16_t, StochasticStepUpdate{su, (uint32_t)seed, (uint32_t)(seed >> 32), step});
 #undef DLRM_RULE
 }
 

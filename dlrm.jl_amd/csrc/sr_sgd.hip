@@ -7,7 +7,8 @@
 // No state stream: the row is loaded where Descent loads it and written once.  Only bf16 tables (TT =
 // uint16_t) are instantiated, MODE 0 and 1.  The step is a device word of the optimizer handle: every launch of
 // a call reads it, and a one-thread launch after the call's last adds one, in stream order (so a captured
-// update advances it on every replay and nothing synchronises).
+// update advances it on every replay and nothing synchronises).  The fused training step with the rule
+// (dlrm_sr_step_bwd) reads the same word in its backward and its apply (sr_step.hip) and advances it the same way.
 #include "apply_kernel.hpp"
 
 namespace dlrm {
@@ -23,7 +24,11 @@ int launch_sr_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bo
                                      StochasticDescent{lr, (uint32_t)seed, (uint32_t)(seed >> 32), step, 0u, 0u}, sa,
                                      nullptr);
     if (rc) return rc;
-    // after the call's last launch: every workgroup of it has read the word when this one starts
+    return launch_sr_step_advance(ctx, step);
+}
+
+// after a call's last launch that reads the word: every workgroup of it has read the word when this one starts
+int launch_sr_step_advance(dlrm_ctx* ctx, uint64_t* step) {
     hipLaunchKernelGGL(sr_step_advance_kernel, dim3(1), dim3(1), 0, ctx_stream(ctx), step);
     return ctx_hip(ctx, hipGetLastError(), "sr_step_advance launch");
 }

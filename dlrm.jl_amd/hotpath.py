@@ -30,8 +30,8 @@ tables are stepped with that optimizer.  The fused step pair is Descent-only (on
 the high halves), so this selects the operator path: the fused forward, the gather backward (which
 writes every dt row and builds the indexer in its launch), then dlrm_adagrad_update(PREBUILT),
 dlrm_split_sgd_update(PREBUILT) or dlrm_sr_sgd_update(PREBUILT) -- three launches (the stochastic rule: and the
-one-thread advance of its step), no host synchronisation, graph-capturable.  `StochasticDescent` has this route
-only: `fused_step`, `adagrad_step` and `pipeline` are refused with it.
+one-thread advance of its step), no host synchronisation, graph-capturable.  Without `stochastic_step=True`
+(below) `StochasticDescent` has this route only: `fused_step`, `adagrad_step` and `pipeline` are refused with it.
 
 `fused_step=True` with `opt=SplitDescent(η)` on bfloat16 tables: the fused step pair with the split rule
 (dlrm_step_fwd, then dlrm_split_step_bwd / dlrm_split_step_bwd_prepare): once-hit rows are stepped inside
@@ -44,6 +44,13 @@ step pair with that rule (dlrm_step_fwd, then dlrm_adagrad_step_bwd / dlrm_adagr
 rows and their state are stepped inside the backward, only the repeated rows' dt rows are written, and
 `pipeline` "apply" / "side" work as they do for Descent.  Tables and state end up bit for bit what the
 operator path gives.  Opt-in again: without the keyword the Adagrad rules keep the operator path.
+
+`stochastic_step=True` with `opt=StochasticDescent(η, seed)` on bfloat16 tables: the fused step pair with that rule
+(dlrm_step_fwd, then dlrm_sr_step_bwd / dlrm_sr_step_bwd_prepare): once-hit rows are stepped and stochastically
+rounded inside the backward, only the repeated rows' dt rows are written, and `pipeline` "apply" / "side" work as
+they do for Descent.  The backward and the apply of a step read the same value of the optimizer's step word, which
+advances by one after the apply; every row ends up bit for bit what the operator path gives from the same step.
+Opt-in, a keyword of its own: without it the rule keeps the operator path.
 """
 import torch
 
@@ -58,7 +65,7 @@ from .update import SparseIndexer, SplitDescent, StochasticDescent, _AdagradBase
 class HotPath:
     def __init__(self, tables, batch, lookups=1, *, lr=0.1, index_base=0, deterministic=True,
                  overlap_indexer=None, pad_to=1, fused=True, materialize_ys=None, pipeline=False, chunk=None,
-                 parts=None, opt=None, fused_step=False, adagrad_step=False):
+                 parts=None, opt=None, fused_step=False, adagrad_step=False, stochastic_step=False):
         if opt is not None and not isinstance(opt, _StatefulOpt):
             raise TypeError("HotPath: opt is an ADAGrad, RowwiseADAGrad, SplitDescent or StochasticDescent "
                             "(None: Descent(lr))")
@@ -66,15 +73,21 @@ class HotPath:
             raise ValueError(f"HotPath: {type(opt).__name__} needs the deterministic update")
         self.opt = opt
         self.ts = tables if isinstance(tables, EmbeddingTableSet) else EmbeddingTableSet(tables)
+        # the fused step pair with the stochastic rule (dlrm_sr_step_bwd); a keyword of its own
+        self.stochastic_step = bool(stochastic_step)
+        if self.stochastic_step and not isinstance(opt, StochasticDescent):
+            raise ValueError("HotPath: stochastic_step=True is the stochastic rule's fused step "
+                             "(opt=StochasticDescent(eta, seed)); the split rule's is fused_step=True, the Adagrad "
+                             "rules' adagrad_step=True, Descent(lr) is fused without a keyword")
         if isinstance(opt, StochasticDescent):
-            # the operator route only: dlrm_*_step_bwd has no instantiation with the stochastic store
+            # without stochastic_step the operator route only; fused_step / adagrad_step are other rules' keywords
             if fused_step or adagrad_step:
-                raise ValueError("HotPath: StochasticDescent has no fused step (fused_step / adagrad_step are the split "
-                                 "and Adagrad rules'): its once-hit rows are rounded in the apply launch, not in the "
-                                 "step backward")
-            if pipeline not in (False, 0, None):
+                raise ValueError("HotPath: fused_step / adagrad_step are the split and Adagrad rules' fused step; "
+                                 "StochasticDescent's is stochastic_step=True (without it the rule takes the operator "
+                                 "route: its once-hit rows are rounded in the apply launch)")
+            if pipeline not in (False, 0, None) and not self.stochastic_step:
                 raise ValueError("HotPath: pipeline must be None with opt=StochasticDescent: the pipelined steps need "
-                                 "a fused step, which this rule does not have")
+                                 "a fused step, which this rule has with stochastic_step=True only")
             if self.ts.dtype != torch.bfloat16:
                 raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not {self.ts.dtype}")
         # the fused step pair with the split rule (dlrm_split_step_bwd); without it opt= takes the operator path
@@ -135,14 +148,18 @@ class HotPath:
         # the training-step pair (dlrm_step_fwd / dlrm_step_bwd): indexer built inside the forward's
         # launch, once-hit rows updated inside the backward's, the rest by the apply launch
         self.step_api = ((not self.materialize_ys) and self.indexer is not None and not self.overlap_indexer and
-                         (opt is None or self.split_step or self.adagrad_step))  # (dlrm_step_bwd: Descent;
-        # dlrm_split_step_bwd: the split rule; dlrm_adagrad_step_bwd: the Adagrad rules)
+                         (opt is None or self.split_step or self.adagrad_step or self.stochastic_step))
+        # (dlrm_step_bwd: Descent; dlrm_split_step_bwd: the split rule; dlrm_adagrad_step_bwd: the Adagrad rules;
+        # dlrm_sr_step_bwd: the stochastic rule)
         if self.split_step and not self.step_api:
             raise ValueError("HotPath: fused_step=True needs the step kernels (one-hot lookups, ys not materialized, "
                              "no side-stream indexer)")
         if self.adagrad_step and not self.step_api:
             raise ValueError("HotPath: adagrad_step=True needs the step kernels (one-hot lookups, ys not materialized, "
                              "no side-stream indexer)")
+        if self.stochastic_step and not self.step_api:
+            raise ValueError("HotPath: stochastic_step=True needs the step kernels (one-hot lookups, ys not "
+                             "materialized, no side-stream indexer)")
         # pipelined steps: the NEXT batch's split indexer is built during this step, so the
         # step's forward launch only gathers; two indexers alternate.
         #   "apply" (`step_prep`): by extra workgroups of this step's apply launch
@@ -154,10 +171,10 @@ class HotPath:
         if mode not in (None, "side", "apply"):
             raise ValueError(f"pipeline must be None, 'side' or 'apply', not {pipeline!r}")
         if opt is not None:
-            if mode is not None and not (self.split_step or self.adagrad_step):
+            if mode is not None and not (self.split_step or self.adagrad_step or self.stochastic_step):
                 raise ValueError("HotPath: the pipelined steps need the fused step (pipeline must be None with opt, "
-                                 "unless opt=SplitDescent with fused_step=True or an Adagrad rule with "
-                                 "adagrad_step=True)")
+                                 "unless opt=SplitDescent with fused_step=True, an Adagrad rule with "
+                                 "adagrad_step=True or opt=StochasticDescent with stochastic_step=True)")
             opt.handle_of(self.ts)  # the state, allocated before any graph capture
         # (pooled bags: "side" only -- the next batch's build beside this step's apply, `step_next`)
         self.pipeline = mode if (mode and ((self.step_api and self.L == 1) or (mode == "side" and self.L > 1))) else None
@@ -254,11 +271,12 @@ class HotPath:
         """dlrm_step_bwd: dot_back + update!(Descent(lr)) with the indexer of step_fwd
         (flags: _lib.STEP_BWD_ONLY / STEP_APPLY_ONLY run one of its two launches).  fused_step:
         dlrm_split_step_bwd, the same with the split rule and the optimizer's eta; adagrad_step:
-        dlrm_adagrad_step_bwd, with the optimizer's rule, eta and eps."""
+        dlrm_adagrad_step_bwd, with the optimizer's rule, eta and eps; stochastic_step: dlrm_sr_step_bwd, with the
+        optimizer's eta, seed and step word (advanced after the launch that runs the apply)."""
         h = self.ctx.bind()
         x = self._fwd_x if x is None else x
         idx = self._fwd_idx if idx is None else idx
-        if self.split_step or self.adagrad_step:
+        if self.split_step or self.adagrad_step or self.stochastic_step:
             args = (h, self.ts.handle, self.opt.handle_of(self.ts), self.indexer.handle, ptr(idx.data), idx.itype,
                     idx.stride, self.index_base, self.B, ptr(x), x.stride(0), ptr(dout), dout.stride(0), self.padding,
                     ptr(self.dx), self.dx.stride(0), ptr(self.dt), self.dt.stride(0), self.opt.eta)
@@ -268,6 +286,8 @@ class HotPath:
                 eta, eps = self.rule_params or (self.opt.eta, self.opt.eps)
                 args = args[:-1] + (eta, eps)
                 one, two = self.lib.dlrm_adagrad_step_bwd, self.lib.dlrm_adagrad_step_bwd_prepare
+            elif self.stochastic_step:
+                one, two = self.lib.dlrm_sr_step_bwd, self.lib.dlrm_sr_step_bwd_prepare
             else:
                 one, two = self.lib.dlrm_split_step_bwd, self.lib.dlrm_split_step_bwd_prepare
             if prepare is not None:

@@ -18,7 +18,9 @@
 # (`Context(0; fused = true, lr = η)` runs that chain on the fused training-step kernels;
 # `Context(0; fused = true, split = HipSplitDescent(η))` does so on split-bf16 tables, through
 # dlrm_split_step_bwd / dlrm_split_step_bwd_prepare; `Context(0; fused = true, adagrad = HipADAGrad(η, ϵ))` or
-# `adagrad = HipRowwiseADAGrad(η, ϵ)` with that Adagrad rule, through dlrm_adagrad_step_bwd / _prepare.)
+# `adagrad = HipRowwiseADAGrad(η, ϵ)` with that Adagrad rule, through dlrm_adagrad_step_bwd / _prepare;
+# `Context(0; fused = true, stochastic = HipStochasticDescent(η; seed))` with the stochastic rule on 2-byte tables,
+# through dlrm_sr_step_bwd / dlrm_sr_step_bwd_prepare.)
 #
 # and `_Train.train!` / `DLRMModel` stay unchanged.  Dense inputs x (bottom-MLP output) and the
 # interaction output cross PCIe here because the MLPs stay on the CPU in the reference; the
@@ -62,8 +64,11 @@ mutable struct Context
     # the once-hit rows and their state with that rule, update! with that same optimizer runs or defers its apply
     adagrad::Any
     eps::Union{Nothing,Float32}   # ... and its ϵ as given here: the pullback's and a deferred apply's alike
+    # stochastic (fused): a HipStochasticDescent likewise (dlrm_sr_step_bwd): the pullback steps and rounds the
+    # once-hit rows, update! with that same optimizer runs or defers the apply, after which its step word advances
+    stochastic::Any
     function Context(device::Integer; stream::Ptr{Cvoid} = C_NULL, fused::Bool = false, lr = nothing,
-                     defer_update::Bool = true, split = nothing, adagrad = nothing)
+                     defer_update::Bool = true, split = nothing, adagrad = nothing, stochastic = nothing)
         out = Ref{Ptr{Cvoid}}(C_NULL)
         rc = ccall((:dlrm_ctx_create, libdlrm), Cint, (Cint, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), device, stream, out)
         rc == 0 || throw(DLRMError(rc, "dlrm_ctx_create"))
@@ -75,8 +80,13 @@ mutable struct Context
         adagrad === nothing || lr === nothing || Float32(lr) == adagrad.eta ||
             throw(ArgumentError("Context: lr = $lr beside adagrad = $(nameof(typeof(adagrad)))($(adagrad.eta), …)"))
         adagrad === nothing || (lr = adagrad.eta)
+        stochastic === nothing || (split === nothing && adagrad === nothing) ||
+            throw(ArgumentError("Context: one rule steps the tables, split =, adagrad = or stochastic ="))
+        stochastic === nothing || lr === nothing || Float32(lr) == stochastic.eta ||
+            throw(ArgumentError("Context: lr = $lr beside stochastic = HipStochasticDescent($(stochastic.eta))"))
+        stochastic === nothing || (lr = stochastic.eta)
         ctx = new(out[], fused, lr === nothing ? nothing : Float32(lr), defer_update, split, adagrad,
-                  adagrad === nothing ? nothing : Float32(adagrad.epsilon))
+                  adagrad === nothing ? nothing : Float32(adagrad.epsilon), stochastic)
         finalizer(c -> ccall((:dlrm_ctx_destroy, libdlrm), Cint, (Ptr{Cvoid},), c.ptr), ctx)
         return ctx
     end
@@ -605,9 +615,19 @@ end
 
 # The training step's backward / apply launches of a fused step `st` (dlrm_step_bwd and _prepare), or, on a
 # context built with `split = HipSplitDescent(η)`, the split rule's (dlrm_split_step_bwd and _prepare), or, with
-# `adagrad = HipADAGrad(η, ϵ) | HipRowwiseADAGrad(η, ϵ)`, that rule's (dlrm_adagrad_step_bwd and _prepare).
+# `adagrad = HipADAGrad(η, ϵ) | HipRowwiseADAGrad(η, ϵ)`, that rule's (dlrm_adagrad_step_bwd and _prepare), or, with
+# `stochastic = HipStochasticDescent(η; seed)`, the stochastic rule's (dlrm_sr_step_bwd and _prepare).
 function _step_bwd(ctx, st, delta_ld, flags)
     d, B = size(st.x)
+    if ctx.stochastic !== nothing
+        h = sr_state(ctx.stochastic, st.tables)
+        return ccall((:dlrm_sr_step_bwd, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid}, Int64,
+                      Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cuint),
+                     ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
+                     st.x.ptr, d, st.delta.ptr, delta_ld, st.padding, st.dx.ptr, d, st.dt.ptr,
+                     size(st.dt, 1), ctx.lr, flags)
+    end
     if ctx.split !== nothing
         _, h = split_state(ctx.split, st.tables)
         return ccall((:dlrm_split_step_bwd, libdlrm), Cint,
@@ -635,6 +655,16 @@ function _step_bwd(ctx, st, delta_ld, flags)
 end
 function _step_bwd_prepare(ctx, st, nix, next, flags)
     d, B = size(st.x)
+    if ctx.stochastic !== nothing
+        h = sr_state(ctx.stochastic, st.tables)
+        return ccall((:dlrm_sr_step_bwd_prepare, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid},
+                      Int64, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat,
+                      Ptr{Cvoid}, Ptr{Cvoid}, Cuint),
+                     ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
+                     st.x.ptr, d, st.delta.ptr, size(st.delta, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
+                     size(st.dt, 1), ctx.lr, nix.ptr, next.data.ptr, flags)
+    end
     if ctx.split !== nothing
         _, h = split_state(ctx.split, st.tables)
         return ccall((:dlrm_split_step_bwd_prepare, libdlrm), Cint,
@@ -965,10 +995,14 @@ function _fused_update!(opt, st, tables)
     ctx.adagrad === nothing || opt === ctx.adagrad ||
         throw(ArgumentError("this context steps its tables with its $(nameof(typeof(ctx.adagrad))) (the pullback ran " *
                             "its backward); update! got $(nameof(typeof(opt)))"))
+    ctx.stochastic === nothing || opt === ctx.stochastic ||
+        throw(ArgumentError("this context steps its tables with its HipStochasticDescent (the pullback ran its " *
+                            "backward); update! got $(nameof(typeof(opt)))"))
     ctx.adagrad === nothing || (opt.eta == ctx.lr && opt.epsilon == ctx.eps) ||
         throw(ArgumentError("the pullback stepped the once-hit rows with η = $(ctx.lr), ϵ = $(ctx.eps); update! got " *
                             "$(opt.eta), $(opt.epsilon)"))
-    if opt isa Union{AbstractHipADAGrad,HipSplitDescent,HipStochasticDescent} && ctx.split === nothing && ctx.adagrad === nothing
+    if opt isa Union{AbstractHipADAGrad,HipSplitDescent,HipStochasticDescent} && ctx.split === nothing &&
+       ctx.adagrad === nothing && ctx.stochastic === nothing
         # every dt row is needed: the forward's split indexer, the once-hit rows as singles items
         st.bwd === :once_hit_applied &&
             throw(ArgumentError("the pullback already stepped the once-hit rows with Descent (η = $(ctx.lr)) and left " *

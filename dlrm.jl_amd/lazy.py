@@ -24,7 +24,9 @@ DLRMHip.jl's lazy `maplookup` for `HipEmbedding`):
 `HipTables(tables, opt=SplitDescent(η))` on bfloat16 tables is the same chain with the split rule: the
 pullback is dlrm_split_step_bwd(DLRM_STEP_BWD_ONLY), update! with that optimizer its APPLY_ONLY launch.
 `HipTables(tables, opt=ADAGrad(η, ε))` or `opt=RowwiseADAGrad(η, ε)` is the same chain with that Adagrad rule
-(dlrm_adagrad_step_bwd).
+(dlrm_adagrad_step_bwd).  `HipTables(tables, opt=StochasticDescent(η, seed), stochastic_step=True)` on bfloat16
+tables is the same chain with the stochastic rule (dlrm_sr_step_bwd): the optimizer's step word advances after the
+apply launch, run at once or deferred; without the keyword that optimizer takes the operator route.
 
 Three launches per step, bit for bit the result of `HotPath.step` and of the five-launch chain.
 
@@ -61,20 +63,28 @@ class HipTables:
     runs the split rule's backward (dlrm_split_step_bwd) and update! with that same optimizer object runs
     or defers its apply.  opt: an ADAGrad(η, ε) or RowwiseADAGrad(η, ε) likewise (dlrm_adagrad_step_bwd): update!
     takes that optimizer object, with the η and ε it had here.  opt: a StochasticDescent(η, seed) on bfloat16
-    tables takes the operator route (the rule has no fused step): the pullback writes every gradient row and
-    update! with that optimizer object steps every row (dlrm_sr_sgd_update), at once."""
+    tables takes the operator route: the pullback writes every gradient row and update! with that optimizer
+    object steps every row (dlrm_sr_sgd_update), at once -- unless stochastic_step=True, the rule's fused step
+    (dlrm_sr_step_bwd), which behaves as the split rule's: the pullback steps and rounds the once-hit rows and
+    update! with that same optimizer object runs or defers the apply, after which the step word advances."""
 
-    def __init__(self, tables, *, lr=None, index_base=1, defer_update=True, opt=None):
+    def __init__(self, tables, *, lr=None, index_base=1, defer_update=True, opt=None, stochastic_step=False):
         self._ts = as_table_set(tables) if not isinstance(tables, EmbeddingTableSet) else tables
+        self.stochastic_step = bool(stochastic_step)
+        if self.stochastic_step and not isinstance(opt, StochasticDescent):
+            raise ValueError("HipTables: stochastic_step=True is the stochastic rule's fused step "
+                             "(opt=StochasticDescent(eta, seed))")
+        if self.stochastic_step and self._ts.dtype != torch.bfloat16:
+            raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not {self._ts.dtype}")
         if opt is not None:
             if not isinstance(opt, (SplitDescent, StochasticDescent, _AdagradBase)):
                 raise TypeError("HipTables: opt is a SplitDescent, a StochasticDescent, an ADAGrad or a RowwiseADAGrad "
                                 "(Descent: lr=eta)")
-            if isinstance(opt, StochasticDescent):
+            if isinstance(opt, StochasticDescent) and not self.stochastic_step:
                 # the operator route: the pullback writes every dt row and update! steps every row (lr stays None)
                 if lr is not None:
-                    raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}: the stochastic rule has no fused step, "
-                                     "so the pullback steps no row (lr must be None)")
+                    raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}: without stochastic_step=True the rule "
+                                     "takes the operator route, so the pullback steps no row (lr must be None)")
                 if self._ts.dtype != torch.bfloat16:
                     raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not "
                                      f"{self._ts.dtype}")
@@ -159,10 +169,11 @@ class HipTables:
         from .hotpath import HotPath
         hp = self._hp.get(batch)
         if hp is None:
-            stochastic = isinstance(self.opt, StochasticDescent)  # (the operator route: a plain step engine)
+            # (the stochastic rule without its fused step: the operator route, a plain step engine)
+            stochastic = isinstance(self.opt, StochasticDescent) and not self.stochastic_step
             hp = HotPath(self._ts, batch, 1, lr=0.0 if self.lr is None else self.lr, index_base=self.index_base,
                          opt=None if stochastic else self.opt, fused_step=isinstance(self.opt, SplitDescent),
-                         adagrad_step=isinstance(self.opt, _AdagradBase))
+                         adagrad_step=isinstance(self.opt, _AdagradBase), stochastic_step=self.stochastic_step)
             hp.rule_params = self._opt_params
             if stochastic:
                 self.opt.handle_of(self._ts)  # the handle and its step word, allocated before any graph capture

@@ -248,8 +248,10 @@ class StochasticDescent(_StatefulOpt):
     restates a step on the host).  The step is a counter on the device, per table set: 0 at first use, one
     more after every update (a captured update advances it on every replay); `seek(tables, step)` sets it and
     `step_of(tables)` reads it (synchronising).  There is no per-row state, so the rule may be alternated
-    freely with Descent on the same tables.  The operator route only: `HotPath` / `HipTables` take it without
-    the fused step (`pipeline=None`)."""
+    freely with Descent on the same tables.  `HotPath` / `HipTables` take it on the operator route
+    (`pipeline=None`) unless built with `stochastic_step=True`, the fused step with this rule (dlrm_sr_step_bwd):
+    the step backward rounds the once-hit rows itself, both launches of a step read the same value of the
+    counter, and it advances after the apply."""
 
     def __init__(self, eta=0.1, seed=0):
         super().__init__()

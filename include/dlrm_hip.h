@@ -295,9 +295,12 @@ int dlrm_indexer_set_parts(dlrm_ctx* ctx, dlrm_indexer* indexer, int parts);
  * dlrm_split_step_bwd's (the split rule on split-bf16 tables), so only the split rule's apply may
  * complete it; SINGLES_ADAGRAD / SINGLES_ROWWISE, set with it: that backward was
  * dlrm_adagrad_step_bwd's with an element-wise / a row-wise handle, and only an Adagrad apply with a
- * handle of that kind may complete it.  (The Julia shim's pullback state, DLRMHip.jl `st.bwd`.) */
+ * handle of that kind may complete it; SINGLES_STOCHASTIC, set with it: that backward was
+ * dlrm_sr_step_bwd's, and only the stochastic rule's apply with the same dlrm_sr_sgd handle may
+ * complete it.  (The Julia shim's pullback state, DLRMHip.jl `st.bwd`.) */
 enum { DLRM_IX_BUILT = 1, DLRM_IX_SPLIT = 2, DLRM_IX_PREPARED = 4, DLRM_IX_SINGLES_DONE = 8,
-       DLRM_IX_SINGLES_SPLIT = 16, DLRM_IX_SINGLES_ADAGRAD = 32, DLRM_IX_SINGLES_ROWWISE = 64 };
+       DLRM_IX_SINGLES_SPLIT = 16, DLRM_IX_SINGLES_ADAGRAD = 32, DLRM_IX_SINGLES_ROWWISE = 64,
+       DLRM_IX_SINGLES_STOCHASTIC = 128 };
 int dlrm_indexer_state(const dlrm_indexer* indexer, unsigned* state);
 
 /* Backward of a training step without a materialized ys (see above). */
@@ -460,12 +463,15 @@ int dlrm_split_sgd_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_split_sgd* op
  * build's) leaves the tables unwritten.  dlrm_sr_sgd_update: DLRM_UPDATE_PREBUILT is honoured;
  * DLRM_UPDATE_ATOMIC returns DLRM_E_UNSUPPORTED; tables that are not DLRM_BF16 (there is nothing
  * to round), or a handle created for another table count / dim, return DLRM_E_ARG; an indexer in
- * state DLRM_IX_SINGLES_DONE, with any rule's mark, returns DLRM_E_STATE and writes nothing (a step
- * backward has already written the once-hit rows rounded to nearest); a split indexer whose
+ * state DLRM_IX_SINGLES_DONE returns DLRM_E_STATE, writes nothing and leaves the step alone (another
+ * rule's step backward has already written the once-hit rows rounded to nearest) -- unless
+ * DLRM_IX_SINGLES_STOCHASTIC says that dlrm_sr_step_bwd stepped them with this handle, in which case
+ * the repeated rows are applied (another handle's: DLRM_E_STATE); a split indexer whose
  * singles are not done is taken whole, once-hit rows included.  The rule keeps no per-row state,
  * so it may be alternated freely with dlrm_sgd_update on the same tables.  Launches neither
  * allocate nor synchronise beyond what dlrm_sgd_update does, so the call is graph-capturable.
- * dlrm_sr_sgd_destroy of NULL returns 0.  There is no fused training step with this rule yet. */
+ * dlrm_sr_sgd_destroy of NULL returns 0.  The fused training step with this rule is dlrm_sr_step_bwd
+ * (below). */
 typedef struct dlrm_sr_sgd dlrm_sr_sgd; /* the seed and the device step word */
 int dlrm_sr_sgd_create(dlrm_ctx* ctx, const dlrm_tables* tables, int64_t seed, dlrm_sr_sgd** out);
 int dlrm_sr_sgd_destroy(dlrm_sr_sgd* opt);
@@ -594,6 +600,46 @@ int dlrm_adagrad_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagr
                                   const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
                                   float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr, float eps,
                                   dlrm_indexer* next_indexer, const void* next_indices, unsigned flags);
+
+/* ---- the training step with the stochastic rule (see "stochastically rounded SGD" above):
+ * dlrm_step_bwd and dlrm_step_bwd_prepare with that rule in place of Descent on DLRM_BF16 tables,
+ * after the same forward.
+ *   dlrm_sr_step_bwd = dlrm_interact_bwd_gather + dlrm_sr_sgd_update(opt, PREBUILT): dx is
+ *   bit-identical to dlrm_interact_bwd_gather's and every touched row ends up bit-identical to
+ *   dlrm_sr_sgd_update's at the same (seed, step).  A once-hit row is stepped inside the backward:
+ *   w = sr_bf16(fmaf(-lr, 0 + g, w), R) with the R of (seed, step, t, r, c) defined above, generated
+ *   at the write; its dt row is never written.  The apply launch steps the repeated rows from their
+ *   dt rows with the same rule.
+ * The step: one training step is one value of the handle's word.  The backward launch and the apply
+ * launch read the same value; the word advances by one, on the device and in stream order, after
+ * the launch that runs the apply -- flags 0, DLRM_STEP_APPLY_ONLY, or dlrm_sr_sgd_update(PREBUILT)
+ * completing a DLRM_STEP_BWD_ONLY backward.  DLRM_STEP_BWD_ONLY alone does not advance it.  As for
+ * dlrm_sr_sgd_update it advances when the call returned DLRM_OK and launched (also under a raised
+ * bounds flag, which leaves every row unwritten), not on an argument or state error; nothing
+ * synchronises, and a captured step advances it on every replay.
+ * Arguments, flags, alignment rules and fallbacks are dlrm_step_bwd's: a shape without a split
+ * backward (F > 32, x or rows not 16-B aligned) and a feature size whose backward has no form with
+ * this rule (dim other than 128 and not <= 64) run dlrm_interact_bwd_gather and let the rule's
+ * apply take the once-hit rows -- the same bits, since R does not depend on the launch that writes
+ * a row; dlrm_sr_step_bwd_prepare on a shape without an in-apply build, these included, runs the
+ * plain step.  Tables that are not DLRM_BF16, or a handle created for another table count / dim,
+ * return DLRM_E_ARG.
+ * The indexer remembers the rule and the handle that stepped its once-hit rows
+ * (DLRM_IX_SINGLES_STOCHASTIC), and only that handle completes the backward, through
+ * dlrm_sr_step_bwd(APPLY_ONLY) or dlrm_sr_sgd_update(PREBUILT), which then applies the repeated
+ * rows.  Every pairing with dlrm_step_bwd, dlrm_split_step_bwd, dlrm_adagrad_step_bwd or their
+ * dlrm_*_update(PREBUILT), in either direction, another dlrm_sr_sgd handle, and a second backward
+ * on one build return DLRM_E_STATE, launch nothing and leave the step alone. */
+int dlrm_sr_step_bwd(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_sr_sgd* opt, dlrm_indexer* indexer,
+                     const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                     const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
+                     float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr, unsigned flags);
+int dlrm_sr_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_sr_sgd* opt,
+                             dlrm_indexer* indexer,
+                             const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                             const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
+                             float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr,
+                             dlrm_indexer* next_indexer, const void* next_indices, unsigned flags);
 
 /* ---- table-sharded exchange over RCCL ------------------------------------
  * DLRM.jl is one process: maplookup hands its output straight to the interaction (model.jl:161-163).
