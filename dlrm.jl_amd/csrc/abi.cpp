@@ -1,8 +1,9 @@
 // abi.cpp — the extern "C" boundary declared in include/dlrm_hip.h.
 //
-// Owns the three handle types (ctx, tables, indexer), validates arguments on the host,
+// Owns the handle types (ctx, tables, indexer, the optimizers'), validates arguments on the host,
 // maps HIP errors to dlrm_status codes and forwards to the kernel launchers.  No launching
-// entry point allocates or synchronises (hipGraph-capturable).
+// entry point allocates or synchronises (hipGraph-capturable).  An optimizer rule is described
+// once, in kRules; the entry points bind it to their call (bind_rule) and pass that down.
 #include <dlfcn.h>
 #include <execinfo.h>
 #include <hip/hip_runtime.h>
@@ -67,11 +68,67 @@ struct dlrm_sr_sgd : StateDims {
     uint64_t* d_step = nullptr;
 };
 
-// The rule that stepped a split build's once-hit rows inside the step backward, and its bit of dlrm_indexer_state
-enum { kRuleDescent = 0, kRuleSplit = 1, kRuleAdagrad = 2, kRuleRowwise = 3,
-       kRuleStochastic = 4 /* (dlrm_sr_step_bwd: the indexer also remembers the handle, singles_sr) */ };
-static const unsigned kRuleBits[5] = {0u, DLRM_IX_SINGLES_SPLIT, DLRM_IX_SINGLES_ADAGRAD, DLRM_IX_SINGLES_ROWWISE,
-                                      DLRM_IX_SINGLES_STOCHASTIC};
+// An optimizer rule on the host: what every call site asks of one, indexed by kRule* (common.hpp).  The arithmetic
+// is the units' (apply.hpp, interact.hip); a rule bound to a call is a BoundRule.
+struct RuleDesc {
+    const char* update_fn;  // its entry points, for the messages: the update ...
+    const char* step_fn;    // ... and the training step's backward (its _prepare form: the same with the suffix)
+    const char* name;       // the rule in words
+    const char* made;       // its handle in words ("... created for %d tables"); NULL: none
+    const char* bf16_only;  // why its tables are bfloat16; NULL: fp32 too
+    const char* no_atomic;  // why it has no atomic mode (an atomic add never holds a row's whole sum or step); NULL:
+                            // it has one
+    unsigned bit;           // of dlrm_indexer_state, when its step backward stepped a build's once-hit rows
+    ApplyFn* apply;         // the update's apply launch
+    ApplyFn* step_apply;    // the training step's
+};
+static const RuleDesc kRules[kNumRules] = {
+    {"dlrm_sgd_update", "dlrm_step_bwd", "Descent", nullptr, nullptr, nullptr, 0u, launch_sgd_apply, launch_sgd_apply},
+    {"dlrm_split_sgd_update", "dlrm_split_step_bwd", "the split rule", "the low halves were",
+     "split tables are bf16 (the high halves)", "a row's two halves are stepped together", DLRM_IX_SINGLES_SPLIT,
+     launch_split_sgd_apply, launch_split_step_apply},
+    // (the two Adagrad rules share their entry points: the kind comes from the handle)
+    {"dlrm_adagrad_update", "dlrm_adagrad_step_bwd", "the element-wise Adagrad rule", "the optimizer state was", nullptr,
+     "the rule needs each row's complete sum", DLRM_IX_SINGLES_ADAGRAD, launch_adagrad_apply, launch_adagrad_step_apply},
+    {"dlrm_adagrad_update", "dlrm_adagrad_step_bwd", "the row-wise Adagrad rule", "the optimizer state was", nullptr,
+     "the rule needs each row's complete sum", DLRM_IX_SINGLES_ROWWISE, launch_rowwise_adagrad_apply,
+     launch_rowwise_adagrad_step_apply},
+    {"dlrm_sr_sgd_update", "dlrm_sr_step_bwd", "the stochastic rule", "the optimizer was",
+     "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule rounds each row's complete step once",
+     DLRM_IX_SINGLES_STOCHASTIC, launch_sr_sgd_apply, launch_sr_step_apply},
+};
+
+// The rule of a call, from its handle and scalars
+static BoundRule bind_rule(float lr) {
+    BoundRule r;
+    r.lr = lr;
+    return r;
+}
+static BoundRule bind_rule(const dlrm_split_sgd* op, float lr) {
+    BoundRule r = bind_rule(lr);
+    r.kind = kRuleSplit;
+    r.state = op->d_ptr;
+    r.aligned16 = op->aligned16;
+    r.handle = op;
+    return r;
+}
+static BoundRule bind_rule(const dlrm_adagrad* op, float lr, float eps) {
+    BoundRule r = bind_rule(lr);
+    r.kind = op->rowwise ? kRuleRowwise : kRuleAdagrad;
+    r.eps = eps;
+    r.state = op->d_ptr;
+    r.aligned16 = op->rowwise || op->aligned16;  // (a row-wise state word is loaded alone)
+    r.handle = op;
+    return r;
+}
+static BoundRule bind_rule(const dlrm_sr_sgd* op, float lr) {
+    BoundRule r = bind_rule(lr);
+    r.kind = kRuleStochastic;
+    r.seed = op->seed;
+    r.step = op->d_step;
+    r.handle = op;
+    return r;
+}
 
 struct dlrm_indexer {
     dlrm_ctx* ctx = nullptr;
@@ -87,9 +144,8 @@ struct dlrm_indexer {
     bool split = false;  // built by dlrm_step_fwd's kernel: once-hit rows are left to the backward
     bool prepared = false;  // built by dlrm_step_bwd_prepare for the next dlrm_step_fwd (not yet consumed)
     bool singles_done = false;  // a split backward has applied this build's once-hit rows already
-    int singles_rule = 0;  // ... with this rule (kRule*): Descent, or the rule of dlrm_split_step_bwd / dlrm_adagrad_step_bwd
-                           // / dlrm_sr_step_bwd
-    const dlrm_sr_sgd* singles_sr = nullptr;  // kRuleStochastic: the handle whose seed and step rounded those rows
+    int singles_rule = 0;  // ... with this rule (kRule*) ...
+    const StateDims* singles_handle = nullptr;  // ... bound to this handle (check_completes)
     // device words for the bounds errors of builds that may run beside a step's write-deciding
     // kernels, which read the ctx's flag to decide whether to write (raising there would be a race,
     // ADVICE r5): [0] dlrm_indexer_prepare (a side-stream build beside the current step; cleared
@@ -171,7 +227,7 @@ static void record_build(dlrm_indexer* ix, bool split, const void* indices, int 
     ix->prepared = false;
     ix->singles_done = false;
     ix->singles_rule = kRuleDescent;
-    ix->singles_sr = nullptr;
+    ix->singles_handle = nullptr;
     ix->dev.has_map = 0;  // (set by dlrm_step_bwd_prepare, whose wave build writes the item map)
     ix->dev.build_err = nullptr;  // (set by dlrm_indexer_prepare)
     ix->indices = indices;
@@ -755,7 +811,7 @@ static int indexer_carve(dlrm_ctx* ctx, dlrm_indexer* ix, int parts) {
     ix->bytes = total;
     ix->built = ix->prepared = ix->singles_done = false;
     ix->singles_rule = kRuleDescent;
-    ix->singles_sr = nullptr;
+    ix->singles_handle = nullptr;
     ix->dev.has_map = 0;
     ix->dev.build_err = nullptr;
     return DLRM_OK;
@@ -974,7 +1030,7 @@ int dlrm_indexer_state(const dlrm_indexer* ix, unsigned* state) {
     if (!ix || !state) return DLRM_E_ARG;
     *state = (ix->built ? DLRM_IX_BUILT : 0u) | (ix->split ? DLRM_IX_SPLIT : 0u) |
              (ix->prepared ? DLRM_IX_PREPARED : 0u) | (ix->singles_done ? DLRM_IX_SINGLES_DONE : 0u) |
-             (ix->singles_done ? kRuleBits[ix->singles_rule] : 0u);
+             (ix->singles_done ? kRules[ix->singles_rule].bit : 0u);
     return DLRM_OK;
 }
 
@@ -1034,104 +1090,71 @@ static int ensure_partials(dlrm_ctx* ctx, dlrm_indexer* ix, int D) {
     return DLRM_OK;
 }
 
-// What the update entry points differ in before their launch.
-struct UpdateRule {
-    const char* fn;            // the entry point, for the messages
-    bool bf16_only;            // split tables
-    const char* made;          // its state handle in words; NULL: none
-    const char* no_atomic;     // why the rule has no atomic mode; NULL: it has one
-    const char* singles_done;  // how a split backward stepped the once-hit rows, which the rule cannot take over;
-                               // NULL: it skips them (their dt rows are all the backward left unwritten)
-    int rule;                  // kRule*: it completes the step backward of its own rule, and no other does
-};
-static const UpdateRule kSgdUpdate = {"dlrm_sgd_update", false, nullptr, nullptr, nullptr, kRuleDescent};
-// (an atomic add never holds the row's whole sum, which the rule squares; a split backward stepped its once-hit
-// rows with Descent and left their dt rows unwritten)
-static const UpdateRule kAdagradUpdate = {"dlrm_adagrad_update", false, "the optimizer state was",
-                                          "the rule needs each row's complete sum", "Descent", kRuleAdagrad};
-// (the same entry point with a row-wise handle: the rule's kind comes from the handle)
-static const UpdateRule kRowwiseUpdate = {"dlrm_adagrad_update", false, "the optimizer state was",
-                                          "the rule needs each row's complete sum", "Descent", kRuleRowwise};
-// (an atomic add on one half cannot carry into the other; a split backward wrote its once-hit rows' high halves
-// with a rounded bf16 step and left their dt rows unwritten -- but dlrm_split_step_bwd's backward stepped them
-// with this rule, and then the update takes the repeated rows that are left)
-static const UpdateRule kSplitUpdate = {"dlrm_split_sgd_update", true, "the low halves were",
-                                        "a row's two halves are stepped together", "a rounded bf16 Descent", kRuleSplit};
+// The rule's handle against the tables (the argument errors of the rule's update and of its training step)
+static int check_rule(dlrm_ctx* ctx, const dlrm_tables* tb, const BoundRule& r, const char* fn) {
+    const RuleDesc& d = kRules[r.kind];
+    CHECK_ARG(!d.bf16_only || tb->dtype == DLRM_BF16, "%s: %s", fn, d.bf16_only);
+    CHECK_ARG(!r.handle || (r.handle->T == tb->T && r.handle->D == tb->D), "%s: %s created for %d tables of dim %d", fn,
+              d.made, r.handle ? r.handle->T : 0, r.handle ? r.handle->D : 0);
+    return DLRM_OK;
+}
 
-// The common part of the update entry points, from the index checks to the indexer's build: sa = the
-// launch's once-hit items.  *atomic: DLRM_UPDATE_ATOMIC of a rule that has the mode (nothing is built).
-static int update_prologue(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const UpdateRule& r, const StateDims* op,
-                           unsigned flags,
-                           const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
-                           const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset, SinglesArgs* sa,
-                           bool* atomic) {
-    *atomic = false;
+// Who may complete whose backward.  A split backward stepped the build's once-hit rows with its rule and left their dt
+// rows unwritten: only the same rule finishes what it started (dlrm_*_update(PREBUILT) and dlrm_*step_bwd(APPLY_ONLY)
+// alike) -- another rule's rows hold another step -- and for the stochastic rule only the same handle: another one has
+// another seed or step.
+static int check_completes(dlrm_ctx* ctx, const dlrm_indexer* ix, const BoundRule& r, const char* fn, const char* mode) {
+    if (!ix->singles_done) return DLRM_OK;
+    const bool same_rule = ix->singles_rule == r.kind;
+    if (same_rule && (r.kind != kRuleStochastic || ix->singles_handle == r.handle)) return DLRM_OK;
+    const RuleDesc& by = kRules[ix->singles_rule];
+    return ctx_fail(ctx, DLRM_E_STATE, "%s%s: a split backward (%s) already stepped this build's once-hit rows with %s%s",
+                    fn, mode, by.step_fn, by.name, same_rule ? " of another handle" : "");
+}
+
+// The update entry points, from the index checks to the rule's launch.
+static int rule_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const BoundRule& r, unsigned flags,
+                       const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
+                       const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset) {
+    const RuleDesc& d = kRules[r.kind];
+    const char* const fn = d.update_fn;
     int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, lookups);
+    if (rc == DLRM_OK) rc = check_rule(ctx, tb, r, fn);
     if (rc) return rc;
-    CHECK_ARG(!r.bf16_only || tb->dtype == DLRM_BF16, "%s: split tables are bf16 (the high halves)", r.fn);
-    CHECK_ARG(!op || (op->T == tb->T && op->D == tb->D), "%s: %s created for %d tables of dim %d", r.fn, r.made,
-              op ? op->T : 0, op ? op->D : 0);
-    CHECK_ARG(grad_dtype == DLRM_F32 || grad_dtype == DLRM_BF16, "%s: grad dtype %d", r.fn, grad_dtype);
-    CHECK_ARG(grad_offset >= 0 && grad_ld >= grad_offset + (int64_t)tb->T * tb->D, "%s: grad_ld too small", r.fn);
-    CHECK_ARG(batch == 0 || tb->T == 0 || grad, "%s: null grad", r.fn);
-    if (flags & DLRM_UPDATE_ATOMIC) {
-        if (r.no_atomic) return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no atomic mode (%s)", r.fn, r.no_atomic);
-        *atomic = true;
-        return DLRM_OK;
+    CHECK_ARG(grad_dtype == DLRM_F32 || grad_dtype == DLRM_BF16, "%s: grad dtype %d", fn, grad_dtype);
+    CHECK_ARG(grad_offset >= 0 && grad_ld >= grad_offset + (int64_t)tb->T * tb->D, "%s: grad_ld too small", fn);
+    CHECK_ARG(batch == 0 || tb->T == 0 || grad, "%s: null grad", fn);
+    if (flags & DLRM_UPDATE_ATOMIC) {  // (nothing is built)
+        if (d.no_atomic) return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no atomic mode (%s)", fn, d.no_atomic);
+        if (tb->dtype != DLRM_F32) return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: atomic mode needs fp32 tables", fn);
+        return launch_sgd_atomic(ctx, tb->d_desc, tb->T, tb->D, indices, itype, table_stride, index_base, batch,
+                                 lookups, grad, grad_dtype, grad_ld, grad_offset, r.lr);  // (Descent: no other has the mode)
     }
-    CHECK_ARG(ix, "%s: deterministic mode needs an indexer", r.fn);
+    CHECK_ARG(ix, "%s: deterministic mode needs an indexer", fn);
     if (flags & DLRM_UPDATE_PREBUILT) {
         if (!built_from(ix, indices, itype, table_stride, index_base, batch, lookups))
-            return ctx_fail(ctx, DLRM_E_STATE, "%s: indexer was not built from these indices", r.fn);
-        // only the rule that stepped a build's once-hit rows applies its repeated rows
-        if (ix->singles_done && ix->singles_rule == kRuleSplit && r.rule != kRuleSplit)
-            return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_split_step_bwd) already stepped this build's "
-                            "once-hit rows with the split rule", r.fn);
-        if (ix->singles_done && ix->singles_rule == kRuleDescent && r.singles_done)
-            return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_step_bwd) already stepped this build's "
-                            "once-hit rows with %s", r.fn, r.singles_done);
-        if (ix->singles_done && (ix->singles_rule == kRuleAdagrad || ix->singles_rule == kRuleRowwise) &&
-            r.rule != ix->singles_rule)
-            return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_adagrad_step_bwd) already stepped this build's "
-                            "once-hit rows with the %s Adagrad rule", r.fn,
-                            ix->singles_rule == kRuleRowwise ? "row-wise" : "element-wise");
-        // (the stochastic rule: the handle too -- another one has another seed or step)
-        if (ix->singles_done && ix->singles_rule == kRuleStochastic &&
-            (r.rule != kRuleStochastic || ix->singles_sr != op))
-            return ctx_fail(ctx, DLRM_E_STATE, "%s: a split backward (dlrm_sr_step_bwd) already stepped this build's "
-                            "once-hit rows with the stochastic rule%s", r.fn,
-                            r.rule == kRuleStochastic ? " of another handle" : "");
+            return ctx_fail(ctx, DLRM_E_STATE, "%s: indexer was not built from these indices", fn);
+        rc = check_completes(ctx, ix, r, fn, "");
     } else {
         rc = dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, lookups);
-        if (rc) return rc;
     }
-    rc = ensure_partials(ctx, ix, tb->D);
+    if (rc == DLRM_OK) rc = ensure_partials(ctx, ix, tb->D);
     if (rc) return rc;
     // a split indexer (dlrm_indexer_build's default form, or dlrm_step_fwd's): its once-hit
     // positions are this launch's too -- unless a split backward (dlrm_step_bwd) has updated them
     // already, in which case only the repeated rows are left
-    *sa = SinglesArgs{(ix->split && !ix->singles_done) ? ix->dev.single : nullptr, indices, itype, table_stride,
-                      index_base, batch * lookups};
-    return DLRM_OK;
+    const SinglesArgs sa{(ix->split && !ix->singles_done) ? ix->dev.single : nullptr, indices, itype, table_stride,
+                         index_base, batch * lookups};
+    return d.apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && r.aligned16, tb->T, tb->D, tb->dtype, lookups,
+                   (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, r, sa, nullptr);
 }
 
 int dlrm_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, unsigned flags, const void* indices, int itype,
                     int64_t table_stride, int index_base, int batch, int lookups, const void* grad, int grad_dtype,
                     int64_t grad_ld, int64_t grad_offset, float lr) {
     CHECK_ARG(ctx && tb, "dlrm_sgd_update: null ctx/tables");
-    SinglesArgs sa;
-    bool atomic;
-    const int rc = update_prologue(ctx, tb, ix, kSgdUpdate, nullptr, flags, indices, itype, table_stride, index_base, batch,
-                                   lookups, grad, grad_dtype, grad_ld, grad_offset, &sa, &atomic);
-    if (rc) return rc;
-    if (atomic) {
-        if (tb->dtype != DLRM_F32)
-            return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_sgd_update: atomic mode needs fp32 tables");
-        return launch_sgd_atomic(ctx, tb->d_desc, tb->T, tb->D, indices, itype, table_stride, index_base, batch,
-                                 lookups, grad, grad_dtype, grad_ld, grad_offset, lr);
-    }
-    return launch_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, tb->T, tb->D, tb->dtype, lookups,
-                            (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr, sa);
+    return rule_update(ctx, tb, ix, bind_rule(lr), flags, indices, itype, table_stride, index_base, batch, lookups, grad,
+                       grad_dtype, grad_ld, grad_offset);
 }
 
 // ------------------------------------------------- optimizers with state: sparse Adagrad, split-bf16 tables
@@ -1147,18 +1170,8 @@ int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_i
                         const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
                         const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset, float lr, float eps) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_adagrad_update: null ctx/tables/optimizer/indexer");
-    SinglesArgs sa;
-    bool atomic;
-    const int rc = update_prologue(ctx, tb, ix, op->rowwise ? kRowwiseUpdate : kAdagradUpdate, op, flags, indices, itype, table_stride, index_base, batch,
-                                   lookups, grad, grad_dtype, grad_ld, grad_offset, &sa, &atomic);
-    if (rc) return rc;
-    if (op->rowwise)
-        return launch_rowwise_adagrad_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, op->d_ptr, tb->T, tb->D, tb->dtype,
-                                            lookups, (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset,
-                                            lr, eps, sa);
-    return launch_adagrad_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_ptr, tb->T, tb->D,
-                                tb->dtype, lookups, (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr,
-                                eps, sa);
+    return rule_update(ctx, tb, ix, bind_rule(op, lr, eps), flags, indices, itype, table_stride, index_base, batch, lookups,
+                       grad, grad_dtype, grad_ld, grad_offset);
 }
 
 int dlrm_split_sgd_create(dlrm_ctx* ctx, const dlrm_tables* tb, uint16_t* const* lo, dlrm_split_sgd** out) {
@@ -1171,20 +1184,9 @@ int dlrm_split_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dl
                           const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
                           const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset, float lr) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_split_sgd_update: null ctx/tables/optimizer/indexer");
-    SinglesArgs sa;
-    bool atomic;
-    const int rc = update_prologue(ctx, tb, ix, kSplitUpdate, op, flags, indices, itype, table_stride, index_base, batch,
-                                   lookups, grad, grad_dtype, grad_ld, grad_offset, &sa, &atomic);
-    if (rc) return rc;
-    return launch_split_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_ptr, tb->T, tb->D, lookups,
-                                  (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr, sa);
+    return rule_update(ctx, tb, ix, bind_rule(op, lr), flags, indices, itype, table_stride, index_base, batch, lookups, grad,
+                       grad_dtype, grad_ld, grad_offset);
 }
-
-// (an atomic add rounds every addend, not the row's step; another rule's step backward rounded its once-hit rows to
-// nearest, and this rule completes none of those -- but dlrm_sr_step_bwd's backward stepped them with this rule, and
-// then the update with the same handle takes the repeated rows that are left)
-static const UpdateRule kSrUpdate = {"dlrm_sr_sgd_update", false, "the optimizer was",
-                                     "the rule rounds each row's complete step once", "another rule", kRuleStochastic};
 
 int dlrm_sr_sgd_create(dlrm_ctx* ctx, const dlrm_tables* tb, int64_t seed, dlrm_sr_sgd** out) {
     CHECK_ARG(ctx && tb && out, "dlrm_sr_sgd_create: null argument");
@@ -1221,14 +1223,8 @@ int dlrm_sr_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_sr_sgd* op, dlrm_ind
                        const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
                        const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset, float lr) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_sr_sgd_update: null ctx/tables/optimizer/indexer");
-    CHECK_ARG(tb->dtype == DLRM_BF16, "dlrm_sr_sgd_update: stochastic rounding is of bf16 tables (fp32: nothing to round)");
-    SinglesArgs sa;
-    bool atomic;
-    const int rc = update_prologue(ctx, tb, ix, kSrUpdate, op, flags, indices, itype, table_stride, index_base, batch,
-                                   lookups, grad, grad_dtype, grad_ld, grad_offset, &sa, &atomic);
-    if (rc) return rc;
-    return launch_sr_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, op->seed, op->d_step, tb->T, tb->D, lookups,
-                               (int64_t)batch * lookups, grad, grad_dtype, grad_ld, grad_offset, lr, sa);
+    return rule_update(ctx, tb, ix, bind_rule(op, lr), flags, indices, itype, table_stride, index_base, batch, lookups, grad,
+                       grad_dtype, grad_ld, grad_offset);
 }
 
 int dlrm_sr_sgd_seek(dlrm_ctx* ctx, dlrm_sr_sgd* op, int64_t step) {
@@ -1333,103 +1329,60 @@ int dlrm_step_fwd(dlrm_ctx* ctx, const dlrm_tables* tb, dlrm_indexer* ix, const 
     return dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, 1);
 }
 
-// The once-hit rule of a training step's backward and apply: Descent (dlrm_step_bwd), the split rule on
-// split-bf16 tables (dlrm_split_step_bwd), a sparse Adagrad rule (dlrm_adagrad_step_bwd; element-wise or
-// row-wise by its handle) or the stochastic rule on bf16 tables (dlrm_sr_step_bwd).  An indexer remembers which one
-// stepped its once-hit rows (singles_rule; the stochastic rule: and with which handle, singles_sr), and only
-// the same rule's apply completes that backward.
-struct StepRule {
-    const char* fn;              // the entry point, for the messages
-    int kind = kRuleDescent;     // kRule*
-    dlrm_split_sgd* op = nullptr;   // kRuleSplit: the low halves
-    dlrm_adagrad* ada = nullptr;    // kRuleAdagrad / kRuleRowwise: the state
-    float eps = 0.0f;               // ... and the rule's epsilon
-    dlrm_sr_sgd* sr = nullptr;      // kRuleStochastic: the seed and the step word
-};
-// who stepped a build's once-hit rows, for the messages
-static const char* const kRuleNames[5] = {"dlrm_step_bwd (Descent)", "dlrm_split_step_bwd (the split rule)",
-                                          "dlrm_adagrad_step_bwd (the element-wise Adagrad rule)",
-                                          "dlrm_adagrad_step_bwd (the row-wise Adagrad rule)",
-                                          "dlrm_sr_step_bwd (the stochastic rule)"};
+// The training step's backward and apply under a rule: Descent (dlrm_step_bwd), the split rule on split-bf16 tables
+// (dlrm_split_step_bwd), a sparse Adagrad rule (dlrm_adagrad_step_bwd; element-wise or row-wise by its handle) or the
+// stochastic rule on bf16 tables (dlrm_sr_step_bwd).  An indexer remembers which rule, bound to which handle, stepped
+// its once-hit rows, and only that one's apply completes the backward (check_completes).
 
-static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* indices, int itype,
-                         int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
+// Whether the shape has the rule's split backward (once-hit rows stepped there): the shapes of the split kernels, the
+// rule's second stream in 16-B aligned rows (the split rule's backward loads the low halves as 8-B or 16-B vectors,
+// the element-wise Adagrad rule's its state rows as 16-B vectors), and the rule's once-hit write for the feature sizes
+static bool has_split_bwd(const dlrm_tables* tb, const BoundRule& r, const void* x, int64_t x_ld) {
+    return step_split_supported(tb->aligned16, tb->T, tb->dtype, tb->D, x, x_ld) && r.aligned16 &&
+           step_bwd_supported(r.kind, tb->dtype, tb->T, tb->D);
+}
+
+static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const BoundRule& r, const void* indices,
+                         int itype, int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
                          const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
-                         int64_t dt_ld, float lr, unsigned flags, const PrepArgs* prep,
-                         const StepRule& rule = StepRule{"dlrm_step_bwd"}) {
-    CHECK_ARG(ctx && tb && ix, "%s: null ctx/tables/indexer", rule.fn);
-    dlrm_split_sgd* const op = rule.op;
-    dlrm_adagrad* const ada = rule.ada;
-    dlrm_sr_sgd* const sr = rule.sr;
+                         int64_t dt_ld, unsigned flags, const PrepArgs* prep) {
+    const char* const fn = kRules[r.kind].step_fn;
     int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, 1);
+    if (rc == DLRM_OK) rc = check_rule(ctx, tb, r, fn);  // (the argument errors of the rule's update)
     if (rc) return rc;
-    if (sr) {  // (dlrm_sr_sgd_update's argument errors)
-        CHECK_ARG(tb->dtype == DLRM_BF16, "%s: stochastic rounding is of bf16 tables (fp32: nothing to round)", rule.fn);
-        CHECK_ARG(sr->T == tb->T && sr->D == tb->D, "%s: the optimizer was created for %d tables of dim %d", rule.fn,
-                  sr->T, sr->D);
-    }
-    if (op) {  // (dlrm_split_sgd_update's argument errors)
-        CHECK_ARG(tb->dtype == DLRM_BF16, "%s: split tables are bf16 (the high halves)", rule.fn);
-        CHECK_ARG(op->T == tb->T && op->D == tb->D, "%s: the low halves were created for %d tables of dim %d", rule.fn,
-                  op->T, op->D);
-    }
-    if (ada)  // (dlrm_adagrad_update's)
-        CHECK_ARG(ada->T == tb->T && ada->D == tb->D, "%s: the optimizer state was created for %d tables of dim %d",
-                  rule.fn, ada->T, ada->D);
     const int d = tb->D, F = tb->T + 1;
     const int64_t P = (int64_t)F * (F - 1) / 2;
     CHECK_ARG(padding >= 0 && x_ld >= d && dout_ld >= d + P + padding && dx_ld >= d && dt_ld >= (int64_t)F * d,
-              "%s: leading dimensions too small", rule.fn);
-    CHECK_ARG(batch == 0 || (x && dout && dx && dt), "%s: null buffer", rule.fn);
+              "%s: leading dimensions too small", fn);
+    CHECK_ARG(batch == 0 || (x && dout && dx && dt), "%s: null buffer", fn);
     if (!built_from(ix, indices, itype, table_stride, index_base, batch, 1))
-        return ctx_fail(ctx, DLRM_E_STATE, "%s: the indexer was not built by dlrm_step_fwd from these indices", rule.fn);
-    CHECK_ARG(flags != (DLRM_STEP_BWD_ONLY | DLRM_STEP_APPLY_ONLY), "%s: flags %u", rule.fn, flags);
+        return ctx_fail(ctx, DLRM_E_STATE, "%s: the indexer was not built by dlrm_step_fwd from these indices", fn);
+    CHECK_ARG(flags != (DLRM_STEP_BWD_ONLY | DLRM_STEP_APPLY_ONLY), "%s: flags %u", fn, flags);
     rc = ensure_partials(ctx, ix, tb->D);
     if (rc) return rc;
     // the split backward (once-hit rows updated there) where the shape has it; otherwise the
     // gather backward writes every dt row and the apply takes a split indexer's once-hit rows too
-    // (the split rule: its backward loads the low halves as 8-B or 16-B vectors; the element-wise Adagrad rule its
-    // state rows as 16-B vectors; an Adagrad rule: the feature sizes whose backward has its once-hit write)
-    const bool split_bwd = ix->split && step_split_supported(tb->aligned16, tb->T, tb->dtype, d, x, x_ld) &&
-                           (!op || op->aligned16) &&
-                           (!ada || ((ada->rowwise || ada->aligned16) && adagrad_step_bwd_supported(ada->rowwise, tb->dtype, tb->T, d))) &&
-                           (!sr || sr_step_bwd_supported(tb->T, d));
+    const bool split_bwd = ix->split && has_split_bwd(tb, r, x, x_ld);
     if (flags & DLRM_STEP_APPLY_ONLY) {
         // the apply of a split build only completes a backward that stepped the once-hit rows
         if (split_bwd && !ix->singles_done)
-            return ctx_fail(ctx, DLRM_E_STATE, "%s(APPLY_ONLY): no backward has run on this build", rule.fn);
-        // ... with this rule: the other one's once-hit rows hold another step
-        if (ix->singles_done && ix->singles_rule != rule.kind)
-            return ctx_fail(ctx, DLRM_E_STATE, "%s(APPLY_ONLY): this build's once-hit rows were stepped by %s", rule.fn,
-                            kRuleNames[ix->singles_rule]);
-        // ... and, the stochastic rule, with this handle's seed and step
-        if (ix->singles_done && sr && ix->singles_sr != sr)
-            return ctx_fail(ctx, DLRM_E_STATE, "%s(APPLY_ONLY): this build's once-hit rows were stepped with another "
-                            "dlrm_sr_sgd handle", rule.fn);
-        rc = DLRM_OK;
+            return ctx_fail(ctx, DLRM_E_STATE, "%s(APPLY_ONLY): no backward has run on this build", fn);
+        rc = check_completes(ctx, ix, r, fn, "(APPLY_ONLY)");
     } else if (split_bwd) {
         // a second backward on one build would step its once-hit rows twice
         if (ix->singles_done)
             return ctx_fail(ctx, DLRM_E_STATE,
                             "%s: this build's once-hit rows were already stepped (one backward per "
-                            "dlrm_step_fwd)", rule.fn);
+                            "dlrm_step_fwd)", fn);
         CHECK_ARG((uintptr_t)dx % 16 == 0 && (uintptr_t)dt % 16 == 0 && dx_ld % 4 == 0 && dt_ld % 4 == 0,
-                  "%s: dx and dt must be 16-B aligned with leading dimensions divisible by 4", rule.fn);
-        if (sr)  // (reads the handle's step word; the launch that runs the apply advances it)
-            rc = launch_sr_step_bwd(ctx, tb->d_desc, tb->T, indices, itype, table_stride, index_base, d, batch, x, x_ld,
-                                    dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, lr, sr->seed, sr->d_step);
-        else if (ada)
-            rc = launch_adagrad_step_bwd(ctx, tb->d_desc, tb->T, tb->dtype, indices, itype, table_stride, index_base, d,
-                                         batch, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, lr, rule.eps,
-                                         ada->rowwise, ada->d_ptr);
-        else
-            rc = launch_step_bwd(ctx, tb->d_desc, tb->T, tb->dtype, indices, itype, table_stride, index_base, d, batch, x,
-                                 x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, lr, tb->h_desc.data(),
-                                 op ? op->d_ptr : nullptr);
+                  "%s: dx and dt must be 16-B aligned with leading dimensions divisible by 4", fn);
+        // (the stochastic rule: reads the handle's step word; the launch that runs the apply advances it)
+        rc = launch_step_bwd(ctx, tb->d_desc, tb->T, tb->dtype, indices, itype, table_stride, index_base, d, batch, x,
+                             x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, ix->dev, r);
         if (rc == DLRM_OK) {
             ix->singles_done = true;
-            ix->singles_rule = rule.kind;
-            ix->singles_sr = sr;
+            ix->singles_rule = r.kind;
+            ix->singles_handle = r.handle;
         }
     } else {
         rc = launch_interact_bwd_gather(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
@@ -1440,37 +1393,18 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
     // them as chunks)
     const SinglesArgs sa{(ix->split && !split_bwd) ? ix->dev.single : nullptr, indices, itype, table_stride,
                          index_base, batch};
-    if (sr)  // (... and the one-thread advance of the step word, after the launch that read it)
-        return launch_sr_step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, sr->seed, sr->d_step, tb->T, tb->D,
-                                    (int64_t)batch, dt, dt_ld, d, lr, sa, prep);
-    if (op)
-        return launch_split_step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && op->aligned16, op->d_ptr, tb->T, tb->D,
-                                       (int64_t)batch, dt, dt_ld, d, lr, sa, prep);
-    if (ada && ada->rowwise)
-        return launch_rowwise_adagrad_step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, ada->d_ptr, tb->T, tb->D,
-                                                 tb->dtype, (int64_t)batch, dt, dt_ld, d, lr, rule.eps, sa, prep);
-    if (ada)
-        return launch_adagrad_step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && ada->aligned16, ada->d_ptr, tb->T,
-                                         tb->D, tb->dtype, (int64_t)batch, dt, dt_ld, d, lr, rule.eps, sa, prep);
-    return launch_sgd_apply(ctx, ix->dev, tb->d_desc, tb->aligned16, tb->T, tb->D, tb->dtype, 1, (int64_t)batch, dt,
-                            DLRM_F32, dt_ld, d, lr, sa, prep);
+    return kRules[r.kind].step_apply(ctx, ix->dev, tb->d_desc, tb->aligned16 && r.aligned16, tb->T, tb->D, tb->dtype, 1,
+                                     (int64_t)batch, dt, DLRM_F32, dt_ld, d, r, sa, prep);
 }
 
-int dlrm_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* indices, int itype,
-                  int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld, const void* dout,
-                  int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr,
-                  unsigned flags) {
-    return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
-                         dx, dx_ld, dt, dt_ld, lr, flags, nullptr);
-}
-
-static int step_bwd_prepare_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* indices, int itype,
-                                 int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
-                                 const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
-                                 int64_t dt_ld, float lr, dlrm_indexer* next, const void* next_indices, unsigned flags,
-                                 const StepRule& rule) {
-    CHECK_ARG(ctx && tb && ix && next && next != ix, "%s_prepare: null or shared indexer", rule.fn);
-    CHECK_ARG(next->T == tb->T && batch <= next->dev.cap, "%s_prepare: next indexer too small", rule.fn);
+static int step_bwd_prepare_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const BoundRule& r,
+                                 const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                                 const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding, float* dx,
+                                 int64_t dx_ld, float* dt, int64_t dt_ld, dlrm_indexer* next, const void* next_indices,
+                                 unsigned flags) {
+    const char* const fn = kRules[r.kind].step_fn;
+    CHECK_ARG(next && next != ix, "%s_prepare: null or shared indexer", fn);
+    CHECK_ARG(next->T == tb->T && batch <= next->dev.cap, "%s_prepare: next indexer too small", fn);
     int rc = check_indices(ctx, tb, next_indices, itype, table_stride, batch, 1);
     if (rc) return rc;
     // the next batch's build runs as extra workgroups of this step's apply launch: the step
@@ -1478,18 +1412,12 @@ static int step_bwd_prepare_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* i
     const int NB = (tb->T + 1 + 15) / 16;
     // (the split backward's shapes only: the apply launch that carries the build has no once-hit items)
     const bool inapply = batch > 0 && tb->T > 0 && batch <= kWaveApplyMaxN && NB <= 2 && tb->aligned16 &&
-                         wave_fits(next, batch) &&
-                         step_split_supported(tb->aligned16, tb->T, tb->dtype, tb->D, x, x_ld) &&
-                         (!rule.op || rule.op->aligned16) &&
-                         (!rule.ada || ((rule.ada->rowwise || rule.ada->aligned16) &&
-                                        adagrad_step_bwd_supported(rule.ada->rowwise, tb->dtype, tb->T, tb->D))) &&
-                         (!rule.sr || sr_step_bwd_supported(tb->T, tb->D));
-    if (!inapply)  // no pipelined form for this shape: the plain step (the next forward builds)
-        return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
-                             padding, dx, dx_ld, dt, dt_ld, lr, flags, nullptr, rule);
-    if (flags & DLRM_STEP_BWD_ONLY)  // (the next build rides on the apply launch)
-        return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
-                             padding, dx, dx_ld, dt, dt_ld, lr, flags, nullptr, rule);
+                         wave_fits(next, batch) && has_split_bwd(tb, r, x, x_ld);
+    // no pipelined form for this shape: the plain step (the next forward builds); BWD_ONLY: the next build rides on
+    // the apply launch
+    if (!inapply || (flags & DLRM_STEP_BWD_ONLY))
+        return step_bwd_impl(ctx, tb, ix, r, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
+                             padding, dx, dx_ld, dt, dt_ld, flags, nullptr);
     next->built = false;
     next->prepared = false;
     // the wave build: 2^wave_parts_log2(batch) parts per table, one wave each (4 per workgroup)
@@ -1497,8 +1425,8 @@ static int step_bwd_prepare_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* i
     if (next->dev.vshift < 2) next->dev.vshift = 2;
     const PrepArgs pa{next->dev, tb->d_desc, tb->T, next_indices, itype, table_stride, index_base, batch,
                       next->prep_err + 1};
-    rc = step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
-                       dx, dx_ld, dt, dt_ld, lr, flags, &pa, rule);
+    rc = step_bwd_impl(ctx, tb, ix, r, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
+                       dx, dx_ld, dt, dt_ld, flags, &pa);
     if (rc) return rc;
     record_build(next, true, next_indices, itype, table_stride, index_base, batch, 1);
     next->prepared = true;
@@ -1506,87 +1434,61 @@ static int step_bwd_prepare_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* i
     return DLRM_OK;
 }
 
-int dlrm_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const void* indices, int itype,
-                          int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
-                          const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
-                          int64_t dt_ld, float lr, dlrm_indexer* next, const void* next_indices, unsigned flags) {
-    return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
-                                 padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags,
-                                 StepRule{"dlrm_step_bwd"});
+// The public pairs: each binds its rule and passes it down.  (The stochastic rule's handle's step word is read by both
+// launches of a step and advanced after the one that runs the apply.)
+#define STEP_ARGS                                                                                                     \
+    const void *indices, int itype, int64_t table_stride, int index_base, int batch, const void *x, int64_t x_ld,     \
+        const void *dout, int64_t dout_ld, int padding, float *dx, int64_t dx_ld, float *dt, int64_t dt_ld
+#define STEP_PASS indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding, dx, dx_ld, dt, dt_ld
+
+int dlrm_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, STEP_ARGS, float lr, unsigned flags) {
+    CHECK_ARG(ctx && tb && ix, "dlrm_step_bwd: null ctx/tables/indexer");
+    return step_bwd_impl(ctx, tb, ix, bind_rule(lr), STEP_PASS, flags, nullptr);
 }
 
-// ---- the same step on split-bf16 tables: the split rule in the backward's once-hit write and in the apply
-int dlrm_split_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dlrm_indexer* ix, const void* indices,
-                        int itype, int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
-                        const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
-                        int64_t dt_ld, float lr, unsigned flags) {
+int dlrm_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, STEP_ARGS, float lr, dlrm_indexer* next,
+                          const void* next_indices, unsigned flags) {
+    CHECK_ARG(ctx && tb && ix, "dlrm_step_bwd_prepare: null or shared indexer");
+    return step_bwd_prepare_impl(ctx, tb, ix, bind_rule(lr), STEP_PASS, next, next_indices, flags);
+}
+
+int dlrm_split_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dlrm_indexer* ix, STEP_ARGS, float lr,
+                        unsigned flags) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_split_step_bwd: null ctx/tables/optimizer/indexer");
-    return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
-                         dx, dx_ld, dt, dt_ld, lr, flags, nullptr, StepRule{"dlrm_split_step_bwd", kRuleSplit, op});
+    return step_bwd_impl(ctx, tb, ix, bind_rule(op, lr), STEP_PASS, flags, nullptr);
 }
 
-int dlrm_split_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dlrm_indexer* ix,
-                                const void* indices, int itype, int64_t table_stride, int index_base, int batch,
-                                const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding, float* dx,
-                                int64_t dx_ld, float* dt, int64_t dt_ld, float lr, dlrm_indexer* next,
-                                const void* next_indices, unsigned flags) {
+int dlrm_split_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* op, dlrm_indexer* ix, STEP_ARGS,
+                                float lr, dlrm_indexer* next, const void* next_indices, unsigned flags) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_split_step_bwd_prepare: null ctx/tables/optimizer/indexer");
-    return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
-                                 padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags,
-                                 StepRule{"dlrm_split_step_bwd", kRuleSplit, op});
+    return step_bwd_prepare_impl(ctx, tb, ix, bind_rule(op, lr), STEP_PASS, next, next_indices, flags);
 }
 
-// ---- the same step with a sparse Adagrad rule (element-wise or row-wise: the handle's kind) in the backward's
-// once-hit write and in the apply
-static StepRule adagrad_step_rule(dlrm_adagrad* op, float eps) {
-    return StepRule{"dlrm_adagrad_step_bwd", op->rowwise ? kRuleRowwise : kRuleAdagrad, nullptr, op, eps};
-}
-
-int dlrm_adagrad_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, const void* indices,
-                          int itype, int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
-                          const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
-                          int64_t dt_ld, float lr, float eps, unsigned flags) {
+int dlrm_adagrad_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, STEP_ARGS, float lr,
+                          float eps, unsigned flags) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_adagrad_step_bwd: null ctx/tables/optimizer/indexer");
-    return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
-                         dx, dx_ld, dt, dt_ld, lr, flags, nullptr, adagrad_step_rule(op, eps));
+    return step_bwd_impl(ctx, tb, ix, bind_rule(op, lr, eps), STEP_PASS, flags, nullptr);
 }
 
-int dlrm_adagrad_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix,
-                                  const void* indices, int itype, int64_t table_stride, int index_base, int batch,
-                                  const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding, float* dx,
-                                  int64_t dx_ld, float* dt, int64_t dt_ld, float lr, float eps, dlrm_indexer* next,
-                                  const void* next_indices, unsigned flags) {
+int dlrm_adagrad_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, STEP_ARGS,
+                                  float lr, float eps, dlrm_indexer* next, const void* next_indices, unsigned flags) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_adagrad_step_bwd_prepare: null ctx/tables/optimizer/indexer");
-    return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
-                                 padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags,
-                                 adagrad_step_rule(op, eps));
+    return step_bwd_prepare_impl(ctx, tb, ix, bind_rule(op, lr, eps), STEP_PASS, next, next_indices, flags);
 }
 
-// ---- the same step with the stochastic rule on bf16 tables in the backward's once-hit write and in the apply; the
-// handle's step word is read by both launches and advanced after the one that runs the apply
-static StepRule sr_step_rule(dlrm_sr_sgd* op) {
-    StepRule r{"dlrm_sr_step_bwd", kRuleStochastic};
-    r.sr = op;
-    return r;
-}
-
-int dlrm_sr_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_sr_sgd* op, dlrm_indexer* ix, const void* indices, int itype,
-                     int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld, const void* dout,
-                     int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr,
+int dlrm_sr_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_sr_sgd* op, dlrm_indexer* ix, STEP_ARGS, float lr,
                      unsigned flags) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_sr_step_bwd: null ctx/tables/optimizer/indexer");
-    return step_bwd_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
-                         dx, dx_ld, dt, dt_ld, lr, flags, nullptr, sr_step_rule(op));
+    return step_bwd_impl(ctx, tb, ix, bind_rule(op, lr), STEP_PASS, flags, nullptr);
 }
 
-int dlrm_sr_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_sr_sgd* op, dlrm_indexer* ix, const void* indices,
-                             int itype, int64_t table_stride, int index_base, int batch, const void* x, int64_t x_ld,
-                             const void* dout, int64_t dout_ld, int padding, float* dx, int64_t dx_ld, float* dt,
-                             int64_t dt_ld, float lr, dlrm_indexer* next, const void* next_indices, unsigned flags) {
+int dlrm_sr_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_sr_sgd* op, dlrm_indexer* ix, STEP_ARGS, float lr,
+                             dlrm_indexer* next, const void* next_indices, unsigned flags) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_sr_step_bwd_prepare: null ctx/tables/optimizer/indexer");
-    return step_bwd_prepare_impl(ctx, tb, ix, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
-                                 padding, dx, dx_ld, dt, dt_ld, lr, next, next_indices, flags, sr_step_rule(op));
+    return step_bwd_prepare_impl(ctx, tb, ix, bind_rule(op, lr), STEP_PASS, next, next_indices, flags);
 }
+#undef STEP_ARGS
+#undef STEP_PASS
 
 // ---- diagnostics: a native backtrace on a fatal signal (SIGSEGV / SIGBUS / SIGABRT), written to
 // stderr before the previous handler runs (Python's faulthandler then prints the Python stack).

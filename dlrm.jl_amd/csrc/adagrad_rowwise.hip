@@ -8,12 +8,12 @@
 
 namespace dlrm {
 
-int launch_rowwise_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16,
-                                 float* const* state, int T_, int D, int tdtype, int L, int64_t N, const void* grad,
-                                 int gdtype, int64_t grad_ld, int64_t grad_offset, float lr, float eps,
-                                 const SinglesArgs& sa) {
+// (r.state: the device array of per-table fp32 [nrows] state pointers)
+int launch_rowwise_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T_, int D,
+                                 int tdtype, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
+                                 int64_t grad_offset, const BoundRule& r, const SinglesArgs& sa, const PrepArgs*) {
     return launch_apply_rule(ctx, ix, tabs, aligned16, T_, D, tdtype, L, N, grad, gdtype, grad_ld, grad_offset,
-                             RowwiseAdagrad{lr, eps, state}, sa, nullptr);
+                             RowwiseAdagrad{r.lr, r.eps, (float* const*)r.state}, sa, nullptr);
 }
 
 }  // namespace dlrm

@@ -5,14 +5,15 @@
 
 namespace dlrm {
 
-int launch_rowwise_adagrad_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16,
-                                      float* const* state, int T_, int D, int tdtype, int64_t N, const float* dt,
-                                      int64_t dt_ld, int64_t dt_offset, float lr, float eps, const SinglesArgs& sa,
+int launch_rowwise_adagrad_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T_,
+                                      int D, int tdtype, int, int64_t N, const void* dt, int, int64_t dt_ld,
+                                      int64_t dt_offset, const BoundRule& r, const SinglesArgs& sa,
                                       const PrepArgs* pa) {
-    return launch_step_apply_rule(ctx, ix, tabs, aligned16, T_, D, tdtype, N, dt, dt_ld, dt_offset,
-                                  RowwiseAdagrad{lr, eps, state}, sa, pa, [&](const SinglesArgs& s1) {
-                                      return launch_rowwise_adagrad_apply(ctx, ix, tabs, aligned16, state, T_, D, tdtype, 1, N,
-                                                                          dt, DLRM_F32, dt_ld, dt_offset, lr, eps, s1);
+    return launch_step_apply_rule(ctx, ix, tabs, aligned16, T_, D, tdtype, N, (const float*)dt, dt_ld, dt_offset,
+                                  RowwiseAdagrad{r.lr, r.eps, (float* const*)r.state}, sa, pa,
+                                  [&](const SinglesArgs& s1) {
+                                      return launch_rowwise_adagrad_apply(ctx, ix, tabs, aligned16, T_, D, tdtype, 1, N,
+                                                                          dt, DLRM_F32, dt_ld, dt_offset, r, s1, nullptr);
                                   });
 }
 

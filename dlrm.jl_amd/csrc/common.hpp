@@ -336,6 +336,7 @@ constexpr int kPartialDim = 256;  // partial rows allocated with the indexer (la
 
 // Host-side launch helpers (defined in abi.cpp) and the per-kernel launchers.
 struct dlrm_ctx;
+struct StateDims;  // (abi.cpp: what an optimizer handle was created for)
 namespace dlrm {
 unsigned* ctx_error_word(dlrm_ctx* ctx);
 hipStream_t ctx_stream(dlrm_ctx* ctx);
@@ -366,6 +367,23 @@ struct Knobs {
 };
 const Knobs& knobs();
 
+// The optimizer rules of the update and of the training step.  abi.cpp's kRules describes each one on the host
+// (names, table types, launches); apply.hpp holds their arithmetic, interact.hip the step backward's once-hit write.
+enum { kRuleDescent = 0, kRuleSplit, kRuleAdagrad, kRuleRowwise, kRuleStochastic, kNumRules };
+// A rule bound to one call: what the public entry points make of their optimizer handle and scalars, and all that
+// the launchers below take of a rule.
+struct BoundRule {
+    int kind = kRuleDescent;
+    float lr = 0.0f, eps = 0.0f;  // (eps: the Adagrad rules)
+    // the handle's device array of per-table pointers to the rule's second stream: uint16 low halves (kRuleSplit),
+    // fp32 state rows (kRuleAdagrad) or words (kRuleRowwise); and whether every row of it is 16-B aligned
+    void* state = nullptr;
+    bool aligned16 = true;
+    uint64_t seed = 0;         // kRuleStochastic: the handle's seed ...
+    uint64_t* step = nullptr;  // ... and its device step word
+    const StateDims* handle = nullptr;  // the optimizer handle itself (Descent: none); the launchers do not read it
+};
+
 int launch_maplookup(dlrm_ctx* ctx, const TableDesc* d_tabs, bool tabs_aligned16, int T, int D, int dtype,
                      const void* idx, int itype, int64_t tstride, int base, int B, int L, void* out,
                      int64_t out_ld, int64_t out_off, const TableDesc* htabs = nullptr);
@@ -390,12 +408,6 @@ int launch_step_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, i
                     int itype, int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, void* out,
                     int64_t out_ld, int padding, const IndexerDev& ix,
     const TableDesc* htabs = nullptr);
-int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T, int dtype, const void* idx, int itype,
-                    int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
-                    int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
-                    float lr,
-    const TableDesc* htabs = nullptr,
-    uint16_t* const* split_lo = nullptr);  // split-bf16 tables: the device array of low-half pointers
 int launch_interact_bwd(dlrm_ctx* ctx, int dtype, int d, int F, int B, const void* dout, int64_t dout_ld,
                         const void* t, int64_t t_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld);
 int64_t hix_table_slots(int64_t cap);
@@ -424,69 +436,35 @@ int launch_step_prepare(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* ta
                         int64_t tstride, int base, int N, unsigned* err);
 struct SinglesArgs;
 struct PrepArgs;
-int launch_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool tabs_aligned16, int T, int D,
-                     int tdtype, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
-                     float lr, const SinglesArgs& singles, const PrepArgs* prep = nullptr);
-// the same apply with an Adagrad rule (apply.hpp): state = the device array of per-table fp32 state
-// pointers ([nrows][D]; row-wise [nrows]).  aligned16: every table row (element-wise: and every
-// state row) is 16-B aligned.
-int launch_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, float* const* state,
-                         int T, int D, int tdtype, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
-                         int64_t grad_offset, float lr, float eps, const SinglesArgs& singles);
-int launch_rowwise_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16,
-                                 float* const* state, int T, int D, int tdtype, int L, int64_t N, const void* grad,
-                                 int gdtype, int64_t grad_ld, int64_t grad_offset, float lr, float eps,
-                                 const SinglesArgs& singles);
-// the same apply with the split rule (apply.hpp SplitDescent) on bf16 tables: lo = the device array of
-// per-table uint16 [nrows][D] low-half pointers.  aligned16: every table row and every low-half row is
-// 16-B aligned.
-int launch_split_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint16_t* const* lo,
-                           int T, int D, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
-                           int64_t grad_offset, float lr, const SinglesArgs& singles);
-// the same apply with the stochastic rule (apply.hpp StochasticDescent) on bf16 tables, then the advance of the
-// handle's device step word `step` by a one-thread launch (sr_sgd.hip); launch_sr_step_set: step = value, on the
-// context's stream.
-int launch_sr_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint64_t seed,
-                        uint64_t* step, int T, int D, int L, int64_t N, const void* grad, int gdtype,
-                        int64_t grad_ld, int64_t grad_offset, float lr, const SinglesArgs& singles);
+// A rule's apply launch over an indexer's build (apply_kernel.hpp launch_apply_rule with the rule at its write
+// sites).  aligned16: every table row and every row of the rule's second stream is 16-B aligned.  Each rule has
+// two, in two units:
+//  - the update's (update.hip, split_sgd.hip, adagrad.hip, adagrad_rowwise.hip, sr_sgd.hip): MODE 0 / 1, any gradient
+//    type and L; only Descent's takes `prep` (the others' callers pass NULL).  The stochastic rule's ends with the
+//    one-thread advance of the step word (nothing to launch: it leaves the word alone);
+//  - the training step's (split_step.hip, adagrad_step.hip, adagrad_rowwise_step.hip, sr_step.hip; Descent's is its
+//    update's): the step's fp32 dt rows (gdtype = DLRM_F32, L = 1); with `prep` and no once-hit items the next
+//    batch's build rides on the launch (MODE 2 / 3 / 5) where the shape's vector kernel exists, otherwise the
+//    update's launch and, with `prep`, the build's own.  The stochastic rule's advances the step word once either way,
+//    after the launch that read it.
+typedef int ApplyFn(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T, int D, int tdtype,
+                    int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
+                    const BoundRule& rule, const SinglesArgs& singles, const PrepArgs* prep);
+ApplyFn launch_sgd_apply, launch_split_sgd_apply, launch_adagrad_apply, launch_rowwise_adagrad_apply, launch_sr_sgd_apply;
+ApplyFn launch_split_step_apply, launch_adagrad_step_apply, launch_rowwise_adagrad_step_apply, launch_sr_step_apply;
+// the stochastic rule's step word, by one-thread launches on the context's stream (sr_sgd.hip)
 int launch_sr_step_set(dlrm_ctx* ctx, uint64_t* step, uint64_t value);
-int launch_sr_step_advance(dlrm_ctx* ctx, uint64_t* step);  // step += 1, by one thread, on the context's stream
-// the training step with the stochastic rule (dlrm_sr_step_bwd): whether the step backward has the rule's once-hit
-// write for this shape (interact.hip), that backward (it reads the step word and does not advance it), and the
-// rule's apply over the fp32 dt followed by the advance of the step word (sr_step.hip): with `prep` and no once-hit
-// items the next batch's build rides on the launch (MODE 2 / 3 / 5), otherwise launch_sr_sgd_apply and, with
-// `prep`, the build's own launch.  Either way the word advances once, after the launch that read it.
-bool sr_step_bwd_supported(int T, int d);
-int launch_sr_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T, const void* idx, int itype, int64_t tstride,
-                       int base, int d, int B, const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, float* dx,
-                       int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix, float lr, uint64_t seed,
-                       const uint64_t* step);
-int launch_sr_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint64_t seed,
-                         uint64_t* step, int T, int D, int64_t N, const float* dt, int64_t dt_ld, int64_t dt_offset,
-                         float lr, const SinglesArgs& singles, const PrepArgs* prep);
-// the training step's split apply over the fp32 dt (split_step.hip): with `prep` and no once-hit items the
-// next batch's build rides on the launch (MODE 2 / 3 / 5), otherwise launch_split_sgd_apply and, with `prep`,
-// the build's own launch.
-int launch_split_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint16_t* const* lo,
-                            int T, int D, int64_t N, const float* dt, int64_t dt_ld, int64_t dt_offset, float lr,
-                            const SinglesArgs& singles, const PrepArgs* prep);
-// the training step with a sparse Adagrad rule (dlrm_adagrad_step_bwd): whether the step backward has the rule's
-// once-hit write for this feature size (interact.hip), that backward, and the rule's apply over the fp32 dt
-// (adagrad_step.hip / adagrad_rowwise_step.hip): with `prep` and no once-hit items the next batch's build rides
-// on the launch where the shape's MODE 2 / 3 / 5 kernel exists, otherwise the rule's own apply and, with
-// `prep`, the build's own launch.
-bool adagrad_step_bwd_supported(bool rowwise, int dtype, int T, int d);
-int launch_adagrad_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T, int dtype, const void* idx, int itype,
-                            int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
-                            int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
-                            float lr, float eps, bool rowwise, float* const* state);
-int launch_adagrad_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16,
-                              float* const* state, int T, int D, int tdtype, int64_t N, const float* dt, int64_t dt_ld,
-                              int64_t dt_offset, float lr, float eps, const SinglesArgs& singles, const PrepArgs* prep);
-int launch_rowwise_adagrad_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16,
-                                      float* const* state, int T, int D, int tdtype, int64_t N, const float* dt,
-                                      int64_t dt_ld, int64_t dt_offset, float lr, float eps,
-                                      const SinglesArgs& singles, const PrepArgs* prep);
+int launch_sr_step_advance(dlrm_ctx* ctx, uint64_t* step);  // step += 1
+// The training step's backward under a rule (interact.hip).  step_bwd_supported: whether the split backward has the
+// rule's once-hit write for this shape (among step_split_supported's; Descent and the split rule: all of them).
+// launch_step_bwd: that backward -- once-hit rows stepped in place with the rule, dt rows of the others written for
+// the apply; the caller checked the shape, the 16-B alignment of dx / dt and of the rule's second stream, and bf16
+// tables for the rules that need them.  The stochastic rule's reads the step word and does not advance it.
+bool step_bwd_supported(int kind, int dtype, int T, int d);
+int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T, int dtype, const void* idx, int itype,
+                    int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
+                    int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
+                    const BoundRule& rule);
 int launch_triangular_slice(dlrm_ctx* ctx, int dtype, int sz, int B, const void* z, int64_t z_bs, void* out,
                             int64_t out_ld);
 int launch_triangular_slice_back(dlrm_ctx* ctx, int dtype, int sz, int B, const void* dy, int64_t dy_ld, void* a,

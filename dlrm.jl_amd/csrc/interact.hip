@@ -1802,8 +1802,8 @@ int launch_step_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, i
     return ctx_hip(ctx, hipGetLastError(), "step_fwd launch");
 }
 
-// The forms <NB, WPS, CPL, SPB> of interact_bwd_split_kernel that exist for a rule (split; adagrad 1: element-wise,
-// 2: row-wise; neither: Descent) and an element type.  d = 128: two waves per sample (WPS 2, 4 samples per block),
+// The forms <NB, WPS, CPL, SPB> of interact_bwd_split_kernel that exist for a rule (kRule*) and an element type.
+// d = 128: two waves per sample (WPS 2, 4 samples per block),
 // or 8 columns per lane (bf16 rows, one wave per sample, 2 samples per block); d <= 64: one wave per sample, 8
 // samples per block.  Descent has them all, with 2, 4 or 8 samples per block at d = 128 (DLRM_BWD_SPB).  The other
 // rules have the default samples per block only, and no form that would run below Descent's occupancy
@@ -1814,44 +1814,44 @@ int launch_step_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, i
 //    77..87, the element-wise one-wave form on fp32 tables 66.
 // The split rule's rows live in bf16 tables, and so do the stochastic rule's: that rule has
 // every default-geometry form of Descent on bf16 tables but the 8-column one with up to 16 features, as the split rule.
-constexpr bool step_bwd_form(bool split, int adagrad, bool f32, int NB, int WPS, int CPL, int SPB,
-                             bool stochastic = false) {
-    const bool d128 = WPS == 2 || CPL == 8;
+constexpr bool step_bwd_form(int rule, bool f32, int NB, int WPS, int CPL, int SPB) {
+    const bool d128 = WPS == 2 || CPL == 8, descent = rule == kRuleDescent;
     if ((CPL == 8 && (f32 || WPS != 1)) || !(SPB == 2 || SPB == 4 || SPB == 8)) return false;
-    if (SPB != (CPL == 8 ? 2 : (d128 ? 4 : 8))) return !split && !adagrad && !stochastic && d128;
-    if (!split && !adagrad && !stochastic) return true;
+    if (SPB != (CPL == 8 ? 2 : (d128 ? 4 : 8))) return descent && d128;
+    if (descent) return true;
     if (CPL == 8 && NB == 1) return false;
-    if (split || stochastic) return !f32;
-    return adagrad == 2 ? NB == 2 : !(NB == 1 && WPS == 1 && f32);
+    if (rule == kRuleSplit || rule == kRuleStochastic) return !f32;
+    return rule == kRuleRowwise ? NB == 2 : !(NB == 1 && WPS == 1 && f32);
 }
-// Shapes whose step backward has an Adagrad form (among step_split_supported's): d = 128 and d <= 64, the forms
-// of interact_bwd_split_kernel.  The row-wise rule also needs the vector apply's summation order to exist for
-// the shape (fp32 dt rows of d / 4 vectors, d / 4 a power of two: apply_kernel.hpp dispatch_apply); the any-D
-// kernels sum a row's squares in column order, which no lane layout here reproduces.  Any other d (the
-// interact_bwd_update_kernel shapes) and the DLRM_BWD_NOSPLIT override take the gather backward.
-bool adagrad_step_bwd_supported(bool rowwise, int dtype, int T_, int d) {
-    if (knobs().bwd_nosplit || !(d == 128 || d <= 64)) return false;
-    if (rowwise && !(d >= 8 && (d & (d - 1)) == 0)) return false;
-    return step_bwd_form(false, rowwise ? 2 : 1, dtype == DLRM_F32, (T_ + 1 + 15) / 16, d == 128 ? 2 : 1, 4,
-                         d == 128 ? 4 : 8);
+// the kRule* of a StepUpdate type
+template <typename SU>
+constexpr int rule_of() {
+    return SU::kSplit ? kRuleSplit
+                      : (SU::kStochastic ? kRuleStochastic
+                                         : (SU::kAdagrad == 2 ? kRuleRowwise : (SU::kAdagrad == 1 ? kRuleAdagrad : kRuleDescent)));
 }
-
-// Shapes whose step backward has the stochastic rule's once-hit write (among step_split_supported's, bf16 tables):
-// d = 128 and d <= 64.  Any other d and the DLRM_BWD_NOSPLIT override take the gather backward.
-bool sr_step_bwd_supported(int T_, int d) {
+// Shapes (among step_split_supported's) whose step backward has the rule's once-hit write.  Descent and the split
+// rule: all of them (interact_bwd_update_kernel takes the d that interact_bwd_split_kernel does not).  An Adagrad rule
+// and the stochastic rule (bf16 tables): d = 128 and d <= 64, the forms of interact_bwd_split_kernel; any other d and
+// the DLRM_BWD_NOSPLIT override take the gather backward.  The row-wise rule also needs the vector apply's summation
+// order to exist for the shape (fp32 dt rows of d / 4 vectors, d / 4 a power of two: apply_kernel.hpp dispatch_apply);
+// the any-D kernels sum a row's squares in column order, which no lane layout here reproduces.
+bool step_bwd_supported(int kind, int dtype, int T_, int d) {
+    if (kind == kRuleDescent || kind == kRuleSplit) return true;
     if (knobs().bwd_nosplit || !(d == 128 || d <= 64)) return false;
-    return step_bwd_form(false, 0, false, (T_ + 1 + 15) / 16, d == 128 ? 2 : 1, 4, d == 128 ? 4 : 8, true);
+    if (kind == kRuleRowwise && !(d >= 8 && (d & (d - 1)) == 0)) return false;
+    return step_bwd_form(kind, dtype == DLRM_F32, (T_ + 1 + 15) / 16, d == 128 ? 2 : 1, 4, d == 128 ? 4 : 8);
 }
 
 // Training-step backward after launch_step_fwd under the rule SU: once-hit rows updated in place, dt rows of the
 // others written for the apply.  The caller checked the shape (launch_step_fwd accepted it), the 16-B alignment of
-// dx / dt and of the rule's second stream, and for an Adagrad rule adagrad_step_bwd_supported.  The DLRM_BWD_SPB /
+// dx / dt and of the rule's second stream, and step_bwd_supported.  The DLRM_BWD_SPB /
 // DLRM_BWD_CPL / DLRM_UPD_SBU overrides are Descent's.
 template <typename T, typename SU>
 static int launch_step_bwd_rule(dlrm_ctx* ctx, const GatherArgs& ga, int F, int d, int B, const void* x_, int64_t x_ld,
                                 const void* dout_, int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
                                 const SU& su) {
-    constexpr bool f32 = sizeof(T) == 4, descent = !SU::kSplit && !SU::kAdagrad && !SU::kStochastic;
+    constexpr bool f32 = sizeof(T) == 4, descent = rule_of<SU>() == kRuleDescent;
     const T* x = (const T*)x_;
     const T* dout = (const T*)dout_;
     const int NB = (F + 15) / 16;
@@ -1862,7 +1862,7 @@ static int launch_step_bwd_rule(dlrm_ctx* ctx, const GatherArgs& ga, int F, int 
     };
     // (a form step_bwd_form leaves out is not instantiated)
 #define DLRM_FORM(N_, DC_, W_, C_, S_, WHAT_)                                                                       \
-    if constexpr (step_bwd_form(SU::kSplit, SU::kAdagrad, f32, N_, W_, C_, S_, SU::kStochastic))                    \
+    if constexpr (step_bwd_form(rule_of<SU>(), f32, N_, W_, C_, S_))                                                \
         if (NB == N_ && spb == S_) {                                                                                \
             hipLaunchKernelGGL((interact_bwd_split_kernel<T, N_, DC_, S_, W_, false, C_, false, SU>),                \
                                dim3((unsigned)((B + S_ - 1) / S_)), dim3(64 * W_ * S_), 0, s, d, F, B, dout, dout_ld, \
@@ -1879,7 +1879,7 @@ static int launch_step_bwd_rule(dlrm_ctx* ctx, const GatherArgs& ga, int F, int 
         // DLRM_BWD_CPL = 4 / 8 forces either form.
         const int cpl_env = descent ? knobs().bwd_cpl : 0;
         const bool cpl8 = d == 128 && !f32 && (cpl_env ? cpl_env == 8 : B > 2048) &&
-                          step_bwd_form(SU::kSplit, SU::kAdagrad, f32, NB, 1, 8, 2, SU::kStochastic);
+                          step_bwd_form(rule_of<SU>(), f32, NB, 1, 8, 2);
         // samples per block (DLRM_BWD_SPB = 2, 4 or 8 overrides)
         const int spb_env = !(descent && d == 128) ? 0
                             : knobs().bwd_spb >= 8 ? 8 : (knobs().bwd_spb >= 4 ? 4 : (knobs().bwd_spb > 0 ? 2 : 0));
@@ -1918,47 +1918,33 @@ static int launch_step_bwd_rule(dlrm_ctx* ctx, const GatherArgs& ga, int F, int 
     }
 }
 
-// (lo: the device array of a split-bf16 table set's low-half pointers, 16-B aligned rows; the caller checked the dtype)
+// The one launcher of the public step backward: the arguments every rule shares, then the rule's StepUpdate type (and,
+// where the rule takes fp32 tables, the element type).
 int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, const void* idx, int itype,
                     int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
                     int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
-                    float lr,
-                    const TableDesc* htabs, uint16_t* const* lo) {
+                    const BoundRule& r) {
     if (B == 0 || T_ == 0) return DLRM_OK;
     const GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
-    const StepUpdate su{ix.single, ix.cap, lr, ctx_error_word(ctx)};
+    const StepUpdate su{ix.single, ix.cap, r.lr, ctx_error_word(ctx)};
+    const bool f32 = dtype == DLRM_F32;
+    float* const* const state = (float* const*)r.state;
 #define DLRM_RULE(TY, ...) \
     return launch_step_bwd_rule<TY>(ctx, ga, T_ + 1, d, B, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, __VA_ARGS__)
-    if (lo) DLRM_RULE(uint16_t, SplitStepUpdate{su, lo});
-    if (dtype == DLRM_F32) DLRM_RULE(float, su);
-    DLRM_RULE(uint16_t, su);
-}
-
-// (state: the device array of the rule's state pointers; the element-wise rule's rows 16-B aligned)
-int launch_adagrad_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, const void* idx, int itype,
-                            int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
-                            int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
-                            float lr, float eps, bool rowwise, float* const* state) {
-    if (B == 0 || T_ == 0) return DLRM_OK;
-    const GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
-    const StepUpdate su{ix.single, ix.cap, lr, ctx_error_word(ctx)};
-    if (dtype == DLRM_F32) {
-        if (rowwise) DLRM_RULE(float, AdagradStepUpdate<true>{su, state, eps});
-        DLRM_RULE(float, AdagradStepUpdate<false>{su, state, eps});
+    switch (r.kind) {
+        case kRuleSplit: DLRM_RULE(uint16_t, SplitStepUpdate{su, (uint16_t* const*)r.state});
+        case kRuleStochastic:
+            DLRM_RULE(uint16_t, StochasticStepUpdate{su, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.step});
+        case kRuleAdagrad:
+            if (f32) DLRM_RULE(float, AdagradStepUpdate<false>{su, state, r.eps});
+            DLRM_RULE(uint16_t, AdagradStepUpdate<false>{su, state, r.eps});
+        case kRuleRowwise:
+            if (f32) DLRM_RULE(float, AdagradStepUpdate<true>{su, state, r.eps});
+            DLRM_RULE(uint16_t, AdagradStepUpdate<true>{su, state, r.eps});
+        default:
+            if (f32) DLRM_RULE(float, su);
+            DLRM_RULE(uint16_t, su);
     }
-    if (rowwise) DLRM_RULE(uint16_t, AdagradStepUpdate<true>{su, state, eps});
-    DLRM_RULE(uint16_t, AdagradStepUpdate<false>{su, state, eps});
-}
-
-// (bf16 tables and sr_step_bwd_supported: the caller checked; step: the handle's device step word)
-int launch_sr_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, const void* idx, int itype, int64_t tstride,
-                       int base, int d, int B, const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, float* dx,
-                       int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix, float lr, uint64_t seed,
-                       const uint64_t* step) {
-    if (B == 0 || T_ == 0) return DLRM_OK;
-    const GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
-    const StepUpdate su{ix.single, ix.cap, lr, ctx_error_word(ctx)};
-    DLRM_RULE(uint16_t, StochasticStepUpdate{su, (uint32_t)seed, (uint32_t)(seed >> 32), step});
 #undef DLRM_RULE
 }
 

@@ -10,11 +10,12 @@
 
 namespace dlrm {
 
-int launch_split_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint16_t* const* lo,
-                           int T_, int D, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
-                           int64_t grad_offset, float lr, const SinglesArgs& sa) {
+// (r.state: the device array of per-table uint16 [nrows][D] low-half pointers; tdtype: bf16, the caller checked)
+int launch_split_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T_, int D, int,
+                           int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
+                           const BoundRule& r, const SinglesArgs& sa, const PrepArgs*) {
     return launch_apply_rule(ctx, ix, tabs, aligned16, T_, D, DLRM_BF16, L, N, grad, gdtype, grad_ld, grad_offset,
-                             SplitDescent{lr, lo}, sa, nullptr);
+                             SplitDescent{r.lr, (uint16_t* const*)r.state}, sa, nullptr);
 }
 
 }  // namespace dlrm

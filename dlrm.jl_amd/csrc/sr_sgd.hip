@@ -16,15 +16,16 @@ namespace dlrm {
 __global__ void sr_step_advance_kernel(uint64_t* step) { *step += 1; }
 __global__ void sr_step_set_kernel(uint64_t* step, uint64_t value) { *step = value; }
 
-int launch_sr_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint64_t seed,
-                        uint64_t* step, int T_, int D, int L, int64_t N, const void* grad, int gdtype,
-                        int64_t grad_ld, int64_t grad_offset, float lr, const SinglesArgs& sa) {
+// (tdtype: bf16, the caller checked)
+int launch_sr_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T_, int D, int, int L,
+                        int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
+                        const BoundRule& r, const SinglesArgs& sa, const PrepArgs*) {
     if (T_ == 0 || N == 0) return DLRM_OK;  // (nothing launched: the step stays)
     const int rc = launch_apply_rule(ctx, ix, tabs, aligned16, T_, D, DLRM_BF16, L, N, grad, gdtype, grad_ld, grad_offset,
-                                     StochasticDescent{lr, (uint32_t)seed, (uint32_t)(seed >> 32), step, 0u, 0u}, sa,
-                                     nullptr);
+                                     StochasticDescent{r.lr, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.step, 0u, 0u},
+                                     sa, nullptr);
     if (rc) return rc;
-    return launch_sr_step_advance(ctx, step);
+    return launch_sr_step_advance(ctx, r.step);
 }
 
 // after a call's last launch that reads the word: every workgroup of it has read the word when this one starts

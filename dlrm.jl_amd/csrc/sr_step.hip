@@ -14,19 +14,19 @@
 
 namespace dlrm {
 
-int launch_sr_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, uint64_t seed,
-                         uint64_t* step, int T_, int D, int64_t N, const float* dt, int64_t dt_ld, int64_t dt_offset,
-                         float lr, const SinglesArgs& sa, const PrepArgs* pa) {
-    const StochasticDescent rule{lr, (uint32_t)seed, (uint32_t)(seed >> 32), step, 0u, 0u};
+int launch_sr_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T_, int D, int, int,
+                         int64_t N, const void* dt, int, int64_t dt_ld, int64_t dt_offset, const BoundRule& r,
+                         const SinglesArgs& sa, const PrepArgs* pa) {
+    const StochasticDescent rule{r.lr, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.step, 0u, 0u};
     bool advanced = false;  // by launch_sr_sgd_apply (nothing to launch: it leaves the word alone)
-    const int rc = launch_step_apply_rule(ctx, ix, tabs, aligned16, T_, D, DLRM_BF16, N, dt, dt_ld, dt_offset, rule, sa, pa,
-                                          [&](const SinglesArgs& s) {
+    const int rc = launch_step_apply_rule(ctx, ix, tabs, aligned16, T_, D, DLRM_BF16, N, (const float*)dt, dt_ld,
+                                          dt_offset, rule, sa, pa, [&](const SinglesArgs& s) {
                                               advanced = true;
-                                              return launch_sr_sgd_apply(ctx, ix, tabs, aligned16, seed, step, T_, D, 1, N,
-                                                                         dt, DLRM_F32, dt_ld, dt_offset, lr, s);
+                                              return launch_sr_sgd_apply(ctx, ix, tabs, aligned16, T_, D, DLRM_BF16, 1, N,
+                                                                         dt, DLRM_F32, dt_ld, dt_offset, r, s, nullptr);
                                           });
     if (rc || advanced) return rc;
-    return launch_sr_step_advance(ctx, step);
+    return launch_sr_step_advance(ctx, r.step);
 }
 
 }  // namespace dlrm

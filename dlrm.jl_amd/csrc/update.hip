@@ -834,9 +834,9 @@ int launch_indexer_build(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* t
 
 int launch_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool tabs_aligned16, int T_, int D,
                      int tdtype, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
-                     float lr, const SinglesArgs& sa, const PrepArgs* pa) {
+                     const BoundRule& r, const SinglesArgs& sa, const PrepArgs* pa) {
     return launch_apply_rule(ctx, ix, tabs, tabs_aligned16, T_, D, tdtype, L, N, grad, gdtype, grad_ld, grad_offset,
-                             Descent{lr}, sa, pa);
+                             Descent{r.lr}, sa, pa);
 }
 
 int launch_sgd_atomic(dlrm_ctx* ctx, TableDesc* tabs, int T_, int D, const void* idx, int itype, int64_t tstride,

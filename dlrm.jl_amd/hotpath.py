@@ -59,7 +59,7 @@ from .embedding import EmbeddingTableSet, PackedIndices
 from .interact import interaction_sizes
 from .runtime import dtype_code, ptr, require_device
 from .shapes import APPLY_MAX_N
-from .update import SparseIndexer, SplitDescent, StochasticDescent, _AdagradBase, _StatefulOpt
+from .update import SparseIndexer, _StatefulOpt
 
 
 class HotPath:
@@ -73,37 +73,21 @@ class HotPath:
             raise ValueError(f"HotPath: {type(opt).__name__} needs the deterministic update")
         self.opt = opt
         self.ts = tables if isinstance(tables, EmbeddingTableSet) else EmbeddingTableSet(tables)
-        # the fused step pair with the stochastic rule (dlrm_sr_step_bwd); a keyword of its own
-        self.stochastic_step = bool(stochastic_step)
-        if self.stochastic_step and not isinstance(opt, StochasticDescent):
-            raise ValueError("HotPath: stochastic_step=True is the stochastic rule's fused step "
-                             "(opt=StochasticDescent(eta, seed)); the split rule's is fused_step=True, the Adagrad "
-                             "rules' adagrad_step=True, Descent(lr) is fused without a keyword")
-        if isinstance(opt, StochasticDescent):
-            # without stochastic_step the operator route only; fused_step / adagrad_step are other rules' keywords
-            if fused_step or adagrad_step:
-                raise ValueError("HotPath: fused_step / adagrad_step are the split and Adagrad rules' fused step; "
-                                 "StochasticDescent's is stochastic_step=True (without it the rule takes the operator "
-                                 "route: its once-hit rows are rounded in the apply launch)")
-            if pipeline not in (False, 0, None) and not self.stochastic_step:
-                raise ValueError("HotPath: pipeline must be None with opt=StochasticDescent: the pipelined steps need "
-                                 "a fused step, which this rule has with stochastic_step=True only")
-            if self.ts.dtype != torch.bfloat16:
-                raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not {self.ts.dtype}")
-        # the fused step pair with the split rule (dlrm_split_step_bwd); without it opt= takes the operator path
-        self.split_step = bool(fused_step)
-        if self.split_step and not isinstance(opt, SplitDescent):
-            raise ValueError("HotPath: fused_step=True is the split rule's fused step (opt=SplitDescent(eta)); "
-                             "Descent(lr) is fused without it, the Adagrad rules have no fused step")
-        if self.split_step and self.ts.dtype != torch.bfloat16:
-            raise ValueError(f"HotPath: fused_step=True needs bfloat16 tables (the high halves), not {self.ts.dtype}")
-        # the fused step pair with an Adagrad rule (dlrm_adagrad_step_bwd); a keyword of its own
-        self.adagrad_step = bool(adagrad_step)
+        # The optimizer's fused step pair (its step_entry) is opt-in by the optimizer's own keyword (its step_keyword);
+        # without it opt= takes the operator route.  Any other rule's keyword is refused.
+        given = {k for k, v in (("fused_step", fused_step), ("adagrad_step", adagrad_step),
+                                ("stochastic_step", stochastic_step)) if v}
+        own = None if opt is None else opt.step_keyword
+        if given - {own}:
+            raise ValueError(f"HotPath: {' / '.join(sorted(given - {own}))}=True is another rule's fused step: the split "
+                             "rule's is fused_step=True (opt=SplitDescent(eta)), the Adagrad rules' adagrad_step=True "
+                             "(opt=ADAGrad(eta, eps) or opt=RowwiseADAGrad(eta, eps)), the stochastic rule's "
+                             "stochastic_step=True (opt=StochasticDescent(eta, seed)); Descent(lr) is fused without a "
+                             "keyword, and without its keyword a rule takes the operator route")
+        self._rule_step = bool(given)  # this engine runs opt's fused step (split_step, adagrad_step, stochastic_step)
         self.rule_params = None
-        if self.adagrad_step and not isinstance(opt, _AdagradBase):
-            raise ValueError("HotPath: adagrad_step=True is the Adagrad rules' fused step (opt=ADAGrad(eta, eps) or "
-                             "opt=RowwiseADAGrad(eta, eps)); the split rule's is fused_step=True, Descent(lr) is fused "
-                             "without a keyword")
+        if opt is not None:
+            opt.check_tables(self.ts.dtype)
         self.B, self.L = int(batch), int(lookups)
         self.T, self.D = len(self.ts), self.ts.D
         self.d = self.D  # dense vector length == feature size (model.jl:220)
@@ -147,19 +131,12 @@ class HotPath:
         self._indexer_done = None
         # the training-step pair (dlrm_step_fwd / dlrm_step_bwd): indexer built inside the forward's
         # launch, once-hit rows updated inside the backward's, the rest by the apply launch
+        # (dlrm_step_bwd: Descent; a rule's own pair with its keyword)
         self.step_api = ((not self.materialize_ys) and self.indexer is not None and not self.overlap_indexer and
-                         (opt is None or self.split_step or self.adagrad_step or self.stochastic_step))
-        # (dlrm_step_bwd: Descent; dlrm_split_step_bwd: the split rule; dlrm_adagrad_step_bwd: the Adagrad rules;
-        # dlrm_sr_step_bwd: the stochastic rule)
-        if self.split_step and not self.step_api:
-            raise ValueError("HotPath: fused_step=True needs the step kernels (one-hot lookups, ys not materialized, "
+                         (opt is None or self._rule_step))
+        if self._rule_step and not self.step_api:
+            raise ValueError(f"HotPath: {own}=True needs the step kernels (one-hot lookups, ys not materialized, "
                              "no side-stream indexer)")
-        if self.adagrad_step and not self.step_api:
-            raise ValueError("HotPath: adagrad_step=True needs the step kernels (one-hot lookups, ys not materialized, "
-                             "no side-stream indexer)")
-        if self.stochastic_step and not self.step_api:
-            raise ValueError("HotPath: stochastic_step=True needs the step kernels (one-hot lookups, ys not "
-                             "materialized, no side-stream indexer)")
         # pipelined steps: the NEXT batch's split indexer is built during this step, so the
         # step's forward launch only gathers; two indexers alternate.
         #   "apply" (`step_prep`): by extra workgroups of this step's apply launch
@@ -171,10 +148,9 @@ class HotPath:
         if mode not in (None, "side", "apply"):
             raise ValueError(f"pipeline must be None, 'side' or 'apply', not {pipeline!r}")
         if opt is not None:
-            if mode is not None and not (self.split_step or self.adagrad_step or self.stochastic_step):
+            if mode is not None and not self._rule_step:
                 raise ValueError("HotPath: the pipelined steps need the fused step (pipeline must be None with opt, "
-                                 "unless opt=SplitDescent with fused_step=True, an Adagrad rule with "
-                                 "adagrad_step=True or opt=StochasticDescent with stochastic_step=True)")
+                                 f"unless {own}=True turns on the fused step of {type(opt).__name__})")
             opt.handle_of(self.ts)  # the state, allocated before any graph capture
         # (pooled bags: "side" only -- the next batch's build beside this step's apply, `step_next`)
         self.pipeline = mode if (mode and ((self.step_api and self.L == 1) or (mode == "side" and self.L > 1))) else None
@@ -192,6 +168,11 @@ class HotPath:
             self._cur = 0
             self._pside = torch.cuda.Stream(device=dev)
             self._pev = torch.cuda.Event()
+
+    # which rule's fused step the engine runs, by the keyword that turned it on (read-only views of _rule_step)
+    split_step = property(lambda self: self._rule_step and self.opt.step_keyword == "fused_step")
+    adagrad_step = property(lambda self: self._rule_step and self.opt.step_keyword == "adagrad_step")
+    stochastic_step = property(lambda self: self._rule_step and self.opt.step_keyword == "stochastic_step")
 
     # -- pieces --------------------------------------------------------------------------
     def _check(self, rc):
@@ -276,42 +257,20 @@ class HotPath:
         h = self.ctx.bind()
         x = self._fwd_x if x is None else x
         idx = self._fwd_idx if idx is None else idx
-        if self.split_step or self.adagrad_step or self.stochastic_step:
-            args = (h, self.ts.handle, self.opt.handle_of(self.ts), self.indexer.handle, ptr(idx.data), idx.itype,
-                    idx.stride, self.index_base, self.B, ptr(x), x.stride(0), ptr(dout), dout.stride(0), self.padding,
-                    ptr(self.dx), self.dx.stride(0), ptr(self.dt), self.dt.stride(0), self.opt.eta)
-            if self.adagrad_step:
-                # (rule_params: the (eta, eps) an owner fixed for both launches of a step, HipTables' deferred
-                # apply among them; None: the optimizer's own, read at the call)
-                eta, eps = self.rule_params or (self.opt.eta, self.opt.eps)
-                args = args[:-1] + (eta, eps)
-                one, two = self.lib.dlrm_adagrad_step_bwd, self.lib.dlrm_adagrad_step_bwd_prepare
-            elif self.stochastic_step:
-                one, two = self.lib.dlrm_sr_step_bwd, self.lib.dlrm_sr_step_bwd_prepare
-            else:
-                one, two = self.lib.dlrm_split_step_bwd, self.lib.dlrm_split_step_bwd_prepare
-            if prepare is not None:
-                nix, nidx = prepare
-                if (nidx.itype, nidx.stride, nidx.B, nidx.L) != (idx.itype, idx.stride, idx.B, idx.L):
-                    raise ValueError("the next batch's indices must have this batch's layout")
-                self._check(two(*args, nix.handle, ptr(nidx.data), flags))
-            else:
-                self._check(one(*args, flags))
+        if self._rule_step:  # the optimizer's pair, handle and scalars (rule_params: an owner's, fixed for both launches)
+            entry, head, params = self.opt.step_entry, (self.opt.handle_of(self.ts),), self.opt.step_params(self.rule_params)
+        else:
+            entry, head, params = ("dlrm_step_bwd", "dlrm_step_bwd_prepare"), (), (self.lr,)
+        args = (h, self.ts.handle, *head, self.indexer.handle, ptr(idx.data), idx.itype, idx.stride, self.index_base,
+                self.B, ptr(x), x.stride(0), ptr(dout), dout.stride(0), self.padding, ptr(self.dx), self.dx.stride(0),
+                ptr(self.dt), self.dt.stride(0), *params)
+        if prepare is None:
+            self._check(getattr(self.lib, entry[0])(*args, flags))
             return
-        if prepare is not None:  # (next indexer, next indices): built by this step's apply launch
-            nix, nidx = prepare
-            if (nidx.itype, nidx.stride, nidx.B, nidx.L) != (idx.itype, idx.stride, idx.B, idx.L):
-                raise ValueError("the next batch's indices must have this batch's layout")
-            self._check(self.lib.dlrm_step_bwd_prepare(h, self.ts.handle, self.indexer.handle, ptr(idx.data),
-                                                       idx.itype, idx.stride, self.index_base, self.B, ptr(x),
-                                                       x.stride(0), ptr(dout), dout.stride(0), self.padding,
-                                                       ptr(self.dx), self.dx.stride(0), ptr(self.dt),
-                                                       self.dt.stride(0), self.lr, nix.handle, ptr(nidx.data), flags))
-            return
-        self._check(self.lib.dlrm_step_bwd(h, self.ts.handle, self.indexer.handle, ptr(idx.data), idx.itype,
-                                           idx.stride, self.index_base, self.B, ptr(x), x.stride(0), ptr(dout),
-                                           dout.stride(0), self.padding, ptr(self.dx), self.dx.stride(0),
-                                           ptr(self.dt), self.dt.stride(0), self.lr, flags))
+        nix, nidx = prepare  # (next indexer, next indices): built by this step's apply launch
+        if (nidx.itype, nidx.stride, nidx.B, nidx.L) != (idx.itype, idx.stride, idx.B, idx.L):
+            raise ValueError("the next batch's indices must have this batch's layout")
+        self._check(getattr(self.lib, entry[1])(*args, nix.handle, ptr(nidx.data), flags))
 
     def build_split(self, indexer, idx):
         """The indexer form dlrm_step_bwd consumes: the wave build (dlrm_indexer_prepare) for one-hot

@@ -45,11 +45,9 @@ Anything else that reads ys gets it materialized (`LazyLookup.materialize`).  `o
 gradient live in per-batch-size buffers reused by the next step, as the reference's own
 preallocated scratch (`DotInteraction`'s per-thread scratchpads) is.
 """
-import torch
-
 from . import _lib
 from .embedding import EmbeddingTableSet, PackedIndices, PreallocationStrategy, as_table_set
-from .update import Descent, SparseEmbeddingUpdate, SplitDescent, StochasticDescent, _AdagradBase, _StatefulOpt
+from .update import Descent, SparseEmbeddingUpdate, StochasticDescent, _AdagradBase, _StatefulOpt
 
 
 class HipTables:
@@ -74,24 +72,21 @@ class HipTables:
         if self.stochastic_step and not isinstance(opt, StochasticDescent):
             raise ValueError("HipTables: stochastic_step=True is the stochastic rule's fused step "
                              "(opt=StochasticDescent(eta, seed))")
-        if self.stochastic_step and self._ts.dtype != torch.bfloat16:
-            raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not {self._ts.dtype}")
+        if opt is not None and not isinstance(opt, _StatefulOpt):
+            raise TypeError("HipTables: opt is a SplitDescent, a StochasticDescent, an ADAGrad or a RowwiseADAGrad "
+                            "(Descent: lr=eta)")
+        # the optimizer's fused step runs these tables' steps (the stochastic rule's: with its keyword only; without,
+        # the operator route: the pullback writes every dt row and update! steps every row, lr stays None)
+        self._rule_step = opt is not None and (self.stochastic_step or not isinstance(opt, StochasticDescent))
+        if self._rule_step:
+            if lr is not None and float(lr) != opt.eta:
+                raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}")
+            lr = opt.eta
+        elif opt is not None and lr is not None:
+            raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}: without stochastic_step=True the rule "
+                             "takes the operator route, so the pullback steps no row (lr must be None)")
         if opt is not None:
-            if not isinstance(opt, (SplitDescent, StochasticDescent, _AdagradBase)):
-                raise TypeError("HipTables: opt is a SplitDescent, a StochasticDescent, an ADAGrad or a RowwiseADAGrad "
-                                "(Descent: lr=eta)")
-            if isinstance(opt, StochasticDescent) and not self.stochastic_step:
-                # the operator route: the pullback writes every dt row and update! steps every row (lr stays None)
-                if lr is not None:
-                    raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}: without stochastic_step=True the rule "
-                                     "takes the operator route, so the pullback steps no row (lr must be None)")
-                if self._ts.dtype != torch.bfloat16:
-                    raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not "
-                                     f"{self._ts.dtype}")
-            else:
-                if lr is not None and float(lr) != opt.eta:
-                    raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}")
-                lr = opt.eta
+            opt.check_tables(self._ts.dtype)
         self.opt = opt
         # an Adagrad rule's (η, ε) as given here: every launch of these tables' steps uses them (the pullback's
         # and a deferred apply's alike), and update! refuses the optimizer object once its own differ
@@ -169,13 +164,11 @@ class HipTables:
         from .hotpath import HotPath
         hp = self._hp.get(batch)
         if hp is None:
-            # (the stochastic rule without its fused step: the operator route, a plain step engine)
-            stochastic = isinstance(self.opt, StochasticDescent) and not self.stochastic_step
-            hp = HotPath(self._ts, batch, 1, lr=0.0 if self.lr is None else self.lr, index_base=self.index_base,
-                         opt=None if stochastic else self.opt, fused_step=isinstance(self.opt, SplitDescent),
-                         adagrad_step=isinstance(self.opt, _AdagradBase), stochastic_step=self.stochastic_step)
+            # the optimizer and its own keyword; without its fused step (the operator route) a plain step engine
+            rule = {"opt": self.opt, self.opt.step_keyword: True} if self._rule_step else {}
+            hp = HotPath(self._ts, batch, 1, lr=0.0 if self.lr is None else self.lr, index_base=self.index_base, **rule)
             hp.rule_params = self._opt_params
-            if stochastic:
+            if self.opt is not None and not self._rule_step:
                 self.opt.handle_of(self._ts)  # the handle and its step word, allocated before any graph capture
             if not hp.step_api:
                 raise ValueError("HipTables: this table set has no training-step kernels (deterministic, one-hot)")
@@ -296,10 +289,8 @@ def update_lazy(opt, tables, grads, *, check_bounds=None):
     if not isinstance(opt, (Descent, _StatefulOpt)):
         raise TypeError("update_ implements Descent (plain SGD, the optimizer DLRM.jl trains with), ADAGrad, "
                         "RowwiseADAGrad, SplitDescent and StochasticDescent")
-    if isinstance(opt, SplitDescent) and tables._ts.dtype != torch.bfloat16:
-        raise ValueError(f"SplitDescent needs bfloat16 tables (the high halves), not {tables._ts.dtype}")
-    if isinstance(opt, StochasticDescent) and tables._ts.dtype != torch.bfloat16:
-        raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not {tables._ts.dtype}")
+    if isinstance(opt, _StatefulOpt):
+        opt.check_tables(tables._ts.dtype)
     lz = grads[0].lazy
     if len(grads) != len(tables) or any(g.lazy is not lz or g.table_index != t for t, g in enumerate(grads)):
         raise ValueError("update_ expects the per-table views of one maplookup pullback")

@@ -50,6 +50,20 @@ class _StatefulOpt:
         """The C update's return code: `grad` columns from `grad_offset`, indices `idx` (PackedIndices)."""
         raise NotImplementedError
 
+    # The rule's fused training step (HotPath, HipTables): the keyword that opts an engine in, the library's pair of
+    # entry points (the step backward and its _prepare form), and `step_params`, the scalars they take after the
+    # buffers (fixed: the ones an owner fixed for both launches of a step, HipTables' deferred apply among them;
+    # None: the optimizer's own, read at the call).
+    step_keyword = None
+    step_entry = None
+    no_atomic = None  # why the rule has no atomic mode (none of these has one)
+
+    def step_params(self, fixed=None):
+        return fixed or (self.eta,)
+
+    def check_tables(self, dtype):
+        """Raises ValueError when the rule cannot step tables of element type `dtype`."""
+
     def _entry(self, tables):
         ts = as_table_set(tables)
         key = tuple(t.data.data_ptr() for t in ts)  # (the parameters themselves: any table set over them)
@@ -84,11 +98,17 @@ class _StatefulOpt:
 class _AdagradBase(_StatefulOpt):
     """Sparse Adagrad over embedding tables (dlrm_adagrad_*)."""
     rowwise = False
+    no_atomic = "an atomic add never holds the row's whole gradient sum, which the rule squares"
+    step_keyword = "adagrad_step"
+    step_entry = ("dlrm_adagrad_step_bwd", "dlrm_adagrad_step_bwd_prepare")
 
     def __init__(self, eta=0.1, eps=1e-8):
         super().__init__()
         self.eta = float(eta)
         self.eps = float(eps)
+
+    def step_params(self, fixed=None):
+        return fixed or (self.eta, self.eps)
 
     def _create(self, ts, ptrs, out):
         return ts.ctx.lib.dlrm_adagrad_create(ts.ctx.bind(), ts.handle, int(self.rowwise), ptrs, out)
@@ -154,13 +174,20 @@ class SplitDescent(_StatefulOpt):
     tables with Descent, an Adagrad optimizer or a `HotPath` without `opt=`: those round the high
     half and leave the low one behind."""
 
+    no_atomic = "an atomic add on one half of a weight cannot carry into the other"
+    step_keyword = "fused_step"
+    step_entry = ("dlrm_split_step_bwd", "dlrm_split_step_bwd_prepare")
+
     def __init__(self, eta=0.1):
         super().__init__()
         self.eta = float(eta)
 
+    def check_tables(self, dtype):
+        if dtype != torch.bfloat16:
+            raise ValueError(f"SplitDescent needs bfloat16 tables (the high halves), not {dtype}")
+
     def _init_state(self, table):
-        if table.dtype != torch.bfloat16:
-            raise ValueError(f"SplitDescent needs bfloat16 tables (the high halves), not {table.dtype}")
+        self.check_tables(table.dtype)
         return torch.zeros(table.shape, dtype=torch.int16, device=table.device)
 
     def _create(self, ts, ptrs, out):
@@ -262,13 +289,20 @@ class StochasticDescent(_StatefulOpt):
         self.eta = float(eta)
         self.seed = seed
 
+    no_atomic = "the rule rounds each row's complete step once, an atomic add would round every addend"
+    step_keyword = "stochastic_step"
+    step_entry = ("dlrm_sr_step_bwd", "dlrm_sr_step_bwd_prepare")
+
+    def check_tables(self, dtype):
+        if dtype != torch.bfloat16:
+            raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not {dtype}")
+
     def _entry(self, tables):
         ts = as_table_set(tables)
         key = tuple(t.data.data_ptr() for t in ts)
         ent = self._state.get(key)
         if ent is None:
-            if ts.dtype != torch.bfloat16:
-                raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not {ts.dtype}")
+            self.check_tables(ts.dtype)
             h = ctypes.c_void_p()
             ts.ctx.check(ts.ctx.lib.dlrm_sr_sgd_create(ts.ctx.bind(), ts.handle, _as_i64(self.seed), ctypes.byref(h)))
             ent = self._state[key] = (ts, [], h)  # (no state tensors: the handle holds the step)
@@ -501,22 +535,10 @@ def update_(opt, tables, grads, indexers=None, *, num_splits=8, nthreads=12, ind
         raise TypeError("update_ implements Descent (plain SGD, the optimizer DLRM.jl trains with), ADAGrad, "
                         "RowwiseADAGrad, SplitDescent and StochasticDescent")
     stateful = isinstance(opt, _StatefulOpt)
-    if isinstance(opt, _AdagradBase) and not deterministic:
-        raise ValueError("update_ with an Adagrad optimizer is deterministic only: an atomic add never holds the "
-                         "row's whole gradient sum, which the rule squares")
-    if isinstance(opt, SplitDescent):
+    if stateful:
         if not deterministic:
-            raise ValueError("update_ with SplitDescent is deterministic only: an atomic add on one half of a "
-                             "weight cannot carry into the other")
-        if _tables_dtype(tables) != torch.bfloat16:
-            raise ValueError(f"SplitDescent needs bfloat16 tables (the high halves), not {_tables_dtype(tables)}")
-    if isinstance(opt, StochasticDescent):
-        if not deterministic:
-            raise ValueError("update_ with StochasticDescent is deterministic only: the rule rounds each row's "
-                             "complete step once, an atomic add would round every addend")
-        if _tables_dtype(tables) != torch.bfloat16:
-            raise ValueError(f"StochasticDescent needs bfloat16 tables (fp32: nothing to round), not "
-                             f"{_tables_dtype(tables)}")
+            raise ValueError(f"update_ with {type(opt).__name__} is deterministic only: {opt.no_atomic}")
+        opt.check_tables(_tables_dtype(tables))
     ts = as_table_set(tables)
     if len(grads) != len(ts):
         raise ValueError(f"{len(grads)} gradients for {len(ts)} tables")
