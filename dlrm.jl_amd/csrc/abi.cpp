@@ -3,7 +3,10 @@
 // Owns the handle types (ctx, tables, indexer, the optimizers'), validates arguments on the host,
 // maps HIP errors to dlrm_status codes and forwards to the kernel launchers.  No launching
 // entry point allocates or synchronises (hipGraph-capturable).  An optimizer rule is described
-// once, in kRules; the entry points bind it to their call (bind_rule) and pass that down.
+// once, in kRules; the entry points bind it to their call (bind_rule) and pass that down.  Which index
+// build a batch takes is decided once, in build_plan.hpp's plan_build; the entry points that build are
+// checks -> plan -> begin_build -> the launch (run_build, or the forward / backward / apply launch that
+// carries the build) -> record_build.
 #include <dlfcn.h>
 #include <execinfo.h>
 #include <hip/hip_runtime.h>
@@ -198,44 +201,49 @@ int ctx_hip(dlrm_ctx* ctx, hipError_t e, const char* what) {
 
 static int hip_set(dlrm_ctx* ctx) { return ctx_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice"); }
 
-// parts per table of the step's split indexer build (DLRM_STEP_PARTS = 1, 2, 4 or 8 overrides,
-// for comparison).  Measured (profiles/r3m_*): inside the step forward 4 parts (8 add more
-// workgroups than they save in sort depth beside the D = 128 gather); inside the apply launch
-// for rows of <= 256 B 8 parts (D = 16: apply + build 12.8 -> 11.4 us), for fp32 x 128 4.
-static int step_parts_log2(int dflt = kStepParts) {
-    const int forced = knobs().step_parts;
-    const int p = forced > 0 ? forced : dflt;
-    return p >= 32 ? 5 : (p >= 16 ? 4 : (p >= 8 ? 3 : (p >= 4 ? 2 : (p >= 2 ? 1 : 0))));
+// ---- an indexer's build: plan (build_plan.hpp plan_build) -> begin_build -> the launch -> record_build
+static IndexerShape shape_of(const dlrm_indexer* ix) {
+    return IndexerShape{ix->dev.cap, ix->T, ix->TV, ix->dev.hsize, ix->parts_log2};
 }
 
-// vshift of the wave build of `batch` positions per table (the step forward's in-launch build and
-// the in-apply / prepared builds): 16 parts per table up to 2048 positions (DLRM_STEP_PARTS may force
-// fewer, >= 4), then 16 parts per 2048 positions (wave_vshift)
-static int wave_parts_log2(int64_t batch, const dlrm_indexer* ix = nullptr) {
-    if (batch > kStepIndexMaxN) return wave_vshift(batch);
-    if (ix && ix->parts_log2 && !knobs().step_parts) return ix->parts_log2;  // (dlrm_indexer_set_parts)
-    const int vs = step_parts_log2(kWaveBuildParts);
-    return vs < 2 ? 2 : vs;
+// The index arguments a build was made from, remembered for built_from
+struct IndexArgs {
+    const void* indices;
+    int itype;
+    int64_t tstride;
+    int base, B, L;
+};
+
+// The word a build raises its bounds errors on
+static unsigned* err_word(dlrm_ctx* ctx, const dlrm_indexer* ix, ErrWord w) {
+    return w == ErrWord::Ctx ? ctx->err : ix->prep_err + (w == ErrWord::Prep1 ? 1 : 0);
 }
 
-static bool has_parts(const dlrm_indexer* ix, int vs) { return (int64_t)ix->TV >= ((int64_t)ix->T << vs) && ix->T > 0; }
-
-static void record_build(dlrm_indexer* ix, bool split, const void* indices, int itype, int64_t tstride, int base,
-                         int B, int L) {
-    ix->built = true;
-    ix->split = split;
+// The only place that changes an indexer's record before a launch: whatever it held is gone (Kept: a prepared
+// build is consumed by the forward that gathers with it, and stands)
+static void begin_build(dlrm_indexer* ix, const BuildPlan& p) {
     ix->prepared = false;
+    if (p.form == BuildForm::Kept) return;
+    ix->built = false;
+    ix->dev.vshift = p.vshift;
+}
+
+// ... and the only one that writes it after a launch that went out
+static void record_build(dlrm_indexer* ix, const BuildPlan& p, const IndexArgs& a) {
+    ix->built = true;
+    ix->split = p.split;
+    ix->prepared = p.prepared;
     ix->singles_done = false;
     ix->singles_rule = kRuleDescent;
     ix->singles_handle = nullptr;
-    ix->dev.has_map = 0;  // (set by dlrm_step_bwd_prepare, whose wave build writes the item map)
-    ix->dev.build_err = nullptr;  // (set by dlrm_indexer_prepare)
-    ix->indices = indices;
-    ix->itype = itype;
-    ix->tstride = tstride;
-    ix->base = base;
-    ix->B = B;
-    ix->L = L;
+    ix->dev.has_map = p.has_map ? 1 : 0;
+    ix->dev.build_err = p.build_err ? err_word(ix->ctx, ix, p.err) : nullptr;
+    ix->indices = a.indices;
+    ix->itype = a.itype;
+    ix->tstride = a.tstride;
+    ix->base = a.base;
+    ix->B = a.B;
+    ix->L = a.L;
 }
 
 static bool built_from(const dlrm_indexer* ix, const void* indices, int itype, int64_t tstride, int base, int B,
@@ -698,13 +706,14 @@ int dlrm_interact_bwd_gather(dlrm_ctx* ctx, const dlrm_tables* tb, dlrm_indexer*
                   "dlrm_interact_bwd_gather: batch*lookups %lld > indexer capacity %lld", (long long)batch * lookups,
                   (long long)ix->dev.cap);
     }
-    if (ix) ix->dev.vshift = 0;
+    const BuildPlan plan = plan_build(BuildSite::BwdGather, IndexerShape{}, batch, knobs(), BuildCaps{});
+    if (ix) begin_build(ix, plan);
     rc = launch_interact_bwd_gather(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
                                     index_base, lookups, d, batch, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld,
                                     ix ? &ix->dev : nullptr, tb->h_desc.data());
     if (rc || !ix) return rc;
     // as dlrm_indexer_build: a following update may pass DLRM_UPDATE_PREBUILT
-    record_build(ix, false, indices, itype, table_stride, index_base, batch, lookups);
+    record_build(ix, plan, IndexArgs{indices, itype, table_stride, index_base, batch, lookups});
     return DLRM_OK;
 }
 
@@ -817,12 +826,6 @@ static int indexer_carve(dlrm_ctx* ctx, dlrm_indexer* ix, int parts) {
     return DLRM_OK;
 }
 
-// Whether a wave build of `batch` positions per table fits this indexer (compact layout: any parts;
-// the flat records hold global perm entries in int32).
-static bool wave_fits(const dlrm_indexer* ix, int64_t batch) {
-    return batch <= ix->dev.cap && batch <= kWaveMaxN && (int64_t)(ix->T > 0 ? ix->T : 1) * ix->dev.cap < (1ll << 31);
-}
-
 int dlrm_indexer_create(dlrm_ctx* ctx, int num_tables, int64_t max_lookups, dlrm_indexer** out) {
     CHECK_ARG(ctx && out, "dlrm_indexer_create: null argument");
     *out = nullptr;
@@ -837,14 +840,11 @@ int dlrm_indexer_create(dlrm_ctx* ctx, int num_tables, int64_t max_lookups, dlrm
     ix->dev.pcap = indexer_slice_cap(cap);
     ix->dev.pdim = kPartialDim;
     ix->dev.chunk_max = kChunk;
-    const int64_t hs = cap > kFastMaxN ? hix_table_slots(cap) : 0;
+    const int64_t hs = carve_hash(cap) ? hix_table_slots(cap) : 0;
     ix->dev.hsize = hs;
     ix->dev.hbits = 0;
     while (((int64_t)1 << ix->dev.hbits) < hs) ++ix->dev.hbits;
-    // 8 virtual tables per table for the in-LDS parts build of kFastMaxN < N <= kPartsMaxN (fast_index_table;
-    // build_vshift <= 3), else one: every wave build packs its parts per table
-    const int parts = cap > kFastMaxN && cap <= kPartsMaxN ? (1 << 3) : 1;
-    const int rc = indexer_carve(ctx, ix, parts);
+    const int rc = indexer_carve(ctx, ix, carve_virtual_tables(cap));
     if (rc != DLRM_OK) {
         delete ix;
         return rc;
@@ -890,11 +890,45 @@ int dlrm_indexer_destroy(dlrm_indexer* ix) {
     return DLRM_OK;
 }
 
-// vshift of a standalone split build of N positions per table: the parts build where it applies
-static int build_vshift(const dlrm_indexer* ix, int64_t N, bool split) {
-    const int p = knobs().build_parts ? knobs().build_parts : (1 << kPartsLog2);
-    const int lg = p >= 8 ? 3 : (p >= 4 ? 2 : 1);
-    return split && N > kFastMaxN && N <= kPartsMaxN && has_parts(ix, lg) ? lg : 0;
+// The entry point's words for a plan that refuses (BuildForm::None with DLRM_E_UNSUPPORTED)
+static int refuse_build(dlrm_ctx* ctx, BuildSite site, int64_t N) {
+    if (site == BuildSite::Prepare)
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_indexer_prepare: batch %d (the wave build: batch <= %d, "
+                        "tables x capacity < 2^31)", (int)N, kWaveMaxN);
+    return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "split indexer build: %lld positions per table", (long long)N);
+}
+
+// The launch of a build that has one of its own, by the plan's form (after begin_build)
+static int run_build(dlrm_ctx* ctx, dlrm_indexer* ix, const dlrm_tables* tb, const BuildPlan& p, const IndexArgs& a) {
+    const int64_t N = (int64_t)a.B * a.L;
+    unsigned* const err = err_word(ctx, ix, p.err);
+    // (an indexer's own word starts each build clear: the apply of this indexer folds it into the ctx's flag)
+    if (p.err == ErrWord::Prep0) {
+        const int rc = ctx_hip(ctx, hipMemsetAsync(err, 0, sizeof(unsigned), ctx->stream), "clear build bounds word");
+        if (rc) return rc;
+    }
+    switch (p.form) {
+    case BuildForm::Bag:
+        return launch_bag_build(ctx, ix->dev, tb->d_desc, tb->T, a.indices, a.itype, a.tstride, a.base, (int)N, err);
+    case BuildForm::Wave:
+        return launch_step_prepare(ctx, ix->dev, tb->d_desc, tb->T, a.indices, a.itype, a.tstride, a.base, (int)N, err);
+    default:  // Lds2, Lds4, LdsParts, Hash, Sorted (the builds inside another launch are their entry point's)
+        return launch_indexer_build(ctx, ix->dev, tb->d_desc, tb->T, a.indices, a.itype, a.tstride, a.base, a.B, a.L,
+                                    p.form, p.split, err, p.side ? ctx->side : nullptr);
+    }
+}
+
+// plan -> begin -> launch -> record, for the sites whose build is a launch of its own
+static int build_now(dlrm_ctx* ctx, dlrm_indexer* ix, const dlrm_tables* tb, BuildSite site, const IndexArgs& a,
+                     const BuildCaps& caps) {
+    const int64_t N = (int64_t)a.B * a.L;
+    const BuildPlan p = plan_build(site, shape_of(ix), N, knobs(), caps);
+    if (p.form == BuildForm::None) return refuse_build(ctx, site, N);  // (a refused call leaves the indexer as it was)
+    begin_build(ix, p);
+    const int rc = run_build(ctx, ix, tb, p, a);
+    if (rc) return rc;
+    record_build(ix, p, a);
+    return DLRM_OK;
 }
 
 int dlrm_indexer_build(dlrm_ctx* ctx, dlrm_indexer* ix, const dlrm_tables* tb, const void* indices, int itype,
@@ -905,36 +939,8 @@ int dlrm_indexer_build(dlrm_ctx* ctx, dlrm_indexer* ix, const dlrm_tables* tb, c
     CHECK_ARG(tb->T == ix->T, "dlrm_indexer_build: indexer has %d tables, tables has %d", ix->T, tb->T);
     CHECK_ARG((int64_t)batch * lookups <= ix->dev.cap, "dlrm_indexer_build: batch*lookups %lld > capacity %lld",
               (long long)batch * lookups, (long long)ix->dev.cap);
-    // the split form where the builds support it: once-hit positions flagged (single[]) instead of
-    // listed as one-position chunks; the apply then updates them with no descriptor read
-    const int64_t N = (int64_t)batch * lookups;
-    const bool split = N <= kFastMaxN || (ix->dev.hsize && N <= kHixMaxN);
-    if (split && N > kPartsMaxN && wave_fits(ix, N) && !knobs().bag_hash) {
-        // pooled bags (configs[4]: 20480 positions per table) and other large batches: the bag build
-        // (update.hip: count, place by part, then the wave build's per-part sort; 2^wave_vshift(N)
-        // parts per table, flat item map) instead of the hash build (4 launches, global atomics;
-        // round 5: 146 us and 13x its algorithmic bytes for configs[4]).  It groups positions
-        // p = b L + k; the apply maps p to its bag.  Bounds errors go to the ctx's flag, as every
-        // dlrm_indexer_build's.
-        ix->built = false;
-        // half the parts of the wave builds (128 to 256 positions per part; configs[4] at 20480: 128
-        // parts, 50.6 us against 66.7 us with 256 -- half the sort workgroups, each still sorting in
-        // registers)
-        ix->dev.vshift = knobs().bag_vs >= 2 && knobs().bag_vs <= wave_vshift(ix->dev.cap < kWaveMaxN ? ix->dev.cap : kWaveMaxN)
-                             ? knobs().bag_vs : wave_vshift(N) - 1;
-        rc = launch_bag_build(ctx, ix->dev, tb->d_desc, tb->T, indices, itype, table_stride, index_base, (int)N,
-                              ctx_error_word(ctx));
-        if (rc) return rc;
-        record_build(ix, true, indices, itype, table_stride, index_base, batch, lookups);
-        ix->dev.has_map = 1;
-        return DLRM_OK;
-    }
-    ix->dev.vshift = build_vshift(ix, N, split);
-    rc = launch_indexer_build(ctx, ix->dev, tb->d_desc, tb->T, indices, itype, table_stride, index_base, batch, lookups,
-                              split);
-    if (rc) return rc;
-    record_build(ix, split, indices, itype, table_stride, index_base, batch, lookups);
-    return DLRM_OK;
+    return build_now(ctx, ix, tb, BuildSite::Build, IndexArgs{indices, itype, table_stride, index_base, batch, lookups},
+                     BuildCaps{});
 }
 
 int dlrm_indexer_build_split(dlrm_ctx* ctx, dlrm_indexer* ix, const dlrm_tables* tb, const void* indices, int itype,
@@ -945,27 +951,8 @@ int dlrm_indexer_build_split(dlrm_ctx* ctx, dlrm_indexer* ix, const dlrm_tables*
     CHECK_ARG(tb->T == ix->T, "dlrm_indexer_build_split: indexer has %d tables, tables has %d", ix->T, tb->T);
     CHECK_ARG(batch <= ix->dev.cap, "dlrm_indexer_build_split: batch %d > capacity %lld", batch,
               (long long)ix->dev.cap);
-    ix->built = false;
-    // above the in-LDS build's 4096 positions: the bag build (configs[2]'s next-batch build at 8192, on
-    // a side stream beside the step: 94.5 vs 96.4 us per step with the in-LDS parts build -- its
-    // three launches are slower alone, 38.7 vs 17.7 us, but their small workgroups run beside the
-    // step's kernels, where the parts build's 104 workgroups of 136 KB LDS each held a whole CU;
-    // DESIGN.md §3 round 6).  DLRM_BAG_SPLIT=0: the parts / hash builds.
-    if (knobs().bag_split && batch > kFastMaxN && wave_fits(ix, batch)) {
-        ix->dev.vshift = wave_vshift(batch) - 1;
-        rc = launch_bag_build(ctx, ix->dev, tb->d_desc, tb->T, indices, itype, table_stride, index_base, batch,
-                              ctx_error_word(ctx));
-        if (rc) return rc;
-        record_build(ix, true, indices, itype, table_stride, index_base, batch, 1);
-        ix->dev.has_map = 1;
-        return DLRM_OK;
-    }
-    ix->dev.vshift = build_vshift(ix, batch, true);
-    rc = launch_indexer_build(ctx, ix->dev, tb->d_desc, tb->T, indices, itype, table_stride, index_base, batch, 1,
-                              true, nullptr);
-    if (rc) return rc;
-    record_build(ix, true, indices, itype, table_stride, index_base, batch, 1);
-    return DLRM_OK;
+    return build_now(ctx, ix, tb, BuildSite::BuildSplit, IndexArgs{indices, itype, table_stride, index_base, batch, 1},
+                     BuildCaps{});
 }
 
 int dlrm_indexer_prepare(dlrm_ctx* ctx, dlrm_indexer* ix, const dlrm_tables* tb, const void* indices, int itype,
@@ -975,27 +962,14 @@ int dlrm_indexer_prepare(dlrm_ctx* ctx, dlrm_indexer* ix, const dlrm_tables* tb,
     if (rc) return rc;
     CHECK_ARG(tb->T == ix->T, "dlrm_indexer_prepare: indexer has %d tables, tables has %d", ix->T, tb->T);
     CHECK_ARG(batch <= ix->dev.cap, "dlrm_indexer_prepare: batch %d > capacity %lld", batch, (long long)ix->dev.cap);
-    const int vs = wave_parts_log2(batch, ix);
-    if (!wave_fits(ix, batch))
-        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_indexer_prepare: batch %d (the wave build: batch <= %d, "
-                        "tables x capacity < 2^31)", batch, kWaveMaxN);
-    ix->built = false;
-    ix->prepared = false;
-    ix->dev.vshift = vs;
-    // bounds errors go to the indexer's own word, not the ctx's flag: this build usually runs on a
-    // side stream beside the current step, whose kernels read the ctx's flag to decide whether to
-    // write their rows.  The next forward / lookup of these indices raises them on the ctx's flag;
-    // the apply of this indexer folds the word in as well (a prebuilt update without a lookup).
-    rc = ctx_hip(ctx, hipMemsetAsync(ix->prep_err, 0, sizeof(unsigned), ctx->stream), "clear build bounds word");
-    if (rc) return rc;
-    rc = launch_step_prepare(ctx, ix->dev, tb->d_desc, tb->T, indices, itype, table_stride, index_base, batch,
-                             ix->prep_err);
-    if (rc) return rc;
-    record_build(ix, true, indices, itype, table_stride, index_base, batch, 1);
-    ix->prepared = true;
-    ix->dev.has_map = 1;
-    ix->dev.build_err = ix->prep_err;
-    return DLRM_OK;
+    // bounds errors go to the indexer's own word, not the ctx's flag (the plan's ErrWord::Prep0): this build usually
+    // runs on a side stream beside the current step, whose kernels read the ctx's flag to decide whether to write
+    // their rows.  The next forward / lookup of these indices raises them on the ctx's flag; the apply of this
+    // indexer folds the word in as well (a prebuilt update without a lookup).
+    BuildCaps caps{};
+    caps.idx_vec32 = idx_vec32(indices, itype, table_stride);
+    caps.cus = ctx->cus;
+    return build_now(ctx, ix, tb, BuildSite::Prepare, IndexArgs{indices, itype, table_stride, index_base, batch, 1}, caps);
 }
 
 // One (virtual) table's build, whole: rows, grouped positions, segment starts.
@@ -1255,78 +1229,56 @@ int dlrm_step_fwd(dlrm_ctx* ctx, const dlrm_tables* tb, dlrm_indexer* ix, const 
     const int64_t P = (int64_t)F * (F - 1) / 2;
     CHECK_ARG(padding >= 0 && x_ld >= d && out_ld >= d + P + padding, "dlrm_step_fwd: leading dimensions too small");
     CHECK_ARG(batch == 0 || (x && out), "dlrm_step_fwd: null buffer");
-    if (ix->prepared && built_from(ix, indices, itype, table_stride, index_base, batch, 1)) {
-        // built by the previous step's apply launch (dlrm_step_bwd_prepare): the gather alone
-        ix->prepared = false;
-        rc = launch_lookup_interact_fwd(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
-                                        index_base, 1, d, batch, x, x_ld, nullptr, 0, out, out_ld, padding, tb->h_desc.data());
-        if (rc != DLRM_E_UNSUPPORTED) return rc;  // (no fused forward for this x: build below)
+    const IndexArgs ia{indices, itype, table_stride, index_base, batch, 1};
+    const auto fused_fwd = [&] {
+        return launch_lookup_interact_fwd(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
+                                          index_base, 1, d, batch, x, x_ld, nullptr, 0, out, out_ld, padding,
+                                          tb->h_desc.data());
+    };
+    BuildCaps caps{};
+    caps.prepared = ix->prepared && built_from(ix, indices, itype, table_stride, index_base, batch, 1);
+    caps.step_fwd = step_fwd_supported(tb->aligned16, tb->T, tb->dtype, d, batch, x, x_ld, tb->h_desc.data());
+    caps.step_split = step_split_supported(tb->aligned16, tb->T, tb->dtype, d, x, x_ld);
+    BuildPlan p = plan_build(BuildSite::StepFwd, shape_of(ix), batch, knobs(), caps);
+    begin_build(ix, p);
+    if (p.form == BuildForm::Kept) {
+        // built by the previous step's apply launch (dlrm_step_bwd_prepare) or by dlrm_indexer_prepare: the gather alone
+        rc = fused_fwd();
+        if (rc != DLRM_E_UNSUPPORTED) return rc;
+        caps.prepared = false;  // (no fused forward for this x: the batch is built as any other)
+        p = plan_build(BuildSite::StepFwd, shape_of(ix), batch, knobs(), caps);
+        begin_build(ix, p);
     }
-    ix->prepared = false;
-    ix->built = false;
-    // the wave build in the forward's launch (vshift >= 2: it also writes the apply's item map)
-    ix->dev.vshift = ix->dev.cap <= kWaveApplyMaxN && wave_fits(ix, batch) ? wave_parts_log2(kStepIndexMaxN, ix) : 0;
-    rc = launch_step_fwd(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride, index_base, d,
-                         batch, x, x_ld, out, out_ld, padding, ix->dev, tb->h_desc.data());
-    if (rc == DLRM_OK) {
-        record_build(ix, true, indices, itype, table_stride, index_base, batch, 1);
-        ix->dev.has_map = ix->dev.vshift >= 2 ? 1 : 0;
+    if (p.form == BuildForm::InForward) {
+        rc = launch_step_fwd(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride, index_base, d,
+                             batch, x, x_ld, out, out_ld, padding, ix->dev, tb->h_desc.data());
+        if (rc) return rc;
+        record_build(ix, p, ia);
         return DLRM_OK;
     }
-    if (rc != DLRM_E_UNSUPPORTED) return rc;
-    ix->dev.vshift = 0;
-    const bool split_ok = step_split_supported(tb->aligned16, tb->T, tb->dtype, d, x, x_ld);
-    if (split_ok && batch <= kFastMaxN) {
-        // no single-launch form for this shape (B > 2048): the fused forward, then the split
-        // indexer in LDS (one 1024-thread workgroup per table)
-        rc = launch_lookup_interact_fwd(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype,
-                                        table_stride, index_base, 1, d, batch, x, x_ld, nullptr, 0, out, out_ld,
-                                        padding, tb->h_desc.data());
-        if (rc == DLRM_OK)
-            rc = launch_indexer_build(ctx, ix->dev, tb->d_desc, tb->T, indices, itype, table_stride, index_base,
-                                      batch, 1, true, nullptr);
-        if (rc == DLRM_OK) {
-            record_build(ix, true, indices, itype, table_stride, index_base, batch, 1);
-            return DLRM_OK;
-        }
-        if (rc != DLRM_E_UNSUPPORTED) return rc;
-    }
-    const int pvs = build_vshift(ix, batch, true);
-    if (split_ok && (pvs > 0 || ix->dev.hsize) && batch > kFastMaxN && batch <= kHixMaxN) {
-        // large batch: the split build (once-hit rows left to dlrm_step_bwd) -- in LDS by table
-        // parts up to kPartsMaxN, else the hash build -- on the side stream beside the fused
-        // forward (launched below); the main stream joins it
+    // no single-launch form for this shape: the fused forward and the plan's build -- after it on the ctx's stream,
+    // or (large batches) before it on the side stream, which the main stream joins
+    if (p.side) {
         rc = ensure_side(ctx);
         if (rc) return rc;
         rc = ctx_hip(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "hipEventRecord(fork)");
         if (rc == DLRM_OK) rc = ctx_hip(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0), "hipStreamWaitEvent(side)");
-        ix->dev.vshift = pvs;
-        if (rc == DLRM_OK)
-            rc = pvs > 0 ? launch_indexer_build(ctx, ix->dev, tb->d_desc, tb->T, indices, itype, table_stride,
-                                                index_base, batch, 1, true, ctx->side)
-                         : launch_hix_build(ctx, ix->dev, tb->d_desc, tb->T, indices, itype, table_stride, index_base,
-                                            batch, true, ctx->side);
+        if (rc == DLRM_OK) rc = run_build(ctx, ix, tb, p, ia);
         if (rc == DLRM_OK) rc = ctx_hip(ctx, hipEventRecord(ctx->ev_join, ctx->side), "hipEventRecord(join)");
         if (rc) return rc;
-        rc = launch_lookup_interact_fwd(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype,
-                                        table_stride, index_base, 1, d, batch, x, x_ld, nullptr, 0, out, out_ld,
-                                        padding, tb->h_desc.data());
-        const int rj = ctx_hip(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(main)");
-        if (rc == DLRM_E_UNSUPPORTED)
-            return ctx_fail(ctx, DLRM_E_UNSUPPORTED,
-                            "dlrm_step_fwd: no fused forward for this shape (16-B aligned rows and x, F <= 96 needed)");
-        if (rc || rj) return rc ? rc : rj;
-        record_build(ix, true, indices, itype, table_stride, index_base, batch, 1);
-        return DLRM_OK;
     }
-    // no single-launch form for this shape: the fused forward, then the (unsplit) indexer
-    rc = launch_lookup_interact_fwd(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
-                                    index_base, 1, d, batch, x, x_ld, nullptr, 0, out, out_ld, padding, tb->h_desc.data());
+    rc = fused_fwd();
+    const int rj = p.side ? ctx_hip(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(main)")
+                          : DLRM_OK;
+    // the one refusal left to meet at run time: the fused forward's own
     if (rc == DLRM_E_UNSUPPORTED)
         return ctx_fail(ctx, DLRM_E_UNSUPPORTED,
                         "dlrm_step_fwd: no fused forward for this shape (16-B aligned rows and x, F <= 96 needed)");
+    if (rc || rj) return rc ? rc : rj;
+    if (!p.side) rc = run_build(ctx, ix, tb, p, ia);
     if (rc) return rc;
-    return dlrm_indexer_build(ctx, ix, tb, indices, itype, table_stride, index_base, batch, 1);
+    record_build(ix, p, ia);
+    return DLRM_OK;
 }
 
 // The training step's backward and apply under a rule: Descent (dlrm_step_bwd), the split rule on split-bf16 tables
@@ -1409,28 +1361,24 @@ static int step_bwd_prepare_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* i
     if (rc) return rc;
     // the next batch's build runs as extra workgroups of this step's apply launch: the step
     // forward's split build (the same parts), so the next dlrm_step_fwd only gathers
-    const int NB = (tb->T + 1 + 15) / 16;
-    // (the split backward's shapes only: the apply launch that carries the build has no once-hit items)
-    const bool inapply = batch > 0 && tb->T > 0 && batch <= kWaveApplyMaxN && NB <= 2 && tb->aligned16 &&
-                         wave_fits(next, batch) && has_split_bwd(tb, r, x, x_ld);
+    BuildCaps caps{};
+    caps.split_bwd = has_split_bwd(tb, r, x, x_ld);
+    caps.bwd_only = (flags & DLRM_STEP_BWD_ONLY) != 0;
+    caps.idx_vec32 = idx_vec32(next_indices, itype, table_stride);
+    const BuildPlan p = plan_build(BuildSite::InApply, shape_of(next), batch, knobs(), caps);
     // no pipelined form for this shape: the plain step (the next forward builds); BWD_ONLY: the next build rides on
     // the apply launch
-    if (!inapply || (flags & DLRM_STEP_BWD_ONLY))
+    if (p.form == BuildForm::None)
         return step_bwd_impl(ctx, tb, ix, r, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld,
                              padding, dx, dx_ld, dt, dt_ld, flags, nullptr);
-    next->built = false;
-    next->prepared = false;
-    // the wave build: 2^wave_parts_log2(batch) parts per table, one wave each (4 per workgroup)
-    next->dev.vshift = wave_parts_log2(batch, next);
-    if (next->dev.vshift < 2) next->dev.vshift = 2;
+    begin_build(next, p);
+    // the wave build: 2^vshift parts per table, one wave each (4 per workgroup)
     const PrepArgs pa{next->dev, tb->d_desc, tb->T, next_indices, itype, table_stride, index_base, batch,
-                      next->prep_err + 1};
+                      err_word(ctx, next, p.err)};
     rc = step_bwd_impl(ctx, tb, ix, r, indices, itype, table_stride, index_base, batch, x, x_ld, dout, dout_ld, padding,
                        dx, dx_ld, dt, dt_ld, flags, &pa);
     if (rc) return rc;
-    record_build(next, true, next_indices, itype, table_stride, index_base, batch, 1);
-    next->prepared = true;
-    next->dev.has_map = 1;
+    record_build(next, p, IndexArgs{next_indices, itype, table_stride, index_base, batch, 1});
     return DLRM_OK;
 }
 

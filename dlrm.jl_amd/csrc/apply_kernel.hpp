@@ -34,14 +34,12 @@ void launch_step_index(hipStream_t s, const PrepArgs& pa);
 #endif
 constexpr int kBuildPrio = DLRM_BUILD_PRIO;  // s_setprio of the in-apply build's waves (0..3)
 
-// The build of more than 2048 positions per table: 3 = the scan build (indexer.hpp
-// wave_build_group_scan; int32 indices, 16-B aligned per table, N % 4 == 0), the default; 1 = rounds
-// (wave_build_group<true>, any index type; DLRM_WAVE_ROUNDS=1 forces it).
-static inline int wave_big_kind(const PrepArgs& pa) {
-    if (knobs().wave_rounds) return 1;
-    const bool vec32 = pa.itype == DLRM_I32 && (uintptr_t)pa.idx % 16 == 0 && (pa.tstride * 4) % 16 == 0 &&
-                       pa.N % 4 == 0;
-    return vec32 ? 3 : 1;
+// The wave build's kernel for the build `pa` (build_plan.hpp wave_kind): one round up to 2048 positions per
+// table; above, the scan build (indexer.hpp wave_build_group_scan; int32 indices, 16-B aligned per table,
+// N % 4 == 0), the default, or rounds (wave_build_group<true>, any index type; DLRM_WAVE_ROUNDS=1 forces it).
+// PrepArgs is a kernel argument and cannot carry the plan's answer, so the two launchers that take one ask here.
+static inline int prep_wave_kind(const PrepArgs& pa) {
+    return wave_kind(pa.N, idx_vec32(pa.idx, pa.itype, pa.tstride), knobs());
 }
 // workgroups of a build (4 parts each)
 __host__ __device__ __forceinline__ int prep_groups(const PrepArgs& pa) { return (pa.T << pa.ix.vshift) / kWaveParts; }
@@ -351,8 +349,8 @@ template <typename TT, typename GT, int VPR, typename R, int OCC = 0>
 static void launch_apply_build_vec(hipStream_t s, const IndexerDev& ix, TableDesc* tabs, int T_, int L, const void* grad,
                                    int64_t grad_ld, int64_t grad_offset, const R& rule, int64_t N, const unsigned* err,
                                    const SinglesArgs& sa, const PrepArgs& pa) {
-    // MODE 2: <= 2048 positions per table; above, 2 + wave_big_kind (3 rounds, 5 scan)
-    const int mode = pa.N <= kStepIndexMaxN ? 2 : 2 + wave_big_kind(pa);
+    // MODE 2 + the wave build's kind: 2 one round (<= 2048 positions per table), 3 rounds, 5 scan
+    const int mode = 2 + prep_wave_kind(pa);
     const unsigned g2 = (unsigned)(apply_grid<TT, GT, VPR, R, OCC>(ix, T_, N, sa) + prep_groups(pa));
     if (mode == 2) launch_apply_build<TT, GT, VPR, 2, R>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, pa);
     else if (mode == 5) launch_apply_build<TT, GT, VPR, 5, R>(s, g2, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, err, sa, pa);

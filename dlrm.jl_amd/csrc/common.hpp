@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/dlrm_hip.h"
+#include "build_plan.hpp"
 
 namespace dlrm {
 
@@ -223,21 +224,9 @@ struct OutMap {
     }
 };
 
-constexpr int kFastMaxN = 4096;     // in-LDS indexer (indexer.hpp): positions per table
-constexpr int kHixMaxN = 1 << 20;   // hash indexer (hashindex.hip): positions per table
-constexpr int kStepIndexMaxN = 2048;  // the forward-launch indexer (interact.hip): positions per table
-constexpr int kStepMaxParts = 16;     // ... which sorts a table as up to 16 parts (by the row's low bits)
-// the wave build (indexer.hpp wave_build_group) of the next batch (in the apply launch) or of a
-// prepared batch (dlrm_indexer_prepare, and dlrm_indexer_build's pooled bags): up to kWaveMaxN
-// positions per table, as 16 parts per 2048 positions (2^wave_vshift(N) parts per table; a part
-// averages <= 128 positions).  The in-apply build (dlrm_step_bwd_prepare) takes up to
-// kWaveApplyMaxN (its scan build keeps a quarter of the table's indices in registers).
-constexpr int kWaveMaxN = 32768;
-constexpr int kWaveApplyMaxN = 16384;
-constexpr int kWaveMaxVshift = 8;
-__host__ __device__ constexpr int wave_vshift(int64_t N) {
-    return N <= 2048 ? 4 : (N <= 4096 ? 5 : (N <= 8192 ? 6 : (N <= 16384 ? 7 : 8)));
-}
+// (kFastMaxN, kHixMaxN, kStepIndexMaxN, kWaveMaxN, kWaveApplyMaxN, kWaveMaxVshift, wave_vshift, kWaveBuildParts,
+// kPartsMaxN, kPartsLog2, kStepParts: build_plan.hpp, with the choice of build that rests on them)
+constexpr int kStepMaxParts = 16;     // the forward-launch indexer sorts a table as up to 16 parts (by the row's low bits)
 // The wave builds' per-part arrays are packed per table (round 6, "compact" layout): part q of
 // table t (virtual table v = (t << vs) + q) keeps its entries at t * cap + off_q, off_q = the
 // table's positions in parts < q (IndexerDev::counts[v][CNT_OFF]); its segment starts at
@@ -246,24 +235,6 @@ __host__ __device__ constexpr int wave_vshift(int64_t N) {
 // cap: 128 x the table at 16384 positions).
 constexpr int kSegPad = 1 << kWaveMaxVshift;
 constexpr int kCntOff = 5;  // counts[v][kCntOff]: the part's offset in its table (wave builds)
-// the next batch's split build in the apply launch (indexer.hpp wave_build_group): parts per
-// table, one wave each, 4 per workgroup (>= 4)
-#ifndef DLRM_WAVE_PARTS
-#define DLRM_WAVE_PARTS 16
-#endif
-constexpr int kWaveBuildParts = DLRM_WAVE_PARTS;
-// split builds of kFastMaxN < N <= kPartsMaxN positions per table: the in-LDS build (1024
-// threads x 8 positions) over 2^kPartsLog2 parts per table (by the row's low bits), each part's
-// workgroup sized for the worst case (all N positions in one part); larger N: the hash build
-constexpr int kPartsMaxN = 8192;
-#ifndef DLRM_BUILD_PARTS_LOG2
-#define DLRM_BUILD_PARTS_LOG2 2
-#endif
-constexpr int kPartsLog2 = DLRM_BUILD_PARTS_LOG2;
-#ifndef DLRM_STEP_PARTS_DEFAULT
-#define DLRM_STEP_PARTS_DEFAULT 4
-#endif
-constexpr int kStepParts = DLRM_STEP_PARTS_DEFAULT;
 
 struct IndexerDev {
     uint32_t* keys0;  uint32_t* keys1;   // global sort scratch (cap > kLdsSortMax)
@@ -345,26 +316,7 @@ int ctx_hip(dlrm_ctx* ctx, hipError_t e, const char* what);
 int ctx_num_cus(dlrm_ctx* ctx);
 int ctx_device(dlrm_ctx* ctx);
 
-// Comparison knobs: every environment variable the library reads, read once (abi.cpp), in this
-// one place.  0 = the default (the measured-best form); a non-zero value forces a variant for
-// A/B runs.  None is needed for correctness.
-struct Knobs {
-    int step_parts;   // DLRM_STEP_PARTS  (1/2/4/8): table parts of the step's split indexer build
-    int build_parts;  // DLRM_BUILD_PARTS (2/4/8): parts of a standalone split build, 4096 < N <= 8192
-    int relu_1pass;   // DLRM_RELU_2PASS=0: the one-launch (last-arriver) relu seam instead of two launches
-    int bwd_ys_body;  // DLRM_BWD_YS=0: the bwd_body kernel for a materialized ys with 33..96 features
-    int bwd_nosplit;  // DLRM_BWD_SPLIT=0: the one-wave step backward instead of the split kernel
-    int bwd_spb;      // DLRM_BWD_SPB (2/4/8): samples per block of the split step backward
-    int bwd_cpl;      // DLRM_BWD_CPL (4/8): columns per lane of the bf16 split step backward
-    int upd_sbu;      // DLRM_UPD_SBU (1/2): super-blocks in flight in the one-wave step backward
-    int wave_rounds;  // DLRM_WAVE_ROUNDS=1: the wave build in rounds above 2048 positions per table
-                      // instead of the scan build
-    int bag_hash;     // DLRM_BAG_WAVE=0: dlrm_indexer_build of 8192 < N <= 32768 positions per table (pooled
-                      // bags) by the hash build instead of the bag build
-    int bag_vs;       // DLRM_BAG_VS (2..8): the bag build's log2 parts per table (default wave_vshift(N))
-    int bag_split;    // DLRM_BAG_SPLIT=0: dlrm_indexer_build_split of 4096 < N <= 32768 by the in-LDS parts /
-                      // hash builds instead of the bag build
-};
+// The comparison knobs (build_plan.hpp Knobs), read from the environment once
 const Knobs& knobs();
 
 // The optimizer rules of the update and of the training step.  abi.cpp's kRules describes each one on the host
@@ -412,8 +364,10 @@ int launch_interact_bwd(dlrm_ctx* ctx, int dtype, int d, int F, int B, const voi
                         const void* t, int64_t t_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld);
 int64_t hix_table_slots(int64_t cap);
 int launch_hix_build(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* tabs, int T, const void* idx, int itype,
-                     int64_t tstride, int base, int N, bool split, hipStream_t stream = nullptr);
+                     int64_t tstride, int base, int N, bool split, unsigned* err, hipStream_t stream = nullptr);
 bool step_split_supported(bool tabs_aligned16, int T, int dtype, int d, const void* x, int64_t x_ld);
+bool step_fwd_supported(bool tabs_aligned16, int T, int dtype, int d, int B, const void* x, int64_t x_ld,
+                        const TableDesc* htabs);
 int launch_maplookup_map(dlrm_ctx* ctx, const TableDesc* d_tabs, bool tabs_aligned16, int T, int D, int dtype,
                          const void* idx, int itype, int64_t tstride, int base, int B, int L, void* out,
                          const OutMap& om, const TableDesc* htabs = nullptr);
@@ -427,9 +381,10 @@ int launch_relu_bwd_bias(dlrm_ctx* ctx, int B, int N, const float* y, int64_t y_
                          float* part, unsigned* counters);
 int launch_scatter_rows(dlrm_ctx* ctx, int esize, int T, int B, int D, const void* src, int64_t src_ld,
                         int64_t src_off, void* dst, const int64_t* dbase, const int64_t* dld, bool vec_ok);
+// form: Lds2, Lds4, LdsParts (split only), Hash or Sorted (unsplit only) -- build_plan.hpp standalone_form
 int launch_indexer_build(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* tabs, int T, const void* idx,
-                         int itype, int64_t tstride, int base, int B, int L, bool split = false,
-                         hipStream_t stream = nullptr);
+                         int itype, int64_t tstride, int base, int B, int L, BuildForm form, bool split,
+                         unsigned* err, hipStream_t stream = nullptr);
 int launch_bag_build(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* tabs, int T, const void* idx, int itype,
                      int64_t tstride, int base, int N, unsigned* err);
 int launch_step_prepare(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* tabs, int T, const void* idx, int itype,

@@ -334,7 +334,7 @@ int64_t hix_table_slots(int64_t cap) {
 }
 
 int launch_hix_build(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* tabs, int T_, const void* idx, int itype,
-                     int64_t tstride, int base, int N, bool split, hipStream_t stream) {
+                     int64_t tstride, int base, int N, bool split, unsigned* err, hipStream_t stream) {
     hipStream_t s = stream ? stream : ctx_stream(ctx);
     if (T_ == 0 || N == 0) {
         // empty batch: every table reports zero segments
@@ -346,7 +346,7 @@ int launch_hix_build(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* tabs,
                         (long long)ix.cap, (long long)ix.hsize);
     const dim3 gp((N + kHixTile - 1) / kHixTile, T_), gs((unsigned)(ix.hsize / (256 * kHixSPT)), T_);
     hipLaunchKernelGGL(hix_insert_kernel, gp, dim3(256), 0, s, ix, tabs, idx, itype, tstride, base, N,
-                       ctx_error_word(ctx));
+                       err);
     hipLaunchKernelGGL(hix_alloc_kernel, gs, dim3(256), 0, s, ix, split ? 1 : 0);
     hipLaunchKernelGGL(hix_place_kernel, gp, dim3(256), 0, s, ix, N, split ? 1 : 0);
     const size_t nw = (size_t)(N + 31) / 32;

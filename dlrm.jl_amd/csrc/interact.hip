@@ -1704,7 +1704,9 @@ int launch_interact_bwd_gather(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_a
             return ctx_hip(ctx, hipGetLastError(), "interact_bwd(+indexer) launch");
         }
         // no fused form for this shape: the indexer's own launch, then the backward
-        const int rc = launch_indexer_build(ctx, *ix, tabs, T_, idx, itype, tstride, base, B, L);
+        const int rc = launch_indexer_build(ctx, *ix, tabs, T_, idx, itype, tstride, base, B, L,
+                                            standalone_form((int64_t)B * L, ix->hsize, false), false,
+                                            ctx_error_word(ctx));
         if (rc) return rc;
     }
     return run_interact_bwd<true>(ctx, dtype, d, T_ + 1, B, dout, dout_ld, nullptr, 0, dx, dx_ld, dt, dt_ld, ga,
@@ -1763,6 +1765,16 @@ int launch_interact_bwd_blocked(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_
 bool step_split_supported(bool tabs_aligned16, int T_, int dtype, int d, const void* x, int64_t x_ld) {
     const int NB = (T_ + 1 + 15) / 16;
     return T_ > 0 && tabs_aligned16 && fwd_aligned(dtype, d, x, x_ld, nullptr, 0) && NB <= 2;
+}
+
+// Shapes launch_step_fwd has a kernel for: exactly its refusals, asked before the build is planned
+// (build_plan.hpp BuildCaps::step_fwd).
+bool step_fwd_supported(bool tabs_aligned16, int T_, int dtype, int d, int B, const void* x, int64_t x_ld,
+                        const TableDesc* htabs) {
+    const int NB = (T_ + 1 + 15) / 16;
+    TabPtrs tp{};
+    return B != 0 && T_ != 0 && tabs_aligned16 && fwd_aligned(dtype, d, x, x_ld, nullptr, 0) && NB <= 2 &&
+           B <= kStepIndexMaxN && fill_tab_ptrs(tp, htabs, T_);
 }
 
 // Training-step forward (split indexer in the same grid).  DLRM_E_UNSUPPORTED when the shape

@@ -399,14 +399,15 @@ static void launch_step_index_kind(hipStream_t s, const PrepArgs& pa) {
 
 // step_index_kernel's own launch (the next batch's split build when the apply launch cannot carry it)
 void launch_step_index(hipStream_t s, const PrepArgs& pa) {
-    const int kind = pa.N <= kStepIndexMaxN ? 0 : wave_big_kind(pa);
-    if (kind == 0) launch_step_index_kind<0>(s, pa);
-    else if (kind == 1) launch_step_index_kind<1>(s, pa);
-    else if (pa.N > kWaveApplyMaxN)  // (pooled bags: 64 tables x 20480; 16 waves keep 8 pieces each in registers)
+    const int kind = prep_wave_kind(pa);
+    if (kind == kWaveOneRound) launch_step_index_kind<0>(s, pa);
+    else if (kind == kWaveRounds) launch_step_index_kind<1>(s, pa);
+    else if (pa.N > kWaveApplyMaxN)  // (16 waves keep 8 pieces each in registers)
         launch_step_index_scan<16, kWaveMaxN>(s, pa);
-    else if (prep_groups(pa) <= pa_cus(pa)) launch_step_index_scan<16>(s, pa);
+    else if (wave_waves(kind, pa.N, prep_groups(pa), pa_cus(pa)) == 16) launch_step_index_scan<16>(s, pa);
     else launch_step_index_scan<8>(s, pa);
 }
+static_assert(kWaveGroupParts == kWaveParts, "build_plan.hpp counts a build's workgroups as the kernels do");
 
 // ---------------------------------------------------------------- bag build (8192 < N <= 32768)
 // dlrm_indexer_build of many positions per table (configs[4]'s pooled bags: 64 tables x 20480,
@@ -802,34 +803,37 @@ static void launch_fast(hipStream_t s, const IndexerDev& ix, const TableDesc* ta
                        s, ix, tabs, idx, itype, tstride, base, N, err);
 }
 
+// The builds with a launch of their own, by the form the plan chose (build_plan.hpp standalone_form).
 // split: the form dlrm_step_bwd consumes (once-hit positions flagged, their rows left to the
-// backward).  stream: NULL = the context's stream.
+// backward).  err: the word for bounds errors.  stream: NULL = the context's stream.
 int launch_indexer_build(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* tabs, int T_, const void* idx,
-                         int itype, int64_t tstride, int base, int B, int L, bool split, hipStream_t stream) {
+                         int itype, int64_t tstride, int base, int B, int L, BuildForm form, bool split,
+                         unsigned* err, hipStream_t stream) {
     if (T_ == 0) return DLRM_OK;
     hipStream_t s = stream ? stream : ctx_stream(ctx);
-    const int64_t N = (int64_t)B * L;
-    unsigned* err = ctx_error_word(ctx);
-    if (ix.vshift > 0) {  // the caller chose the parts build (kFastMaxN < N <= kPartsMaxN, split)
-        if (!split || N > kPartsMaxN)
-            return ctx_fail(ctx, DLRM_E_ARG, "indexer parts build: N=%lld split=%d", (long long)N, (int)split);
-        launch_fast<1024, 8, true>(s, ix, tabs, T_, idx, itype, tstride, base, (int)N, err);
-    } else if (N <= 1024 * 2) {
-        if (split) launch_fast<1024, 2, true>(s, ix, tabs, T_, idx, itype, tstride, base, (int)N, err);
-        else launch_fast<1024, 2, false>(s, ix, tabs, T_, idx, itype, tstride, base, (int)N, err);
-    } else if (N <= kFastMaxN) {  // (8 positions per thread, one workgroup per table: slower than the hash
-                                  // build at N = 8192; in 4 parts per table it is the faster one)
-        if (split) launch_fast<1024, 4, true>(s, ix, tabs, T_, idx, itype, tstride, base, (int)N, err);
-        else launch_fast<1024, 4, false>(s, ix, tabs, T_, idx, itype, tstride, base, (int)N, err);
-    } else if (ix.hsize && N <= kHixMaxN) {
-        return launch_hix_build(ctx, ix, tabs, T_, idx, itype, tstride, base, (int)N, split, s);
-    } else if (split) {
-        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "split indexer build: %lld positions per table", (long long)N);
-    } else {
+    const int N = (int)((int64_t)B * L);
+    switch (form) {
+    case BuildForm::LdsParts:
+        if (!split) break;
+        launch_fast<1024, 8, true>(s, ix, tabs, T_, idx, itype, tstride, base, N, err);
+        return ctx_hip(ctx, hipGetLastError(), "indexer_build launch");
+    case BuildForm::Lds2:
+        if (split) launch_fast<1024, 2, true>(s, ix, tabs, T_, idx, itype, tstride, base, N, err);
+        else launch_fast<1024, 2, false>(s, ix, tabs, T_, idx, itype, tstride, base, N, err);
+        return ctx_hip(ctx, hipGetLastError(), "indexer_build launch");
+    case BuildForm::Lds4:
+        if (split) launch_fast<1024, 4, true>(s, ix, tabs, T_, idx, itype, tstride, base, N, err);
+        else launch_fast<1024, 4, false>(s, ix, tabs, T_, idx, itype, tstride, base, N, err);
+        return ctx_hip(ctx, hipGetLastError(), "indexer_build launch");
+    case BuildForm::Hash: return launch_hix_build(ctx, ix, tabs, T_, idx, itype, tstride, base, N, split, err, s);
+    case BuildForm::Sorted:
+        if (split) break;
         hipLaunchKernelGGL(indexer_build_kernel<false>, dim3(T_), dim3(kBuildThreads), 0, s, ix, tabs, idx, itype,
                            tstride, base, B, L, err);
+        return ctx_hip(ctx, hipGetLastError(), "indexer_build launch");
+    default: break;
     }
-    return ctx_hip(ctx, hipGetLastError(), "indexer_build launch");
+    return ctx_fail(ctx, DLRM_E_ARG, "indexer build: form %d split=%d has no launch of its own", (int)form, (int)split);
 }
 
 int launch_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool tabs_aligned16, int T_, int D,

@@ -274,9 +274,11 @@ class HotPath:
 
     def build_split(self, indexer, idx):
         """The indexer form dlrm_step_bwd consumes: the wave build (dlrm_indexer_prepare) for one-hot
-        batches of <= shapes.APPLY_MAX_N positions per table, else dlrm_indexer_build_split (the
-        in-LDS parts build up to 8192 positions, the hash build above: beside a step of B = 8192 the
-        parts build's 104 workgroups cost the step less than the wave build's 416)."""
+        batches of <= shapes.APPLY_MAX_N positions per table, else dlrm_indexer_build_split (in LDS up
+        to 4096 positions, the bag build up to 32768, the hash build above: beside a step of B = 8192
+        the bag build's small workgroups cost the step less than the wave build's 416 or the in-LDS
+        parts build's 104 of 136 KB LDS each; DLRM_BAG_SPLIT=0 selects the parts / hash builds.
+        DESIGN.md section 20 has the table)."""
         h = self.ctx.bind()
         if idx.L == 1 and self.B <= APPLY_MAX_N and self._prepare_ok is not False:
             rc = self.lib.dlrm_indexer_prepare(h, indexer.handle, self.ts.handle, ptr(idx.data), idx.itype,

@@ -43,8 +43,10 @@ WORKLOADS = {
 
 WAVE_MAX_N = 32768  # the wave build's positions per table (csrc/common.hpp kWaveMaxN)
 # One GPU: the in-apply wave build, and the side stream's wave build, up to APPLY_MAX_N positions per
-# table; above, the side stream's in-LDS parts build (configs[2] at 8192: 85.3 M samples/s, against
-# 69 M with the scan build in the apply launch and 82 M with it on the side stream, round 5).  The
+# table; above, dlrm_indexer_build_split on the side stream -- since round 6 the bag build (configs[2]
+# at 8192: 94.5 against 96.4 us per step with the in-LDS parts build it replaced there, which had given
+# 85.3 M samples/s against 69 M with the scan build in the apply launch and 82 M with it on the side
+# stream, round 5; DESIGN.md section 20 has the table of builds).  The
 # sharded update's indexer: the wave build up to PREPARE_MAX_N (the scan build: 13.4 us for 4
 # tables x 16384 positions, against 40 us for the hash build).  DLRM_APPLY_MAX_N / DLRM_PREPARE_MAX_N
 # override, for A/B runs.

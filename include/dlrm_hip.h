@@ -229,9 +229,12 @@ int dlrm_indexer_destroy(dlrm_indexer* indexer);
 /* Dedupe: per table, group the lookup positions by row -> one segment per distinct row
  * holding the positions that hit it in ascending order (segment order is unspecified).
  * Asynchronous; device-side counts only.  By batch * lookups positions per table: <= 4096 in LDS
- * (one workgroup per table), <= 8192 in LDS over 4 parts, <= 32768 the bag build (count, place by
- * part, per-part sort: pooled bags, round 6; DLRM_BAG_WAVE=0 selects the next form instead), above
- * that the hash build.  Out-of-range indices are left out and raise the bounds flag. */
+ * (one workgroup per table); <= 8192 in LDS over 4 parts where the indexer was created for 4097..8192
+ * positions, else the hash build; <= 32768 (and tables x capacity < 2^31) the bag build (count, place
+ * by part, per-part sort: pooled bags, round 6; DLRM_BAG_WAVE=0 selects the hash build instead); up to
+ * 2^20 the hash build; above, one workgroup per table sorting in HBM.  Up to 2^20 the build is split
+ * (once-hit positions flagged, not listed; the update takes them from the flags).  Out-of-range
+ * indices are left out and raise the ctx's bounds flag.  DESIGN.md section 20 has the table. */
 int dlrm_indexer_build(dlrm_ctx* ctx, dlrm_indexer* indexer, const dlrm_tables* tables,
                        const void* indices, int itype, int64_t table_stride, int index_base,
                        int batch, int lookups);
@@ -240,7 +243,10 @@ int dlrm_indexer_build(dlrm_ctx* ctx, dlrm_indexer* indexer, const dlrm_tables* 
  * rows are listed for the apply.  dlrm_step_fwd builds it inside the forward's launch; building
  * it here instead lets a caller prepare the NEXT batch's indexer ahead of time (it depends only
  * on the indices, e.g. on a side stream during the current step) and run a step as
- * dlrm_lookup_interact_fwd(ys = NULL) + dlrm_step_bwd. */
+ * dlrm_lookup_interact_fwd(ys = NULL) + dlrm_step_bwd.  By batch positions per table: <= 4096 in
+ * LDS; <= 32768 (and tables x capacity < 2^31) the bag build (DLRM_BAG_SPLIT=0: the forms of
+ * dlrm_indexer_build without it, split); up to 2^20 the hash build; above, DLRM_E_UNSUPPORTED and the
+ * indexer is left as it was.  Bounds errors go to the ctx's flag. */
 int dlrm_indexer_build_split(dlrm_ctx* ctx, dlrm_indexer* indexer, const dlrm_tables* tables,
                              const void* indices, int itype, int64_t table_stride, int index_base,
                              int batch);

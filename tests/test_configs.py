@@ -161,7 +161,7 @@ def test_bench_form_vs_oracle(pkg, gpu, workload):
 # ---------------------------------------------------------------------------- configs[2]
 def test_kaggle_bf16_b8192_step_vs_oracle(pkg, gpu):
     """configs[2]: the full Kaggle tables (33.8M rows x 128 bf16 = 8.6 GB), B = 8192, uniform
-    indices: the step (hash indexer on the side stream, bf16 MFMA interaction, once-hit rows
+    indices: the step (split build on the side stream, bf16 MFMA interaction, once-hit rows
     updated in the backward) against the oracle on the touched rows."""
     rows = pkg.KAGGLE_EMBEDDING_SIZES
     D, B = 128, 8192

@@ -212,7 +212,7 @@ def _np_segments(idx_row):
                                            ([2], 1, 1, None), ([100000, 3], 5000, 1, None), ([256, 257, 70000], 2048, 1, None),
                                            ([300, 100000, 5_000_000], 2048, 1, 1.1), ([100000, 1000], 4000, 2, 1.2),
                                            ([0x10000, 0x1000000], 1500, 1, None),
-                                           # hash build (N > 4096): all-distinct, tiny, skewed, pooled
+                                           # N > 4096 (in LDS by parts up to a capacity of 8192, the bag build above): all-distinct, tiny, skewed, pooled
                                            ([3, 4, 10, 1000, 5_000_000], 8192, 1, None),
                                            ([1_000_000, 1_000_000, 3], 2048, 10, 1.2),
                                            ([2, 100000, 33_000_000], 16384, 1, None),
@@ -568,9 +568,9 @@ def test_sgd_update_hash_build_vs_oracle(pkg, gpu, rows, B, L, zipf):
 
 @pytest.mark.parametrize("B", [6000, 9000])
 def test_hash_build_bounds_error_and_reuse(pkg, gpu, B):
-    """Large-N builds (the hash build beyond 4096 positions): an out-of-range index is
-    skipped and flagged; the next build with the same indexer (hash slots reset by the
-    previous build) is exact again."""
+    """Large-N builds (beyond 4096 positions: in LDS by parts at 6000, the bag build at 9000; the hash build
+    takes neither size since the bag build): an out-of-range index is skipped and flagged; the next build with
+    the same indexer is exact again."""
     rows = [10, 50000]
     rng = np.random.default_rng(11)
     idx = rand_indices(rng, rows, B, 1)
@@ -709,10 +709,10 @@ def test_hotpath_step_matches_operator_sequence(pkg, gpu, overlap, materialize):
     ([5, 100000, 3, 77] * 6 + [9, 10], 128, 300, None, torch.bfloat16),
     ([300, 100000, 5_000_000], 64, 3000, None, torch.float32),         # N > 2048: unsplit fallback
     ([300, 100000, 3, 5_000_000], 64, 3000, 1.1, torch.float32),       # 2048 < N <= 4096: split in-LDS build
-    ([300, 100000, 3, 5_000_000], 64, 6000, 1.1, torch.float32),       # N > 4096: split hash build
+    ([300, 100000, 3, 5_000_000], 64, 6000, 1.1, torch.float32),       # N > 4096: split parts build, side stream
     ([5, 100000, 3, 77] * 6 + [9, 10], 128, 8192, None, torch.bfloat16),  # configs[2] shape (bf16, B=8192)
     ([50] * 40, 32, 200, None, torch.float32),                         # F = 41: unsplit fallback
-    ([50] * 40, 32, 6000, None, torch.float32),                        # F = 41, N > 4096: unsplit hash build
+    ([50] * 40, 32, 6000, None, torch.float32),                        # F = 41, N > 4096: dlrm_indexer_build's row
     ([1], 16, 64, None, torch.float32),                                # every position hits one row
     ([10, 3000, 7, 100000, 3], 256, 512, 1.2, torch.float32),          # 1-KB rows: 4 chunks per lane group
     ([10, 3000, 7, 100000, 3] * 3, 8, 37, 1.1, torch.bfloat16),        # d <= 64: one backward wave per sample
