@@ -56,10 +56,20 @@ def test_golden_full_step(pkg, gpu, golden, kind):
 
 
 # ------------------------------------------------------------------ lookup
-@pytest.mark.parametrize("dim", [4, 8, 16, 32, 64, 128, 256, 12])
+@pytest.mark.parametrize("dim", [4, 8, 16, 32, 64, 128, 256, 12, 512, 1024])
 @pytest.mark.parametrize("lookups", [1, 3])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_lookup_vs_oracle(pkg, gpu, dim, lookups, dtype):
+    _lookup_vs_oracle(pkg, gpu, dim, lookups, dtype)
+
+
+@pytest.mark.parametrize("lookups", [1, 3])
+def test_lookup_vs_oracle_4kb_bf16_rows(pkg, gpu, lookups):
+    """dim 2048 bf16: a 4-KB row, the whole zero row, the longest the vector kernel takes (fp32: dim 1024 above)."""
+    _lookup_vs_oracle(pkg, gpu, 2048, lookups, torch.bfloat16)
+
+
+def _lookup_vs_oracle(pkg, gpu, dim, lookups, dtype):
     rng = np.random.default_rng(dim * 10 + lookups)
     rows = [5, 1000, 3, 77]
     B = 37
@@ -73,6 +83,38 @@ def test_lookup_vs_oracle(pkg, gpu, dim, lookups, dtype):
     ref = np.zeros((B, P + dim * len(rows)), dtype=ref_tabs[0].dtype)
     oracle.maplookup(ref_tabs, idx, 0, B, lookups, ref, P)
     assert np.array_equal(to_np_bits(out)[:, P:], ref[:, P:])
+
+
+def test_pooled_lookup_dim1024_bad_index_in_a_bag(pkg, gpu):
+    """Pooled bags of 5 at dim 1024 fp32 (four 16-B vectors per lane) through HotPath.lookup, so the output can be read
+    before check_bounds: an out-of-range index counts as a row of zeros in its place, the bag's other four rows are
+    summed in k order, the flag is raised and no other bag changes."""
+    rng = np.random.default_rng(1024)
+    rows, B, L, D = [5, 1000, 3, 77], 37, 5, 1024
+    T = len(rows)
+    tabs = rand_tables(rng, rows, D)
+    idx = rand_indices(rng, rows, B, L)
+    hp = pkg.HotPath(pkg.EmbeddingTableSet(dev_tables(tabs, gpu)), B, L, index_base=0)
+    assert hp.materialize_ys
+    hp.ys.zero_()
+    hp.lookup(pkg.PackedIndices(torch.from_numpy(idx).reshape(T, B, L).to(gpu)))
+    hp.check_bounds()
+    ref = np.zeros((B, (T + 1) * D), dtype=np.float32)
+    oracle.maplookup(tabs, idx, 0, B, L, ref, D)
+    assert np.array_equal(to_np_f32(hp.ys)[:, D:], ref[:, D:])
+    bad = idx.copy()
+    for b, t, k, value in ((11, 1, 2, rows[1]), (30, 3, 0, -1)):  # (past the end in mid-bag; negative, the bag's first)
+        bad[t, b * L + k] = value
+        acc = np.zeros(D, dtype=np.float32)
+        for kk in range(L):
+            row = np.zeros(D, dtype=np.float32) if kk == k else tabs[t][idx[t, b * L + kk]]
+            acc = row.copy() if kk == 0 else acc + row
+        ref[b, (t + 1) * D:(t + 2) * D] = acc
+    hp.lookup(pkg.PackedIndices(torch.from_numpy(bad).reshape(T, B, L).to(gpu)))
+    got = to_np_f32(hp.ys)
+    with pytest.raises(pkg.BoundsError):
+        hp.check_bounds()
+    assert np.array_equal(got[:, D:], ref[:, D:])
 
 
 @pytest.mark.parametrize("ntab", [31, 33, 40])
@@ -511,7 +553,7 @@ def test_backward_built_indexer(pkg, gpu, rows, B, zipf):
     _assert_segments(hp.indexer, idx, B)
 
 
-@pytest.mark.parametrize("dim", [16, 128, 256, 8, 12])
+@pytest.mark.parametrize("dim", [16, 128, 256, 8, 12, 512])
 @pytest.mark.parametrize("L", [1, 4])
 def test_sgd_update_vs_oracle(pkg, gpu, dim, L):
     rng = np.random.default_rng(dim + 100 * L)
