@@ -12,6 +12,7 @@ from .dac import DAC_DTYPE, DACLoader, DACMaps
 from .dense import DenseMLP, DLRMModel, ShardedDLRMModel, bce_loss, bce_loss_back, kaggle_mlp_sizes, random_mlp
 from .embedding import (DefaultStrategy, EmbeddingTableSet, PackedIndices, PreallocationStrategy, SimpleEmbedding,
                         lookup, maplookup)
+from .evaluate import Evaluator, eval_reference
 from .hotpath import HotPath
 from .lazy import DeferredUpdate, HipTables, LazyGrad, LazyLookup
 from .interact import (POST_INTERACTION_PAD_TO_MUL, DotInteraction, cdiv, dot_back, dot_interaction, fast_vcat,
@@ -32,5 +33,5 @@ __all__ = [
     "dot_interaction", "rrule_dot_interaction", "triangular_slice", "triangular_slice_back", "rrule_triangular_slice",
     "self_batched_mul", "rrule_self_batched_mul", "step_pipeline", "step_chunk", "step_parts", "zipf_perm", "HipTables", "LazyLookup",
     "LazyGrad", "DeferredUpdate", "ADAGrad", "RowwiseADAGrad", "SplitDescent", "split_f32", "merge_split",
-    "StochasticDescent", "sr_round", "sr_bits", "philox4x32_10",
+    "StochasticDescent", "sr_round", "sr_bits", "philox4x32_10", "Evaluator", "eval_reference",
 ]

@@ -107,6 +107,8 @@ SIGNATURES = {
     "dlrm_sr_sgd_seek": (_i32, [_vp, _vp, _i64]),
     "dlrm_sr_sgd_step": (_i32, [_vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),
     "dlrm_bce_head":(_i32, [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "dlrm_eval_layout": (_i32, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _pi64]),
+    "dlrm_eval_accumulate": (_i32, [_vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp]),
     "dlrm_relu_bwd_bias_workspace": (_i32, [_i32, _i32, _pi64, _pi64]),
     "dlrm_relu_bwd_bias": (_i32, [_vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "dlrm_dac_parse_tsv": (_i32, [_vp, _i64, _vp, _i64, _pi64]),

@@ -553,6 +553,26 @@ int dlrm_bce_head(dlrm_ctx* ctx, int batch, const float* logits, int64_t logits_
     return launch_bce_head(ctx, batch, logits, logits_ld, labels, prob, dlogit, loss, dbias);
 }
 
+// ---------------------------------------------------------------------- evaluation
+int dlrm_eval_layout(int* bins, int* shift, int64_t* words) {
+    if (!bins || !shift || !words) return DLRM_E_ARG;
+    *bins = kEvalBins;
+    *shift = kEvalShift;
+    *words = kEvalWords;
+    return DLRM_OK;
+}
+
+int dlrm_eval_accumulate(dlrm_ctx* ctx, int64_t* state, int batch, const float* scores, int64_t scores_ld, int is_prob,
+                         const float* labels, float* prob) {
+    CHECK_ARG(ctx, "dlrm_eval_accumulate: null ctx");
+    CHECK_ARG(batch >= 1 && scores_ld >= 1, "dlrm_eval_accumulate: batch=%d scores_ld=%lld", batch,
+              (long long)scores_ld);
+    CHECK_ARG(state && scores && labels, "dlrm_eval_accumulate: null buffer");
+    CHECK_ARG((uintptr_t)state % 8 == 0, "dlrm_eval_accumulate: state must be 8-B aligned");
+    return launch_eval_accumulate(ctx, reinterpret_cast<unsigned long long*>(state), batch, scores, scores_ld,
+                                  is_prob != 0, labels, prob);
+}
+
 int dlrm_relu_bwd_bias_workspace(int batch, int n, int64_t* work_floats, int64_t* counters) {
     if (batch < 0 || n < 0 || !work_floats || !counters) return DLRM_E_ARG;
     *work_floats = relu_bwd_chunks(batch) * (int64_t)n;

@@ -375,6 +375,14 @@ int launch_dac_decode(dlrm_ctx* ctx, const void* rec, int B, float* labels, floa
                       void* sparse, int itype, int64_t tstride);
 int launch_bce_head(dlrm_ctx* ctx, int B, const float* z, int64_t z_ld, const float* y, float* prob, float* dz,
                     float* loss, float* dbias);
+// dlrm_eval_accumulate's state (eval.hip): kEvalHeader counter words, then hist[2][kEvalBins] over the float bits
+// of a probability in [0, 1] shifted right by kEvalShift (10 mantissa bits kept)
+constexpr int kEvalShift = 13;
+constexpr int kEvalBins = (0x3F800000 >> kEvalShift) + 1;
+constexpr int kEvalHeader = 8;
+constexpr int64_t kEvalWords = kEvalHeader + 2 * (int64_t)kEvalBins;
+int launch_eval_accumulate(dlrm_ctx* ctx, unsigned long long* state, int B, const float* scores, int64_t scores_ld,
+                           bool is_prob, const float* labels, float* prob);
 int64_t relu_bwd_chunks(int B);
 int64_t relu_bwd_groups(int N);
 int launch_relu_bwd_bias(dlrm_ctx* ctx, int B, int N, const float* y, int64_t y_ld, float* g, int64_t g_ld, float* gb,

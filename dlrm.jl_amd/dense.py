@@ -27,7 +27,8 @@ import torch.distributed as dist
 
 from . import _lib
 
-from .embedding import EmbeddingTableSet
+from .embedding import EmbeddingTableSet, PackedIndices
+from .evaluate import Evaluator
 from .hotpath import HotPath
 from .interact import interaction_sizes
 from .runtime import context, ptr, require_device
@@ -115,6 +116,19 @@ class DenseMLP:
         self._acts = acts
         self._logits = logits and self.sigmoid_last
         return acts[-1]
+
+    def infer(self, x, *, logits=False):
+        """`forward` without keeping anything: the activations of the last training forward (what its
+        backward reads) stay as they are."""
+        n = len(self.W)
+        for i in range(n):
+            if i == n - 1 and self.sigmoid_last:
+                x = torch.addmm(self.b[i], x, self.W[i].t())
+                if not logits:
+                    x = torch.sigmoid(x)
+            else:
+                x = torch._addmm_activation(self.b[i], x, self.W[i].t())
+        return x
 
     def _relu_seam(self, i, g):
         """relu pullback + bias gradient of layer i: one HIP launch on the GPU (dlrm_relu_bwd_bias),
@@ -210,6 +224,7 @@ class DLRMModel:
         self.tdtype = ts.dtype
         self.loss = None
         self.prob = None
+        self._dz = self._head_prob = None
         bottom.flatten()  # one Descent launch per MLP
         top.flatten()
 
@@ -223,15 +238,50 @@ class DLRMModel:
         self.prob = self.top.forward(out.float()).reshape(-1)
         return self.prob
 
+    def predict(self, dense, sparse):
+        """The model call for evaluation: the logits [B][1] of a batch (the sigmoid is `Evaluator.add`'s, with
+        dlrm_bce_head's expression).  Bottom MLP, `HotPath.infer`, top MLP: nothing a training step keeps is
+        touched -- no indexer, no saved activation, no optimizer state -- so it can run between two steps."""
+        if not isinstance(sparse, PackedIndices):
+            sparse = PackedIndices(sparse, device=self.tables.device)
+        x = self.bottom.infer(dense)
+        out = self.hot.infer(x.to(self.tdtype), sparse)
+        return self.top.infer(out.float(), logits=True)
+
+    def test(self, data, record=None, evaluator=None, probs=None):
+        """The reference's `test(model, data; record, strategy)` (src/train/utils.jl:31-46): for every
+        (labels, dense, sparse) of `data` (a `DACLoader`, or any iterable of such batches of the model's batch
+        size), `predict` and one `Evaluator.add`; one synchronisation, at the end.  Appends the accuracy
+        (correct / total) to `record` and returns `Evaluator.result()`: dict(total, correct, accuracy, logloss,
+        auc, positives, negatives).  evaluator: an `Evaluator` to use (reset first; its state holds this pass
+        afterwards); probs: a list that receives every batch's probabilities (a device tensor each)."""
+        dev = self.tables.device
+        ev = Evaluator(dev) if evaluator is None else evaluator.reset()
+        for labels, dense, sparse in data:
+            z = self.predict(dense, sparse)
+            check_labels(labels, z)
+            p = None
+            if probs is not None:
+                p = torch.empty(z.shape[0], dtype=torch.float32, device=dev)
+                probs.append(p)
+            ev.add(z, labels, prob=p)
+        res = ev.result()
+        if record is not None:
+            record.append(res["accuracy"])
+        return res
+
     def head(self, z, labels):
         """dlrm_bce_head on the top MLP's logits: prob, loss, dLoss/dlogit (self._dz) and the last
         layer's bias gradient, one launch."""
         B = z.shape[0]
         check_labels(labels, z)
-        if self.prob is None or self.prob.shape[0] != B:
+        # (keyed on _dz, the head's own buffer: `forward` rebinds prob to its result, which the head must not reuse)
+        if self._dz is None or self._dz.shape[0] != B:
             self.prob = torch.empty(B, dtype=torch.float32, device=z.device)
             self.loss = torch.empty((), dtype=torch.float32, device=z.device)
             self._dz = torch.empty((B, 1), dtype=torch.float32, device=z.device)
+            self._head_prob = self.prob
+        self.prob = self._head_prob
         ctx = self.top._ctx()
         ctx.check(ctx.lib.dlrm_bce_head(ctx.bind(), B, ptr(z), z.stride(0), ptr(labels), ptr(self.prob),
                                         ptr(self._dz), ptr(self.loss), ptr(self.top.gb[-1])))

@@ -51,6 +51,9 @@ rounded inside the backward, only the repeated rows' dt rows are written, and `p
 they do for Descent.  The backward and the apply of a step read the same value of the optimizer's step word, which
 advances by one after the apply; every row ends up bit for bit what the operator path gives from the same step.
 Opt-in, a keyword of its own: without it the rule keeps the operator path.
+
+`infer(x, idx)` is the inference forward (evaluation, `DLRMModel.predict`): lookup + interaction into `out` with no
+indexer build and no change to what a training step left or a pipelined one prepared.
 """
 import torch
 
@@ -106,6 +109,7 @@ class HotPath:
         self.materialize_ys = bool(materialize_ys)
         self.ys = torch.empty((self.B, self.F * self.D), dtype=dt, device=dev) if self.materialize_ys else None
         self._fwd_x = self._fwd_idx = None
+        self._infer_ys = None  # `infer`'s own ys, allocated by its first call on a shape without the fused kernel
         self.out = torch.empty((self.B, self.width), dtype=dt, device=dev)
         self.dx = torch.empty((self.B, self.d), dtype=torch.float32, device=dev)
         self.dt = torch.empty((self.B, self.F * self.d), dtype=torch.float32, device=dev)
@@ -402,6 +406,28 @@ class HotPath:
         else:
             self.lookup(idx)
             self.interact_fwd(x)
+        return self.out
+
+    def infer(self, x, idx):
+        """The inference forward: lookup + interaction into `out`, and nothing else.  It builds no indexer
+        and leaves `_fwd_x` / `_fwd_idx`, `_cur` / `_ix_of`, `ys` and the optimizer's state alone, so it can run
+        between two training steps, pipelined ones included (`forward` is the training forward: on the step
+        kernels it rebuilds the current indexer).  One launch (dlrm_lookup_interact_fwd without ys); a shape
+        without the fused kernel takes dlrm_maplookup + dlrm_interact_fwd through a ys of its own."""
+        h = self.ctx.bind()
+        if self._infer_ys is None:
+            rc = self.lib.dlrm_lookup_interact_fwd(h, self.ts.handle, ptr(idx.data), idx.itype, idx.stride,
+                                                   self.index_base, self.B, self.L, ptr(x), x.stride(0), None, 0,
+                                                   ptr(self.out), self.out.stride(0), self.padding)
+            if rc != _lib.E_UNSUPPORTED:
+                self._check(rc)
+                return self.out
+            self._infer_ys = torch.empty((self.B, self.F * self.D), dtype=self.ts.dtype, device=self.ts.device)
+        ys = self._infer_ys
+        self._check(self.lib.dlrm_maplookup(h, self.ts.handle, ptr(idx.data), idx.itype, idx.stride, self.index_base,
+                                            self.B, self.L, ptr(ys), ys.stride(0), self.d))
+        self._check(self.lib.dlrm_interact_fwd(h, self.dcode, self.d, self.F, self.B, ptr(x), x.stride(0), ptr(ys),
+                                               ys.stride(0), ptr(self.out), self.out.stride(0), self.padding))
         return self.out
 
     def backward(self, idx, dout):

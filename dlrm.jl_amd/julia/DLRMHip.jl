@@ -1132,4 +1132,100 @@ function Base.iterate(l::HipDACLoader, i = 1)
     return (; labels = l.labels, dense = l.dense, sparse = PackedIndices(l.sparse, B, 1)), i + 1
 end
 
+#####
+##### Evaluation: `test(model, data; record, strategy)` (src/train/utils.jl:31-46) with device-resident counters
+#####
+
+"""
+    HipEval(ctx)
+
+The state of one evaluation pass (dlrm_eval_accumulate, include/dlrm_hip.h): counters and a per-class
+histogram of the predictions' upper float bits, `words` 8-byte words in HBM, zeroed.  `evaluate!` folds a
+batch in (one launch, no synchronisation), `results` reads it: accuracy as the reference's `test` counts it
+(`round.(predictions) .== labels`), log loss and the AUC of the predictions truncated to 10 mantissa bits.
+"""
+mutable struct HipEval
+    ctx::Context
+    bins::Int
+    shift::Int
+    state::DeviceMatrix{Int64}
+    scores::Union{Nothing,DeviceMatrix{Float32}}   # upload scratch of the last batch size
+    labels::Union{Nothing,DeviceMatrix{Float32}}
+end
+function HipEval(ctx::Context)
+    bins, shift, words = Ref{Cint}(0), Ref{Cint}(0), Ref{Int64}(0)
+    check(ctx, ccall((:dlrm_eval_layout, libdlrm), Cint, (Ref{Cint}, Ref{Cint}, Ref{Int64}), bins, shift, words))
+    ev = HipEval(ctx, Int(bins[]), Int(shift[]), DeviceMatrix{Int64}(ctx, words[], 1), nothing, nothing)
+    return reset!(ev)
+end
+
+function reset!(ev::HipEval)
+    upload!(ev.state, zeros(Int64, size(ev.state)))
+    return ev
+end
+
+_on_device(ev::HipEval, v::DeviceMatrix{Float32}, slot::Symbol) = v
+function _on_device(ev::HipEval, v::AbstractArray, slot::Symbol)
+    host = reshape(convert(Array{Float32}, v), 1, :)
+    buf = getfield(ev, slot)
+    if buf === nothing || size(buf) != size(host)
+        buf = DeviceMatrix{Float32}(ev.ctx, 1, length(host))
+        setfield!(ev, slot, buf)
+    end
+    return upload!(buf, host)
+end
+
+"""
+    evaluate!(ev, predictions, labels; is_prob = true)
+
+Folds one batch into `ev`: `predictions` (the model's output, probabilities; `is_prob = false` for logits)
+and `labels`, host arrays (uploaded) or `DeviceMatrix{Float32}` of 1 × B.
+"""
+function evaluate!(ev::HipEval, predictions, labels; is_prob::Bool = true)
+    p, y = _on_device(ev, predictions, :scores), _on_device(ev, labels, :labels)
+    B = length(p)
+    length(y) == B || throw(DimensionMismatch("$B predictions, $(length(y)) labels"))
+    check(ev.ctx, ccall((:dlrm_eval_accumulate, libdlrm), Cint,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}),
+                        ev.ctx.ptr, ev.state.ptr, B, p.ptr, 1, is_prob ? 1 : 0, y.ptr, C_NULL))
+    return ev
+end
+
+"""
+    results(ev) -> (; total, correct, accuracy, logloss, auc, positives, negatives)
+
+Copies the state to the host (synchronises).  `auc` counts a (negative, positive) pair whose predictions
+share a bin half; `NaN` without both classes.
+"""
+function results(ev::HipEval)
+    w = vec(Array(ev.state))
+    total, correct, P, N = Int(w[1]), Int(w[2]), Int(w[3]), Int(w[4])
+    loss_sum = reinterpret(Float64, w[6])
+    neg, pos = view(w, 9:(8 + ev.bins)), view(w, (9 + ev.bins):(8 + 2 * ev.bins))
+    num2, above = BigInt(0), BigInt(0)
+    for k in ev.bins:-1:1
+        neg[k] == 0 || (num2 += neg[k] * (2 * above + pos[k]))
+        above += pos[k]
+    end
+    auc = P * N == 0 ? NaN : Float64(num2 / (2 * BigInt(P) * N))
+    return (; total, correct, accuracy = correct / total, logloss = loss_sum / total, auc, positives = P, negatives = N)
+end
+
+"""
+    test(model, data, ev::HipEval; record = Float32[], strategy)
+
+The reference's `test` loop with the counting on the device: pushes `correct / total` onto `record` and
+returns `results(ev)`.
+"""
+function test(model, data, ev::HipEval; record = Float32[], strategy)
+    reset!(ev)
+    for d in data
+        labels, dense, sparse = d
+        evaluate!(ev, model(dense, sparse; strategy), labels)
+    end
+    r = results(ev)
+    push!(record, r.accuracy)
+    return r
+end
+
 end # module

@@ -44,6 +44,9 @@ tables through `HipTables` (`ts`, indexing, iteration) run a pending update and 
 Anything else that reads ys gets it materialized (`LazyLookup.materialize`).  `out`, `dx` and the
 gradient live in per-batch-size buffers reused by the next step, as the reference's own
 preallocated scratch (`DotInteraction`'s per-thread scratchpads) is.
+
+Evaluation between steps: `HipTables.infer(x, sparse)` runs a pending update first (`flush()`), then the
+inference forward (`HotPath.infer`), so it sees every applied update and leaves the step state alone.
 """
 from . import _lib
 from .embedding import EmbeddingTableSet, PackedIndices, PreallocationStrategy, as_table_set
@@ -139,6 +142,16 @@ class HipTables:
         else:
             hp.step_bwd(lz.delta, x=lz.x, idx=lz.idx, flags=_lib.STEP_APPLY_ONLY)
         self._pending = None  # (only once the apply launch was queued: a failed call keeps it pending)
+
+    def infer(self, x, sparse):
+        """The evaluation forward over these tables: `HotPath.infer` (lookup + interaction, no indexer, nothing of a
+        step touched) after `flush()`, so a deferred update!'s apply launch has run and the forward reads the
+        tables as the last step leaves them.  Returns the engine's `out` ([B][width], reused by the next call)."""
+        idx = PackedIndices(sparse, device=self._ts.device)
+        self.flush()
+        hp = self.hotpath(idx.B)
+        hp.validate(x, idx)
+        return hp.infer(x, idx)
 
     def check_index_base(self, index_base, op):
         """A caller-passed index base must be the tables' own (None: the tables')."""

@@ -688,6 +688,29 @@ int dlrm_relu_bwd_bias_workspace(int batch, int n, int64_t* work_floats, int64_t
 int dlrm_relu_bwd_bias(dlrm_ctx* ctx, int batch, int n, const float* y, int64_t y_ld, float* g, int64_t g_ld,
                        float* dbias, float* work, unsigned* counters);
 
+/* ---- evaluation (the reference's `test`, src/train/utils.jl:31-46, plus log loss and AUC) ----
+ * dlrm_eval_layout: *bins = 130049, *shift = 13, *words = 8 + 2·bins: the size of a state in 8-byte words.
+ * dlrm_eval_accumulate: folds one batch of scores and labels into `state`, caller-owned device memory of
+ *   `words` words, 8-B aligned.  One launch, no allocation, no synchronisation, hipGraph-capturable.  Reset is
+ *   the caller's memset to zero, reading is the caller's copy, and two states merge by integer addition of
+ *   words 0-4 and the histogram (loss_sum by a double addition).
+ *     word 0 total      1 correct      2 positives (labels == 1.0f)      3 negatives (labels == 0.0f)
+ *          4 batches (calls)      5 loss_sum (IEEE double bits)
+ *          6 the last call's mean loss (float bits in the low half)      7 zero
+ *          8 + c·bins + k   hist[c][k], u64; class c = 0 negatives, 1 positives
+ *   Per sample b < batch: p = scores[b·scores_ld] if is_prob, else 1/(1 + exp(-scores[b·scores_ld])) with
+ *   dlrm_bce_head's expression (the same bits); prob[b] = p (prob may be NULL).  The sample is correct iff
+ *   rintf(p) == labels[b] (round.(predictions) .== labels: ties to even, so p = 0.5 predicts 0; a soft label or
+ *   a NaN is never correct).  Its loss term is dlrm_bce_head's, summed over the batch in dlrm_bce_head's order
+ *   into a float L: loss_sum += (double)L, word 6 = L·(1.0f/batch).  hist[c][float_bits(min(max(p, 0), 1)) >> shift]
+ *   is incremented for a label of exactly 0 or 1 (a NaN p: bin 0): positive float bits order as their values
+ *   do, so the histogram ranks the scores truncated to 10 mantissa bits (the AUC's input).
+ *   Integer atomics only: every word is reproducible.  Calls on one stream serialise; concurrent calls on one
+ *   state from two streams are undefined.  batch >= 1, scores_ld >= 1. */
+int dlrm_eval_layout(int* bins, int* shift, int64_t* words);
+int dlrm_eval_accumulate(dlrm_ctx* ctx, int64_t* state, int batch, const float* scores, int64_t scores_ld, int is_prob,
+                         const float* labels, float* prob);
+
 /* ---- Criteo DAC data path (SURVEY §8 rows f2 + f4; criteo.jl:85-344) ----------------------
  * dlrm_dac_record: DACRecord (criteo.jl:91-95), 160 bytes, the binary file format (mmap-able).
  * dlrm_dac_parse_tsv: parseline over a buffer of TSV lines (criteo.jl:164-176): label Int32,
