@@ -730,7 +730,7 @@ int dlrm_interact_bwd_gather(dlrm_ctx* ctx, const dlrm_tables* tb, dlrm_indexer*
     if (ix) begin_build(ix, plan);
     rc = launch_interact_bwd_gather(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
                                     index_base, lookups, d, batch, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld,
-                                    ix ? &ix->dev : nullptr, tb->h_desc.data());
+                                    ix ? &ix->dev : nullptr);
     if (rc || !ix) return rc;
     // as dlrm_indexer_build: a following update may pass DLRM_UPDATE_PREBUILT
     record_build(ix, plan, IndexArgs{indices, itype, table_stride, index_base, batch, lookups});
@@ -752,7 +752,7 @@ int dlrm_interact_bwd_blocked(dlrm_ctx* ctx, const dlrm_tables* tb, const void* 
               "dlrm_interact_bwd_blocked: null buffer");
     return launch_interact_bwd_blocked(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
                                        index_base, 1, d, batch, x, x_ld, dout, dout_ld, dx, dx_ld, dst, dst_base,
-                                       dst_ld, tb->h_desc.data());
+                                       dst_ld);
 }
 
 // --------------------------------------------------------------------------- indexer
@@ -1256,19 +1256,15 @@ int dlrm_step_fwd(dlrm_ctx* ctx, const dlrm_tables* tb, dlrm_indexer* ix, const 
                                           tb->h_desc.data());
     };
     BuildCaps caps{};
-    caps.prepared = ix->prepared && built_from(ix, indices, itype, table_stride, index_base, batch, 1);
+    // (a prepared build is kept where the fused forward can gather from it: otherwise the batch is built as any other)
+    caps.prepared = ix->prepared && built_from(ix, indices, itype, table_stride, index_base, batch, 1) &&
+                    lookup_fwd_supported(tb->aligned16, tb->T, tb->dtype, d, batch, x, x_ld, tb->h_desc.data());
     caps.step_fwd = step_fwd_supported(tb->aligned16, tb->T, tb->dtype, d, batch, x, x_ld, tb->h_desc.data());
     caps.step_split = step_split_supported(tb->aligned16, tb->T, tb->dtype, d, x, x_ld);
-    BuildPlan p = plan_build(BuildSite::StepFwd, shape_of(ix), batch, knobs(), caps);
+    const BuildPlan p = plan_build(BuildSite::StepFwd, shape_of(ix), batch, knobs(), caps);
     begin_build(ix, p);
-    if (p.form == BuildForm::Kept) {
-        // built by the previous step's apply launch (dlrm_step_bwd_prepare) or by dlrm_indexer_prepare: the gather alone
-        rc = fused_fwd();
-        if (rc != DLRM_E_UNSUPPORTED) return rc;
-        caps.prepared = false;  // (no fused forward for this x: the batch is built as any other)
-        p = plan_build(BuildSite::StepFwd, shape_of(ix), batch, knobs(), caps);
-        begin_build(ix, p);
-    }
+    // built by the previous step's apply launch (dlrm_step_bwd_prepare) or by dlrm_indexer_prepare: the gather alone
+    if (p.form == BuildForm::Kept) return fused_fwd();
     if (p.form == BuildForm::InForward) {
         rc = launch_step_fwd(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride, index_base, d,
                              batch, x, x_ld, out, out_ld, padding, ix->dev, tb->h_desc.data());
@@ -1310,8 +1306,7 @@ int dlrm_step_fwd(dlrm_ctx* ctx, const dlrm_tables* tb, dlrm_indexer* ix, const 
 // rule's second stream in 16-B aligned rows (the split rule's backward loads the low halves as 8-B or 16-B vectors,
 // the element-wise Adagrad rule's its state rows as 16-B vectors), and the rule's once-hit write for the feature sizes
 static bool has_split_bwd(const dlrm_tables* tb, const BoundRule& r, const void* x, int64_t x_ld) {
-    return step_split_supported(tb->aligned16, tb->T, tb->dtype, tb->D, x, x_ld) && r.aligned16 &&
-           step_bwd_supported(r.kind, tb->dtype, tb->T, tb->D);
+    return r.aligned16 && step_bwd_supported(r.kind, tb->aligned16, tb->T, tb->dtype, tb->D, x, x_ld);
 }
 
 static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const BoundRule& r, const void* indices,
@@ -1358,7 +1353,7 @@ static int step_bwd_impl(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_indexer* ix, const
         }
     } else {
         rc = launch_interact_bwd_gather(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
-                                        index_base, 1, d, batch, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, nullptr, tb->h_desc.data());
+                                        index_base, 1, d, batch, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, nullptr);
     }
     if (rc || (flags & DLRM_STEP_BWD_ONLY)) return rc;
     // once-hit rows: updated by the split backward, else by this apply (an unsplit indexer lists

@@ -23,6 +23,10 @@ namespace dlrm {
 constexpr int kFastMaxN = 4096;     // in-LDS indexer (indexer.hpp): positions per table
 constexpr int kHixMaxN = 1 << 20;   // hash indexer (hashindex.hip): positions per table
 constexpr int kStepIndexMaxN = 2048;  // the forward-launch indexer (interact.hip): positions per table
+constexpr int kArgTables = 32;  // table pointers that travel by value in a forward kernel's arguments (common.hpp TabPtrs)
+// The optimizer rules of the update and of the training step (common.hpp BoundRule; interact_plan.hpp: the step
+// backward's forms per rule)
+enum { kRuleDescent = 0, kRuleSplit, kRuleAdagrad, kRuleRowwise, kRuleStochastic, kNumRules };
 // the wave build (indexer.hpp wave_build_group) of the next batch (in the apply launch) or of a
 // prepared batch (dlrm_indexer_prepare), and the bag build's per-part sort: up to kWaveMaxN
 // positions per table, as 16 parts per 2048 positions (2^wave_vshift(N) parts per table; a part

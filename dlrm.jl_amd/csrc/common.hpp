@@ -16,8 +16,7 @@ struct __attribute__((aligned(16))) TableDesc {
     int64_t nrows;
 };
 
-// Up to kArgTables table pointers travel by value in a forward kernel's arguments (TabPtrs).
-constexpr int kArgTables = 32;
+// (kArgTables, the table pointers a forward kernel takes by value as TabPtrs: build_plan.hpp)
 
 // Device-side error word: bit 0 = an out-of-range index was skipped.
 constexpr unsigned kErrIndex = 1u;
@@ -321,7 +320,7 @@ const Knobs& knobs();
 
 // The optimizer rules of the update and of the training step.  abi.cpp's kRules describes each one on the host
 // (names, table types, launches); apply.hpp holds their arithmetic, interact.hip the step backward's once-hit write.
-enum { kRuleDescent = 0, kRuleSplit, kRuleAdagrad, kRuleRowwise, kRuleStochastic, kNumRules };
+// (the kRule* constants: build_plan.hpp)
 // A rule bound to one call: what the public entry points make of their optimizer handle and scalars, and all that
 // the launchers below take of a rule.
 struct BoundRule {
@@ -344,27 +343,29 @@ int launch_interact_fwd(dlrm_ctx* ctx, int dtype, int d, int F, int B, const voi
 int launch_lookup_interact_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, int T, int dtype,
                                const void* idx, int itype, int64_t tstride, int base, int L, int d, int B,
                                const void* x, int64_t x_ld, void* ys, int64_t ys_ld, void* out, int64_t out_ld,
-                               int padding,
-    const TableDesc* htabs = nullptr);
+                               int padding, const TableDesc* htabs = nullptr);
 int launch_interact_bwd_gather(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, int T, int dtype,
                                const void* idx, int itype, int64_t tstride, int base, int L, int d, int B,
                                const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, float* dx,
-                               int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev* ix,
-    const TableDesc* htabs = nullptr);
+                               int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev* ix);
 int launch_interact_bwd_blocked(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, int T, int dtype,
                                 const void* idx, int itype, int64_t tstride, int base, int L, int d, int B,
                                 const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, float* dx,
-                                int64_t dx_ld, float* dst, const int64_t* dbase, const int64_t* dld,
-    const TableDesc* htabs = nullptr);
+                                int64_t dx_ld, float* dst, const int64_t* dbase, const int64_t* dld);
 int launch_step_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, int T, int dtype, const void* idx,
                     int itype, int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, void* out,
-                    int64_t out_ld, int padding, const IndexerDev& ix,
-    const TableDesc* htabs = nullptr);
+                    int64_t out_ld, int padding, const IndexerDev& ix, const TableDesc* htabs = nullptr);
 int launch_interact_bwd(dlrm_ctx* ctx, int dtype, int d, int F, int B, const void* dout, int64_t dout_ld,
                         const void* t, int64_t t_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld);
 int64_t hix_table_slots(int64_t cap);
 int launch_hix_build(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* tabs, int T, const void* idx, int itype,
                      int64_t tstride, int base, int N, bool split, unsigned* err, hipStream_t stream = nullptr);
+// Whether a shape has a kernel, asked before a build is planned: each is the return code of the launcher's own plan
+// (interact_plan.hpp plan_interact).  lookup_fwd_supported: launch_lookup_interact_fwd of
+// one-hot indices without ys; step_fwd_supported: launch_step_fwd; step_split_supported: the step backward takes a
+// split indexer (Descent's launch_step_bwd has a kernel).
+bool lookup_fwd_supported(bool tabs_aligned16, int T, int dtype, int d, int B, const void* x, int64_t x_ld,
+                          const TableDesc* htabs);
 bool step_split_supported(bool tabs_aligned16, int T, int dtype, int d, const void* x, int64_t x_ld);
 bool step_fwd_supported(bool tabs_aligned16, int T, int dtype, int d, int B, const void* x, int64_t x_ld,
                         const TableDesc* htabs);
@@ -419,11 +420,12 @@ ApplyFn launch_split_step_apply, launch_adagrad_step_apply, launch_rowwise_adagr
 int launch_sr_step_set(dlrm_ctx* ctx, uint64_t* step, uint64_t value);
 int launch_sr_step_advance(dlrm_ctx* ctx, uint64_t* step);  // step += 1
 // The training step's backward under a rule (interact.hip).  step_bwd_supported: whether the split backward has the
-// rule's once-hit write for this shape (among step_split_supported's; Descent and the split rule: all of them).
+// rule's once-hit write for this shape: step_split_supported's shapes, and of them all for Descent and the split rule
+// (which forms the others have: DESIGN.md section 22).
 // launch_step_bwd: that backward -- once-hit rows stepped in place with the rule, dt rows of the others written for
 // the apply; the caller checked the shape, the 16-B alignment of dx / dt and of the rule's second stream, and bf16
 // tables for the rules that need them.  The stochastic rule's reads the step word and does not advance it.
-bool step_bwd_supported(int kind, int dtype, int T, int d);
+bool step_bwd_supported(int kind, bool tabs_aligned16, int T, int dtype, int d, const void* x, int64_t x_ld);
 int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T, int dtype, const void* idx, int itype,
                     int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
                     int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "interact_plan.hpp"
 
 #ifdef DLRM_PHASE
 // Phase timestamps of the split indexer inside the step forward's launch (table DLRM_PHASE);
@@ -1472,6 +1473,11 @@ __global__ __launch_bounds__(256) void interact_bwd_scalar(int d, int F, int B, 
 }
 
 // ------------------------------------------------------------------------ launchers
+// Every launcher is interact_align -> plan_interact (interact_plan.hpp; DESIGN.md section 22 has the table) -> launch:
+// the plan picks the kernel and its template arguments, with_elem / with_int turn them into types, and the grid and
+// the dynamic LDS are sized here, beside the device types they come from.
+static_assert(256 * kBwdIndexEPL == kBwdIndexMaxN, "interact_bwd_index_kernel's indexer and the plan's bound");
+
 static unsigned grid_for(int64_t items, int per_block, int cus) {
     int64_t g = (items + per_block - 1) / per_block;
     const int64_t cap = (int64_t)cus * 16;
@@ -1479,8 +1485,25 @@ static unsigned grid_for(int64_t items, int per_block, int cus) {
     return (unsigned)(g < 1 ? 1 : g);
 }
 
-// samples per 4-wave workgroup of the one-hot forward (fwd_body: one wave per sample)
-static int fwd_samples_per_block(int, int) { return 4; }
+// Run-time value -> compile-time: f(T{}) with the plan's element type; f(std::integral_constant<int, V>) with the V
+// of Vs that n equals (false: none)
+template <typename F> static void with_elem(bool f32, F&& f) { f32 ? f(float{}) : f(uint16_t{}); }
+template <int... Vs, typename F> static bool with_int(int n, F&& f) {
+    return ((n == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// The plan of a site (F = T_ + 1 features; the sites without tables pass tabs16 = true); htabs: the tables' host
+// descriptors where the site may take their pointers by value
+static InteractPlan plan_site(InteractSite site, bool tabs16, int T_, int dtype, int d, int B, int L, const void* x,
+                              int64_t x_ld, const void* t = nullptr, int64_t t_ld = 0, const float* dx = nullptr,
+                              int64_t dx_ld = 0, const float* dt = nullptr, int64_t dt_ld = 0,
+                              const TableDesc* htabs = nullptr, int rule = kRuleDescent) {
+    int64_t rows = htabs ? 0 : -1;
+    for (int k = 0; htabs && k < T_; ++k) rows = htabs[k].nrows > rows ? htabs[k].nrows : rows;
+    return plan_interact(site, InteractShape{dtype, d, T_ + 1, B, L, t != nullptr},
+                         interact_align(dtype, d, x, x_ld, t, t_ld, dx, dx_ld, dt, dt_ld, tabs16, T_, rows), knobs(), rule);
+}
+
 // The tracing build holds the d = 128 forward at the shipped two workgroups per CU with unused
 // dynamic LDS (16 KB static + 40 KB: two fit in 160 KB): the stamps change the kernel's register
 // count, and a third workgroup would change the timeline they are there to show.
@@ -1490,64 +1513,41 @@ constexpr size_t kFwdTraceLds = 40 * 1024;
 constexpr size_t kFwdTraceLds = 0;
 #endif
 
-template <typename T, int NB, bool FUSED>
-static void launch_fwd_nb(hipStream_t s, int cus, int d, int F, int B, const void* x, int64_t x_ld, void* ys,
-                          int64_t ys_ld, void* out, int64_t out_ld, int padding, const GatherArgs& ga,
-                          const TabPtrs& tp) {
-    const bool pooled = FUSED && ga.L > 1;
-    const unsigned g = grid_for(B, pooled ? 4 : fwd_samples_per_block(d, NB), cus);
-    if (FUSED && ga.L > 1)
-        hipLaunchKernelGGL((interact_fwd_kernel<T, NB, FUSED, true>), dim3(g), dim3(256), 0, s, d, F, B, (const T*)x,
-                           x_ld, (T*)ys, ys_ld, (T*)out, out_ld, padding, ga, tp);
-    else if (d == 128)  // the BASELINE feature size, compiled for it
-        hipLaunchKernelGGL((interact_fwd_kernel<T, NB, FUSED, false, 128>), dim3(g), dim3(256), kFwdTraceLds, s, d, F, B,
-                           (const T*)x, x_ld, (T*)ys, ys_ld, (T*)out, out_ld, padding, ga, tp);
-    else
-        hipLaunchKernelGGL((interact_fwd_kernel<T, NB, FUSED, false>), dim3(g), dim3(256), 0, s, d, F, B, (const T*)x,
-                           x_ld, (T*)ys, ys_ld, (T*)out, out_ld, padding, ga, tp);
-}
-
-template <typename T, bool FUSED>
-static bool dispatch_fwd(int NB, hipStream_t s, int cus, int d, int F, int B, const void* x, int64_t x_ld, void* ys,
-                         int64_t ys_ld, void* out, int64_t out_ld, int padding, const GatherArgs& ga,
-                         const TabPtrs& tp = TabPtrs{}) {
-    switch (NB) {
-#define DLRM_CASE(N) \
-    case N: launch_fwd_nb<T, N, FUSED>(s, cus, d, F, B, x, x_ld, ys, ys_ld, out, out_ld, padding, ga, tp); return true;
-        DLRM_CASE(1) DLRM_CASE(2) DLRM_CASE(3) DLRM_CASE(4) DLRM_CASE(5) DLRM_CASE(6)
-#undef DLRM_CASE
-        default: return false;
-    }
-}
-
-static bool fwd_aligned(int dtype, int d, const void* x, int64_t x_ld, const void* ys, int64_t ys_ld) {
-    const int vec = dtype == DLRM_F32 ? 4 : 8;  // elements per 16-B fragment load
-    return (uintptr_t)x % 16 == 0 && (uintptr_t)ys % 16 == 0 && (x_ld % vec) == 0 && (ys_ld % vec) == 0 &&
-           (d % vec) == 0;
+// interact_fwd_kernel (one wave per sample, 4 samples per workgroup) as the plan has it
+template <bool FUSED>
+static void launch_fwd(const InteractPlan& p, hipStream_t s, int cus, int d, int F, int B, const void* x, int64_t x_ld,
+                       void* ys, int64_t ys_ld, void* out, int64_t out_ld, int padding, const GatherArgs& ga,
+                       const TabPtrs& tp) {
+    with_elem(p.f32, [&](auto e) {
+        typedef decltype(e) T;
+        const auto go = [&](auto kernel, size_t lds) {
+            hipLaunchKernelGGL(kernel, dim3(grid_for(B, 4, cus)), dim3(256), lds, s, d, F, B, (const T*)x, x_ld, (T*)ys,
+                               ys_ld, (T*)out, out_ld, padding, ga, tp);
+        };
+        with_int<1, 2, 3, 4, 5, 6>(p.NB, [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            if (FUSED && p.pooled) go(interact_fwd_kernel<T, NB, FUSED, true>, 0);
+            else if (p.DC == 128) go(interact_fwd_kernel<T, NB, FUSED, false, 128>, kFwdTraceLds);
+            else go(interact_fwd_kernel<T, NB, FUSED, false>, 0);
+        });
+    });
 }
 
 int launch_interact_fwd(dlrm_ctx* ctx, int dtype, int d, int F, int B, const void* x, int64_t x_ld, void* ys,
                         int64_t ys_ld, void* out, int64_t out_ld, int padding) {
-    if (B == 0) return DLRM_OK;
+    const InteractPlan p = plan_site(InteractSite::Fwd, true, F - 1, dtype, d, B, 1, x, x_ld, ys, ys_ld);
+    if (p.kernel == InteractKernel::None) return p.rc;
     hipStream_t s = ctx_stream(ctx);
     const int cus = ctx_num_cus(ctx);
-    const int NB = (F + 15) / 16;
-    GatherArgs ga{};
-    bool done = false;
-    if (fwd_aligned(dtype, d, x, x_ld, ys, ys_ld))
-        done = dtype == DLRM_F32
-                   ? dispatch_fwd<float, false>(NB, s, cus, d, F, B, x, x_ld, ys, ys_ld, out, out_ld, padding, ga)
-                   : dispatch_fwd<uint16_t, false>(NB, s, cus, d, F, B, x, x_ld, ys, ys_ld, out, out_ld, padding, ga);
-    if (!done) {  // NB > 6 would exceed 256 VGPRs; odd alignments
-        const int W = d + F * (F - 1) / 2 + padding;
-        const unsigned g = grid_for((int64_t)B * W, 256, cus);
-        if (dtype == DLRM_F32)
-            hipLaunchKernelGGL(interact_fwd_scalar<float>, dim3(g), dim3(256), 0, s, d, F, B, (const float*)x, x_ld,
-                               (float*)ys, ys_ld, (float*)out, out_ld, padding);
-        else
-            hipLaunchKernelGGL(interact_fwd_scalar<uint16_t>, dim3(g), dim3(256), 0, s, d, F, B, (const uint16_t*)x,
-                               x_ld, (uint16_t*)ys, ys_ld, (uint16_t*)out, out_ld, padding);
-    }
+    if (p.kernel == InteractKernel::Fwd)
+        launch_fwd<false>(p, s, cus, d, F, B, x, x_ld, ys, ys_ld, out, out_ld, padding, GatherArgs{}, TabPtrs{});
+    else
+        with_elem(p.f32, [&](auto e) {
+            typedef decltype(e) T;
+            const unsigned g = grid_for((int64_t)B * (d + F * (F - 1) / 2 + padding), 256, cus);
+            hipLaunchKernelGGL(interact_fwd_scalar<T>, dim3(g), dim3(256), 0, s, d, F, B, (const T*)x, x_ld, (T*)ys, ys_ld,
+                               (T*)out, out_ld, padding);
+        });
     return ctx_hip(ctx, hipGetLastError(), "interact_fwd launch");
 }
 
@@ -1557,160 +1557,118 @@ int launch_interact_fwd(dlrm_ctx* ctx, int dtype, int d, int F, int B, const voi
 int launch_lookup_interact_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, int T_, int dtype,
                                const void* idx, int itype, int64_t tstride, int base, int L, int d, int B,
                                const void* x, int64_t x_ld, void* ys, int64_t ys_ld, void* out, int64_t out_ld,
-                               int padding,
-                    const TableDesc* htabs) {
-    if (B == 0) return DLRM_OK;
-    const int F = T_ + 1;
-    const int NB = (F + 15) / 16;
-    if (T_ == 0 || !tabs_aligned16 || !fwd_aligned(dtype, d, x, x_ld, ys, ys_ld) || NB > 6) return DLRM_E_UNSUPPORTED;
-    // Pooled bags with ys kept: the many-wave pooled gather (maplookup) + the interaction on ys
-    // beat one wave gathering T*L rows per sample (measured 489 vs 701 us at 64 x 256, L = 10);
-    // the caller's two-launch fallback gives the same bits.
-    if (L > 1 && ys && (int64_t)T_ * L > 64) return DLRM_E_UNSUPPORTED;
-    hipStream_t s = ctx_stream(ctx);
-    const int cus = ctx_num_cus(ctx);
+                               int padding, const TableDesc* htabs) {
+    const InteractPlan p = plan_site(InteractSite::LookupFwd, tabs_aligned16, T_, dtype, d, B, L, x, x_ld, ys, ys_ld,
+                                     nullptr, 0, nullptr, 0, htabs);
+    if (p.kernel == InteractKernel::None) return p.rc;
     GatherArgs ga{tabs, idx, itype, tstride, base, L, ctx_error_word(ctx)};
     TabPtrs tp{};
-    if (L == 1 && NB <= 2 && !fill_tab_ptrs(tp, htabs, T_)) return DLRM_E_UNSUPPORTED;  // (the two-launch form)
-    const bool ok = dtype == DLRM_F32
-                        ? dispatch_fwd<float, true>(NB, s, cus, d, F, B, x, x_ld, ys, ys_ld, out, out_ld, padding, ga, tp)
-                        : dispatch_fwd<uint16_t, true>(NB, s, cus, d, F, B, x, x_ld, ys, ys_ld, out, out_ld, padding, ga, tp);
-    if (!ok) return DLRM_E_UNSUPPORTED;
+    if (p.tab_ptrs) fill_tab_ptrs(tp, htabs, T_);
+    launch_fwd<true>(p, ctx_stream(ctx), ctx_num_cus(ctx), d, T_ + 1, B, x, x_ld, ys, ys_ld, out, out_ld, padding, ga, tp);
     return ctx_hip(ctx, hipGetLastError(), "lookup_interact_fwd launch");
 }
 
-template <typename T, int NB, bool GATHER>
-static void launch_bwd_nb(hipStream_t s, int cus, int d, int F, int B, const void* dout, int64_t dout_ld,
-                          const void* t, int64_t t_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
-                          const GatherArgs& ga, const void* x, int64_t x_ld) {
-    typedef BwdGeom<NB> G;
-    const unsigned g = grid_for(B, G::WPB, cus);
-    const size_t lds = sizeof(float) * G::LDS_FLOATS * G::WPB + (GATHER ? (sizeof(TableDesc) + 16) * (F - 1) : 0);
-    hipLaunchKernelGGL((interact_bwd_kernel<T, NB, GATHER>), dim3(g), dim3(64 * G::WPB), lds, s, d, F, B,
-                       (const T*)dout, dout_ld, (const T*)t, t_ld, dx, dx_ld, dt, dt_ld, ga, (const T*)x, x_ld);
+// What the backward kernels share (t: a materialized ys, else x and ga's table rows)
+struct BwdArgs {
+    int d, F, B;
+    const void* dout;
+    int64_t dout_ld;
+    const void* t;
+    int64_t t_ld;
+    float *dx, *dt;
+    int64_t dx_ld, dt_ld;
+    GatherArgs ga;
+    const void* x;
+    int64_t x_ld;
+};
+
+// interact_bwd_split_kernel: SPB samples per workgroup, WPS waves per sample, no dynamic LDS
+template <typename T, int NB, int DC, int SPB, int WPS, bool MAPPED, int CPL, bool YS, typename SU>
+static void launch_split(hipStream_t s, const BwdArgs& a, const SU& su) {
+    hipLaunchKernelGGL((interact_bwd_split_kernel<T, NB, DC, SPB, WPS, MAPPED, CPL, YS, SU>),
+                       dim3((unsigned)((a.B + SPB - 1) / SPB)), dim3(64 * WPS * SPB), 0, s, a.d, a.F, a.B, (const T*)a.dout,
+                       a.dout_ld, a.dx, a.dx_ld, a.dt, a.dt_ld, a.ga, (const T*)(YS ? a.t : a.x), YS ? a.t_ld : a.x_ld, su);
 }
 
-template <typename T, bool GATHER>
-static void dispatch_bwd(int NB, hipStream_t s, int cus, int d, int F, int B, const void* dout, int64_t dout_ld,
-                         const void* t, int64_t t_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
-                         const GatherArgs& ga, const void* x, int64_t x_ld) {
-    switch (NB) {
-#define DLRM_CASE(N)                                                                                               \
-    case N:                                                                                                        \
-        launch_bwd_nb<T, N, GATHER>(s, cus, d, F, B, dout, dout_ld, t, t_ld, dx, dx_ld, dt, dt_ld, ga, x, x_ld); \
-        break;
-        DLRM_CASE(1) DLRM_CASE(2) DLRM_CASE(3) DLRM_CASE(4) DLRM_CASE(5) DLRM_CASE(6) DLRM_CASE(7)
-#undef DLRM_CASE
-    }
-}
-
-// dT = S T per sample; T from `t` (materialized ys) or, GATHER, from x + the table rows.
-template <bool GATHER>
-static int run_interact_bwd(dlrm_ctx* ctx, int dtype, int d, int F, int B, const void* dout, int64_t dout_ld,
-                            const void* t, int64_t t_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
-                            const GatherArgs& ga, bool rows_aligned, const void* x, int64_t x_ld) {
-    if (B == 0) return DLRM_OK;
+// dT = S T per sample by the kernels without an update: T from a.t or, gather, from x + the table rows; mapped (the
+// blocked backward): dt is the send layout
+static int launch_bwd(dlrm_ctx* ctx, const InteractPlan& p, const BwdArgs& a, const char* what) {
+    typedef InteractKernel K;
     hipStream_t s = ctx_stream(ctx);
     const int cus = ctx_num_cus(ctx);
-    const int NB = (F + 15) / 16;
-    const int esz = dtype == DLRM_F32 ? 4 : 2;
-    const bool t_ok = GATHER ? (rows_aligned && (uintptr_t)x % (4 * esz) == 0 && (x_ld % 4) == 0)
-                             : ((uintptr_t)t % (4 * esz) == 0 && (t_ld % 4) == 0);
-    const bool aligned = d % 4 == 0 && t_ok && (uintptr_t)dx % 16 == 0 && (uintptr_t)dt % 16 == 0 && (dx_ld % 4) == 0 &&
-                         (dt_ld % 4) == 0;
-    // a materialized ys with 33..96 features (pooled bags): the split kernel's load plan, one wave
-    // per 64-column super-block (the one-wave-per-sample bwd_body kernel spills at NB = 5 and ran
-    // the pooled backward at 145 us); bit-identical (the same MFMA sums).  DLRM_BWD_YS = 0: bwd_body.
-    const bool ys_split = !knobs().bwd_ys_body;
-    const int wps = d >= 256 ? 4 : (d >= 128 ? 2 : 1);
-    if (!GATHER && ys_split && aligned && NB >= 3 && NB <= 6 && d == 64 * wps) {
-        const StepUpdate su{nullptr, 0, 0.0f, ctx_error_word(ctx)};
-#define DLRM_YS(TY, N_, W_)                                                                                         \
-    hipLaunchKernelGGL((interact_bwd_split_kernel<TY, N_, 0, 1, W_, false, 4, true>), dim3((unsigned)B),            \
-                       dim3(64 * W_), 0, s, d, F, B, (const TY*)dout, dout_ld, dx, dx_ld, dt, dt_ld, ga,           \
-                       (const TY*)t, t_ld, su)
-#define DLRM_YS_W(TY, N_) \
-    if (wps == 4) DLRM_YS(TY, N_, 4); else if (wps == 2) DLRM_YS(TY, N_, 2); else DLRM_YS(TY, N_, 1);
-#define DLRM_YS_NB(TY)                                                                            \
-    switch (NB) {                                                                                 \
-        case 3: DLRM_YS_W(TY, 3) break;                                                           \
-        case 4: DLRM_YS_W(TY, 4) break;                                                           \
-        case 5: DLRM_YS_W(TY, 5) break;                                                           \
-        default: DLRM_YS_W(TY, 6) break;                                                          \
-    }
-        if (dtype == DLRM_F32) { DLRM_YS_NB(float) } else { DLRM_YS_NB(uint16_t) }
-#undef DLRM_YS_NB
-#undef DLRM_YS_W
-#undef DLRM_YS
-        return ctx_hip(ctx, hipGetLastError(), "interact_bwd(ys, split) launch");
-    }
-    if (aligned && NB >= 1 && NB <= 7) {  // NB = 8 would need > 64 KB of dynamic LDS
-        if (dtype == DLRM_F32)
-            dispatch_bwd<float, GATHER>(NB, s, cus, d, F, B, dout, dout_ld, t, t_ld, dx, dx_ld, dt, dt_ld, ga, x, x_ld);
-        else
-            dispatch_bwd<uint16_t, GATHER>(NB, s, cus, d, F, B, dout, dout_ld, t, t_ld, dx, dx_ld, dt, dt_ld, ga, x,
-                                           x_ld);
-    } else {
-        const unsigned g = grid_for((int64_t)B * F * d, 256, cus);
-        if (dtype == DLRM_F32)
-            hipLaunchKernelGGL((interact_bwd_scalar<float, GATHER>), dim3(g), dim3(256), 0, s, d, F, B,
-                               (const float*)dout, dout_ld, (const float*)t, t_ld, dx, dx_ld, dt, dt_ld, ga,
-                               (const float*)x, x_ld);
-        else
-            hipLaunchKernelGGL((interact_bwd_scalar<uint16_t, GATHER>), dim3(g), dim3(256), 0, s, d, F, B,
-                               (const uint16_t*)dout, dout_ld, (const uint16_t*)t, t_ld, dx, dx_ld, dt, dt_ld, ga,
-                               (const uint16_t*)x, x_ld);
-    }
-    return ctx_hip(ctx, hipGetLastError(), "interact_bwd launch");
+    const StepUpdate su{nullptr, 0, 0.0f, ctx_error_word(ctx)};
+    with_elem(p.f32, [&](auto e) {
+        typedef decltype(e) T;
+        const auto go = [&](auto kernel, unsigned g, int threads, size_t lds) {
+            hipLaunchKernelGGL(kernel, dim3(g), dim3(threads), lds, s, a.d, a.F, a.B, (const T*)a.dout, a.dout_ld,
+                               (const T*)a.t, a.t_ld, a.dx, a.dx_ld, a.dt, a.dt_ld, a.ga, (const T*)a.x, a.x_ld);
+        };
+        with_int<0, 1>(p.gather, [&](auto gather) {
+            constexpr bool GATHER = decltype(gather)::value != 0;
+            if (p.kernel == K::BwdScalar)
+                go(interact_bwd_scalar<T, GATHER>, grid_for((int64_t)a.B * a.F * a.d, 256, cus), 256, 0);
+            else if (p.kernel == K::Bwd)
+                with_int<1, 2, 3, 4, 5, 6, 7>(p.NB, [&](auto nb) {
+                    typedef BwdGeom<decltype(nb)::value> G;
+                    go(interact_bwd_kernel<T, decltype(nb)::value, GATHER>, grid_for(a.B, G::WPB, cus), 64 * G::WPB,
+                       sizeof(float) * G::LDS_FLOATS * G::WPB + (GATHER ? (sizeof(TableDesc) + 16) * (a.F - 1) : 0));
+                });
+        });
+        if (p.kernel == K::BwdSplit && p.ys)
+            with_int<3, 4, 5, 6>(p.NB, [&](auto nb) {
+                with_int<1, 2, 4>(p.WPS, [&](auto w) {
+                    launch_split<T, decltype(nb)::value, 0, 1, decltype(w)::value, false, 4, true>(s, a, su);
+                });
+            });
+        else if (p.kernel == K::BwdSplit)
+            with_int<1, 2>(p.NB, [&](auto nb) {
+                if (p.DC == 128) launch_split<T, decltype(nb)::value, 128, 4, 2, true, 4, false>(s, a, su);
+                else launch_split<T, decltype(nb)::value, 0, 2, 1, true, 4, false>(s, a, su);
+            });
+    });
+    return ctx_hip(ctx, hipGetLastError(), what);
 }
 
 int launch_interact_bwd(dlrm_ctx* ctx, int dtype, int d, int F, int B, const void* dout, int64_t dout_ld,
                         const void* t, int64_t t_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld) {
-    return run_interact_bwd<false>(ctx, dtype, d, F, B, dout, dout_ld, t, t_ld, dx, dx_ld, dt, dt_ld, GatherArgs{},
-                                   true, nullptr, 0);
+    const InteractPlan p = plan_site(InteractSite::Bwd, true, F - 1, dtype, d, B, 1, nullptr, 0, t, t_ld, dx, dx_ld, dt, dt_ld);
+    if (p.kernel == InteractKernel::None) return p.rc;
+    return launch_bwd(ctx, p, BwdArgs{d, F, B, dout, dout_ld, t, t_ld, dx, dt, dx_ld, dt_ld, GatherArgs{}, nullptr, 0},
+                      p.ys ? "interact_bwd(ys, split) launch" : "interact_bwd launch");
 }
 
 int launch_interact_bwd_gather(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, int T_, int dtype,
                                const void* idx, int itype, int64_t tstride, int base, int L, int d, int B,
                                const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, float* dx,
-                               int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev* ix,
-                    const TableDesc* htabs) {
-    GatherArgs ga{tabs, idx, itype, tstride, base, L, ctx_error_word(ctx)};
+                               int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev* ix) {
+    const InteractPlan p = plan_site(ix ? InteractSite::BwdGatherIndexed : InteractSite::BwdGather, tabs_aligned16, T_, dtype,
+                                     d, B, L, x, x_ld, nullptr, 0, dx, dx_ld, dt, dt_ld);
     const int F = T_ + 1;
-    const int NB = (F + 15) / 16;
-    const int esz = dtype == DLRM_F32 ? 4 : 2;
-    if (ix && B > 0 && T_ > 0) {
-        const bool aligned = d % 4 == 0 && tabs_aligned16 && (uintptr_t)x % (4 * esz) == 0 && (x_ld % 4) == 0 &&
-                             (uintptr_t)dx % 16 == 0 && (uintptr_t)dt % 16 == 0 && (dx_ld % 4) == 0 && (dt_ld % 4) == 0;
-        if (aligned && NB <= 2 && (int64_t)B * L <= 256 * kBwdIndexEPL) {
-            hipStream_t s = ctx_stream(ctx);
-            const int cus = ctx_num_cus(ctx);
-            size_t lds = sizeof(FastLds<256, kBwdIndexEPL>);
-#define DLRM_LAUNCH_BWDIX(TY, N_)                                                                                 \
-    {                                                                                                              \
-        typedef BwdGeom<N_> G;                                                                                     \
-        const size_t blds = sizeof(float) * G::LDS_FLOATS * G::WPB + sizeof(TableDesc) * T_;                       \
-        if (blds > lds) lds = blds;                                                                                \
-        const unsigned g = grid_for(B, G::WPB, cus);                                                               \
-        hipLaunchKernelGGL((interact_bwd_index_kernel<TY, N_>), dim3(g + T_), dim3(256), lds, s, d, F, B,          \
-                           (const TY*)dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, (const TY*)x, x_ld, *ix);           \
+    const GatherArgs ga{tabs, idx, itype, tstride, base, L, ctx_error_word(ctx)};
+    if (p.kernel == InteractKernel::BwdIndex) {
+        with_elem(p.f32, [&](auto e) {
+            typedef decltype(e) T;
+            with_int<1, 2>(p.NB, [&](auto nb) {
+                typedef BwdGeom<decltype(nb)::value> G;
+                size_t lds = sizeof(FastLds<256, kBwdIndexEPL>);
+                const size_t blds = sizeof(float) * G::LDS_FLOATS * G::WPB + sizeof(TableDesc) * T_;
+                if (blds > lds) lds = blds;
+                hipLaunchKernelGGL((interact_bwd_index_kernel<T, decltype(nb)::value>),
+                                   dim3(grid_for(B, G::WPB, ctx_num_cus(ctx)) + T_), dim3(256), lds, ctx_stream(ctx), d, F, B,
+                                   (const T*)dout, dout_ld, dx, dx_ld, dt, dt_ld, ga, (const T*)x, x_ld, *ix);
+            });
+        });
+        return ctx_hip(ctx, hipGetLastError(), "interact_bwd(+indexer) launch");
     }
-            if (dtype == DLRM_F32) {
-                if (NB == 1) DLRM_LAUNCH_BWDIX(float, 1) else DLRM_LAUNCH_BWDIX(float, 2)
-            } else {
-                if (NB == 1) DLRM_LAUNCH_BWDIX(uint16_t, 1) else DLRM_LAUNCH_BWDIX(uint16_t, 2)
-            }
-#undef DLRM_LAUNCH_BWDIX
-            return ctx_hip(ctx, hipGetLastError(), "interact_bwd(+indexer) launch");
-        }
-        // no fused form for this shape: the indexer's own launch, then the backward
+    if (p.build_first) {
         const int rc = launch_indexer_build(ctx, *ix, tabs, T_, idx, itype, tstride, base, B, L,
                                             standalone_form((int64_t)B * L, ix->hsize, false), false,
                                             ctx_error_word(ctx));
         if (rc) return rc;
     }
-    return run_interact_bwd<true>(ctx, dtype, d, T_ + 1, B, dout, dout_ld, nullptr, 0, dx, dx_ld, dt, dt_ld, ga,
-                                  tabs_aligned16, x, x_ld);
+    if (p.kernel == InteractKernel::None) return p.rc;
+    return launch_bwd(ctx, p, BwdArgs{d, F, B, dout, dout_ld, nullptr, 0, dx, dt, dx_ld, dt_ld, ga, x, x_ld},
+                      "interact_bwd launch");
 }
 
 // dlrm_interact_bwd_gather with table t's dt rows written to dst + dbase[t] + b * dld[t] (the
@@ -1719,122 +1677,66 @@ int launch_interact_bwd_gather(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_a
 int launch_interact_bwd_blocked(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, int T_, int dtype,
                                 const void* idx, int itype, int64_t tstride, int base, int L, int d, int B,
                                 const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, float* dx,
-                                int64_t dx_ld, float* dst, const int64_t* dbase, const int64_t* dld,
-                    const TableDesc* htabs) {
-    if (B == 0 || T_ == 0) return DLRM_OK;
-    const int F = T_ + 1;
-    const int NB = (F + 15) / 16;
-    const int esz = dtype == DLRM_F32 ? 4 : 2;
-    const bool aligned = d % 4 == 0 && tabs_aligned16 && (uintptr_t)x % (4 * esz) == 0 && (x_ld % 4) == 0 &&
-                         (uintptr_t)dx % 16 == 0 && (uintptr_t)dst % 16 == 0 && (dx_ld % 4) == 0;
-    if (!aligned || NB > 7)
-        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "interact_bwd_blocked: 16-B aligned rows and F <= 112 needed");
-    GatherArgs ga{tabs, idx, itype, tstride, base, L, ctx_error_word(ctx), dbase, dld};
-    hipStream_t s = ctx_stream(ctx);
-    const int cus = ctx_num_cus(ctx);
-    if (L == 1 && NB <= 2 && (d == 128 || d <= 64) && fwd_aligned(dtype, d, x, x_ld, nullptr, 0)) {
-        // the step backward's kernel (two waves per sample at d = 128, one at d <= 64) with no
-        // once-hit update: every table row's gradient goes to the send layout
-        const StepUpdate su{nullptr, 0, 0.0f, ctx_error_word(ctx)};
-#define DLRM_LAUNCH_BLK(TY, N_)                                                                                    \
-    if (d == 128)                                                                                                  \
-        hipLaunchKernelGGL((interact_bwd_split_kernel<TY, N_, 128, 4, 2, true>), dim3((unsigned)((B + 3) / 4)),      \
-                           dim3(128 * 4), 0, s, d, F, B, (const TY*)dout, dout_ld, dx, dx_ld, dst, 0, ga, (const TY*)x,\
-                           x_ld, su);                                                                              \
-    else                                                                                                           \
-        hipLaunchKernelGGL((interact_bwd_split_kernel<TY, N_, 0, 2, 1, true>), dim3((unsigned)((B + 1) / 2)),        \
-                           dim3(64 * 2), 0, s, d, F, B, (const TY*)dout, dout_ld, dx, dx_ld, dst, 0, ga, (const TY*)x, \
-                           x_ld, su);
-        if (dtype == DLRM_F32) {
-            if (NB == 1) { DLRM_LAUNCH_BLK(float, 1) } else { DLRM_LAUNCH_BLK(float, 2) }
-        } else {
-            if (NB == 1) { DLRM_LAUNCH_BLK(uint16_t, 1) } else { DLRM_LAUNCH_BLK(uint16_t, 2) }
-        }
-#undef DLRM_LAUNCH_BLK
-        return ctx_hip(ctx, hipGetLastError(), "interact_bwd_blocked(split) launch");
-    }
-    if (dtype == DLRM_F32)
-        dispatch_bwd<float, true>(NB, s, cus, d, F, B, dout, dout_ld, nullptr, 0, dx, dx_ld, dst, 0, ga, x, x_ld);
-    else
-        dispatch_bwd<uint16_t, true>(NB, s, cus, d, F, B, dout, dout_ld, nullptr, 0, dx, dx_ld, dst, 0, ga, x, x_ld);
-    return ctx_hip(ctx, hipGetLastError(), "interact_bwd_blocked launch");
+                                int64_t dx_ld, float* dst, const int64_t* dbase, const int64_t* dld) {
+    const InteractPlan p = plan_site(InteractSite::BwdBlocked, tabs_aligned16, T_, dtype, d, B, L, x, x_ld, nullptr, 0, dx,
+                                     dx_ld, dst, 0);
+    if (p.rc) return ctx_fail(ctx, p.rc, "interact_bwd_blocked: 16-B aligned rows and F <= 112 needed");
+    if (p.kernel == InteractKernel::None) return DLRM_OK;
+    const GatherArgs ga{tabs, idx, itype, tstride, base, L, ctx_error_word(ctx), dbase, dld};
+    return launch_bwd(ctx, p, BwdArgs{d, T_ + 1, B, dout, dout_ld, nullptr, 0, dx, dst, dx_ld, 0, ga, x, x_ld},
+                      p.kernel == InteractKernel::BwdSplit ? "interact_bwd_blocked(split) launch"
+                                                           : "interact_bwd_blocked launch");
 }
 
-// Shapes whose backward can take a split indexer (interact_bwd_update_kernel: F <= 32, 16-B
-// aligned rows and x), whatever the batch size.
-bool step_split_supported(bool tabs_aligned16, int T_, int dtype, int d, const void* x, int64_t x_ld) {
-    const int NB = (T_ + 1 + 15) / 16;
-    return T_ > 0 && tabs_aligned16 && fwd_aligned(dtype, d, x, x_ld, nullptr, 0) && NB <= 2;
+// Whether a shape has a kernel, asked before a build is planned (build_plan.hpp BuildCaps): the launchers' own plans.
+// The step backward's take one sample: no batch size changes whether a kernel exists.
+bool lookup_fwd_supported(bool tabs_aligned16, int T_, int dtype, int d, int B, const void* x, int64_t x_ld,
+                          const TableDesc* htabs) {
+    return plan_site(InteractSite::LookupFwd, tabs_aligned16, T_, dtype, d, B, 1, x, x_ld, nullptr, 0, nullptr, 0, nullptr, 0,
+                     htabs).rc == DLRM_OK;
 }
-
-// Shapes launch_step_fwd has a kernel for: exactly its refusals, asked before the build is planned
-// (build_plan.hpp BuildCaps::step_fwd).
 bool step_fwd_supported(bool tabs_aligned16, int T_, int dtype, int d, int B, const void* x, int64_t x_ld,
                         const TableDesc* htabs) {
-    const int NB = (T_ + 1 + 15) / 16;
-    TabPtrs tp{};
-    return B != 0 && T_ != 0 && tabs_aligned16 && fwd_aligned(dtype, d, x, x_ld, nullptr, 0) && NB <= 2 &&
-           B <= kStepIndexMaxN && fill_tab_ptrs(tp, htabs, T_);
+    return plan_site(InteractSite::StepFwd, tabs_aligned16, T_, dtype, d, B, 1, x, x_ld, nullptr, 0, nullptr, 0, nullptr, 0,
+                     htabs).rc == DLRM_OK;
+}
+bool step_bwd_supported(int kind, bool tabs_aligned16, int T_, int dtype, int d, const void* x, int64_t x_ld) {
+    return plan_site(InteractSite::StepBwd, tabs_aligned16, T_, dtype, d, 1, 1, x, x_ld, nullptr, 0, nullptr, 0, nullptr, 0,
+                     nullptr, kind).kernel != InteractKernel::None;
+}
+bool step_split_supported(bool tabs_aligned16, int T_, int dtype, int d, const void* x, int64_t x_ld) {
+    return step_bwd_supported(kRuleDescent, tabs_aligned16, T_, dtype, d, x, x_ld);
 }
 
 // Training-step forward (split indexer in the same grid).  DLRM_E_UNSUPPORTED when the shape
 // has no such kernel (the caller then runs the fused forward and the indexer separately).
 int launch_step_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, int T_, int dtype, const void* idx,
                     int itype, int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, void* out,
-                    int64_t out_ld, int padding, const IndexerDev& ix,
-                    const TableDesc* htabs) {
-    const int F = T_ + 1;
-    const int NB = (F + 15) / 16;
-    if (B == 0 || T_ == 0 || !tabs_aligned16 || !fwd_aligned(dtype, d, x, x_ld, nullptr, 0) || NB > 2 ||
-        B > kStepIndexMaxN)
-        return DLRM_E_UNSUPPORTED;
-    hipStream_t s = ctx_stream(ctx);
-    const int cus = ctx_num_cus(ctx);
-    GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
+                    int64_t out_ld, int padding, const IndexerDev& ix, const TableDesc* htabs) {
+    const InteractPlan p = plan_site(InteractSite::StepFwd, tabs_aligned16, T_, dtype, d, B, 1, x, x_ld, nullptr, 0, nullptr,
+                                     0, nullptr, 0, htabs);
+    if (p.kernel == InteractKernel::None) return p.rc;
+    const GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
     TabPtrs tp{};
-    if (!fill_tab_ptrs(tp, htabs, T_)) return DLRM_E_UNSUPPORTED;
+    fill_tab_ptrs(tp, htabs, T_);
     const bool wave = ix.vshift >= 2;
     size_t lds = wave ? sizeof(WaveBuildLds) : sizeof(StepLds);
     if (lds < sizeof(float) * 4 * kStage) lds = sizeof(float) * 4 * kStage;
-    const unsigned g = grid_for(B, fwd_samples_per_block(d, NB), cus) +
-                       (wave ? (T_ << ix.vshift) / kWaveParts : (T_ << ix.vshift));
-#define DLRM_LAUNCH_FWDIX(TY, N_)                                                                                  \
-    if (d == 128)                                                                                                  \
-        hipLaunchKernelGGL((interact_fwd_index_kernel<TY, N_, 128>), dim3(g), dim3(256), lds, s, d, F, B,            \
-                           (const TY*)x, x_ld, (TY*)out, out_ld, padding, ga, ix, tp);                               \
-    else                                                                                                           \
-        hipLaunchKernelGGL((interact_fwd_index_kernel<TY, N_>), dim3(g), dim3(256), lds, s, d, F, B, (const TY*)x,   \
-                           x_ld, (TY*)out, out_ld, padding, ga, ix, tp);
-    if (dtype == DLRM_F32) {
-        if (NB == 1) DLRM_LAUNCH_FWDIX(float, 1) else DLRM_LAUNCH_FWDIX(float, 2)
-    } else {
-        if (NB == 1) DLRM_LAUNCH_FWDIX(uint16_t, 1) else DLRM_LAUNCH_FWDIX(uint16_t, 2)
-    }
-#undef DLRM_LAUNCH_FWDIX
+    const unsigned g = grid_for(B, 4, ctx_num_cus(ctx)) + (wave ? (T_ << ix.vshift) / kWaveParts : (T_ << ix.vshift));
+    with_elem(p.f32, [&](auto e) {
+        typedef decltype(e) T;
+        const auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(g), dim3(256), lds, ctx_stream(ctx), d, T_ + 1, B, (const T*)x, x_ld, (T*)out,
+                               out_ld, padding, ga, ix, tp);
+        };
+        with_int<1, 2>(p.NB, [&](auto nb) {
+            if (p.DC == 128) go(interact_fwd_index_kernel<T, decltype(nb)::value, 128>);
+            else go(interact_fwd_index_kernel<T, decltype(nb)::value>);
+        });
+    });
     return ctx_hip(ctx, hipGetLastError(), "step_fwd launch");
 }
 
-// The forms <NB, WPS, CPL, SPB> of interact_bwd_split_kernel that exist for a rule (kRule*) and an element type.
-// d = 128: two waves per sample (WPS 2, 4 samples per block),
-// or 8 columns per lane (bf16 rows, one wave per sample, 2 samples per block); d <= 64: one wave per sample, 8
-// samples per block.  Descent has them all, with 2, 4 or 8 samples per block at d = 128 (DLRM_BWD_SPB).  The other
-// rules have the default samples per block only, and no form that would run below Descent's occupancy
-// (DESIGN.md sections 14 and 15):
-//  - 8 columns per lane with up to 16 features (NB = 1): the split write took that form from 6 to 5 waves per SIMD
-//    (96 VGPRs against Descent's 80), so those shapes keep the two-wave form, which holds Descent's 8;
-//  - with up to 16 features Descent's forms hold 8 waves per SIMD at 56..59 VGPRs, and the row-wise forms need
-//    77..87, the element-wise one-wave form on fp32 tables 66.
-// The split rule's rows live in bf16 tables, and so do the stochastic rule's: that rule has
-// every default-geometry form of Descent on bf16 tables but the 8-column one with up to 16 features, as the split rule.
-constexpr bool step_bwd_form(int rule, bool f32, int NB, int WPS, int CPL, int SPB) {
-    const bool d128 = WPS == 2 || CPL == 8, descent = rule == kRuleDescent;
-    if ((CPL == 8 && (f32 || WPS != 1)) || !(SPB == 2 || SPB == 4 || SPB == 8)) return false;
-    if (SPB != (CPL == 8 ? 2 : (d128 ? 4 : 8))) return descent && d128;
-    if (descent) return true;
-    if (CPL == 8 && NB == 1) return false;
-    if (rule == kRuleSplit || rule == kRuleStochastic) return !f32;
-    return rule == kRuleRowwise ? NB == 2 : !(NB == 1 && WPS == 1 && f32);
-}
 // the kRule* of a StepUpdate type
 template <typename SU>
 constexpr int rule_of() {
@@ -1842,122 +1744,85 @@ constexpr int rule_of() {
                       : (SU::kStochastic ? kRuleStochastic
                                          : (SU::kAdagrad == 2 ? kRuleRowwise : (SU::kAdagrad == 1 ? kRuleAdagrad : kRuleDescent)));
 }
-// Shapes (among step_split_supported's) whose step backward has the rule's once-hit write.  Descent and the split
-// rule: all of them (interact_bwd_update_kernel takes the d that interact_bwd_split_kernel does not).  An Adagrad rule
-// and the stochastic rule (bf16 tables): d = 128 and d <= 64, the forms of interact_bwd_split_kernel; any other d and
-// the DLRM_BWD_NOSPLIT override take the gather backward.  The row-wise rule also needs the vector apply's summation
-// order to exist for the shape (fp32 dt rows of d / 4 vectors, d / 4 a power of two: apply_kernel.hpp dispatch_apply);
-// the any-D kernels sum a row's squares in column order, which no lane layout here reproduces.
-bool step_bwd_supported(int kind, int dtype, int T_, int d) {
-    if (kind == kRuleDescent || kind == kRuleSplit) return true;
-    if (knobs().bwd_nosplit || !(d == 128 || d <= 64)) return false;
-    if (kind == kRuleRowwise && !(d >= 8 && (d & (d - 1)) == 0)) return false;
-    return step_bwd_form(kind, dtype == DLRM_F32, (T_ + 1 + 15) / 16, d == 128 ? 2 : 1, 4, d == 128 ? 4 : 8);
-}
 
 // Training-step backward after launch_step_fwd under the rule SU: once-hit rows updated in place, dt rows of the
-// others written for the apply.  The caller checked the shape (launch_step_fwd accepted it), the 16-B alignment of
-// dx / dt and of the rule's second stream, and step_bwd_supported.  The DLRM_BWD_SPB /
-// DLRM_BWD_CPL / DLRM_UPD_SBU overrides are Descent's.
+// others written for the apply.  (A form step_bwd_form leaves out is not instantiated.)
 template <typename T, typename SU>
-static int launch_step_bwd_rule(dlrm_ctx* ctx, const GatherArgs& ga, int F, int d, int B, const void* x_, int64_t x_ld,
-                                const void* dout_, int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld,
-                                const SU& su) {
-    constexpr bool f32 = sizeof(T) == 4, descent = rule_of<SU>() == kRuleDescent;
-    const T* x = (const T*)x_;
-    const T* dout = (const T*)dout_;
-    const int NB = (F + 15) / 16;
+static int launch_step_bwd_rule(dlrm_ctx* ctx, const InteractPlan& p, const BwdArgs& a, const SU& su) {
+    [[maybe_unused]] constexpr bool f32 = sizeof(T) == 4, descent = rule_of<SU>() == kRuleDescent;
     hipStream_t s = ctx_stream(ctx);
-    auto launched = [&](const char* form) {
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? DLRM_OK : ctx_hip(ctx, e, (std::string(SU::kName) + form + " launch").c_str());
-    };
-    // (a form step_bwd_form leaves out is not instantiated)
-#define DLRM_FORM(N_, DC_, W_, C_, S_, WHAT_)                                                                       \
-    if constexpr (step_bwd_form(rule_of<SU>(), f32, N_, W_, C_, S_))                                                \
-        if (NB == N_ && spb == S_) {                                                                                \
-            hipLaunchKernelGGL((interact_bwd_split_kernel<T, N_, DC_, S_, W_, false, C_, false, SU>),                \
-                               dim3((unsigned)((B + S_ - 1) / S_)), dim3(64 * W_ * S_), 0, s, d, F, B, dout, dout_ld, \
-                               dx, dx_ld, dt, dt_ld, ga, x, x_ld, su);                                               \
-            return launched(WHAT_);                                                                                 \
-        }
-#define DLRM_FORMS(DC_, W_, C_, WHAT_)                                                                  \
-    DLRM_FORM(1, DC_, W_, C_, 8, WHAT_) DLRM_FORM(1, DC_, W_, C_, 4, WHAT_) DLRM_FORM(1, DC_, W_, C_, 2, WHAT_) \
-    DLRM_FORM(2, DC_, W_, C_, 8, WHAT_) DLRM_FORM(2, DC_, W_, C_, 4, WHAT_) DLRM_FORM(2, DC_, W_, C_, 2, WHAT_)
-    if (!knobs().bwd_nosplit && (d == 128 || d <= 64)) {
-        // bf16, B > 2048: 8 columns per lane, one wave per sample, 2 samples per block
-        // (kaggle-d128-b8192-bf16: backward 52.2 -> 48.4 us, step 110.9 -> 103.3 us, r6q; at B = 2048
-        // the two-wave form keeps the step shorter: Terabyte rows 50.6 vs 48.7 M samples/s, r6s).
-        // DLRM_BWD_CPL = 4 / 8 forces either form.
-        const int cpl_env = descent ? knobs().bwd_cpl : 0;
-        const bool cpl8 = d == 128 && !f32 && (cpl_env ? cpl_env == 8 : B > 2048) &&
-                          step_bwd_form(rule_of<SU>(), f32, NB, 1, 8, 2);
-        // samples per block (DLRM_BWD_SPB = 2, 4 or 8 overrides)
-        const int spb_env = !(descent && d == 128) ? 0
-                            : knobs().bwd_spb >= 8 ? 8 : (knobs().bwd_spb >= 4 ? 4 : (knobs().bwd_spb > 0 ? 2 : 0));
-        const int spb = spb_env ? spb_env : (cpl8 ? 2 : (d == 128 ? 4 : 8));
-        if (cpl8) {
-            DLRM_FORMS(128, 1, 8, SU::kAdagrad ? "(8 columns per lane)" : "(split)")
-        } else if (d == 128) {  // (two 64-column super-blocks): two waves per sample
-            DLRM_FORMS(128, 2, 4, "(split)")
-        } else {  // d <= 64: the same kernel with one wave per sample
-            DLRM_FORMS(0, 1, 4, "(one wave per sample)")
-        }
-        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no kernel for this shape", SU::kName);
+    bool done = false;
+    if (p.kernel == InteractKernel::BwdSplit) {
+        with_int<1, 2>(p.NB, [&](auto nb) {
+            with_int<1, 2>(p.WPS, [&](auto w) {
+                with_int<4, 8>(p.CPL, [&](auto c) {
+                    with_int<8, 4, 2>(p.SPB, [&](auto spb) {
+                        constexpr int NB = decltype(nb)::value, WPS = decltype(w)::value, CPL = decltype(c)::value;
+                        constexpr int SPB = decltype(spb)::value, DC = WPS == 2 || CPL == 8 ? 128 : 0;
+                        if constexpr (step_bwd_form(rule_of<SU>(), f32, NB, WPS, CPL, SPB)) {
+                            launch_split<T, NB, DC, SPB, WPS, false, CPL, false, SU>(s, a, su);
+                            done = true;
+                        }
+                    });
+                });
+            });
+        });
+    } else if constexpr (SU::kAdagrad == 0 && !SU::kStochastic) {  // interact_bwd_update_kernel: Descent, the split rule
+        if (p.kernel == InteractKernel::BwdUpdate) with_int<1, 2>(p.NB, [&](auto nb) {
+            with_int<1, 2>(p.SBU, [&](auto sbu) {
+                with_int<0, 128>(p.DC, [&](auto dc) {
+                    constexpr int NB = decltype(nb)::value, SBU = decltype(sbu)::value, DC = decltype(dc)::value;
+                    if constexpr (descent ? (SBU == 1 || DC == 128) : (SBU == 1 && DC == 0)) {
+                        typedef BwdGeom<NB> G;
+                        const size_t lds = sizeof(float) * G::template lds_floats<true>() * G::WPB +
+                                           (sizeof(TableDesc) + (SU::kSplit ? sizeof(void*) : 0)) * (a.F - 1);
+                        hipLaunchKernelGGL((interact_bwd_update_kernel<T, NB, SBU, DC, SU>),
+                                           dim3(grid_for(a.B, G::WPB, ctx_num_cus(ctx))), dim3(64 * G::WPB), lds, s, a.d, a.F,
+                                           a.B, (const T*)a.dout, a.dout_ld, a.dx, a.dx_ld, a.dt, a.dt_ld, a.ga,
+                                           (const T*)a.x, a.x_ld, su);
+                        done = true;
+                    }
+                });
+            });
+        });
     }
-#undef DLRM_FORMS
-#undef DLRM_FORM
-    // any other d: interact_bwd_update_kernel (Descent and the split rule; an Adagrad or the stochastic rule's caller
-    // took the gather backward).  One super-block of T rows in flight: two (the gather backward's choice) spill here
-    if constexpr (SU::kAdagrad != 0 || SU::kStochastic) {
-        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no kernel for this shape", SU::kName);
-    } else {
-        const int dc = descent && d == 128 ? 128 : 0, sbu = dc == 128 && knobs().upd_sbu == 2 ? 2 : 1;
-#define DLRM_UPD(N_, SBU_, DC_)                                                                                     \
-    if constexpr (descent || (SBU_ == 1 && DC_ == 0))                                                               \
-        if (NB == N_ && sbu == SBU_ && dc == DC_) {                                                                 \
-            typedef BwdGeom<N_> G;                                                                                  \
-            const size_t lds = sizeof(float) * G::template lds_floats<true>() * G::WPB +                            \
-                               (sizeof(TableDesc) + (SU::kSplit ? sizeof(void*) : 0)) * (F - 1);                    \
-            hipLaunchKernelGGL((interact_bwd_update_kernel<T, N_, SBU_, DC_, SU>),                                   \
-                               dim3(grid_for(B, G::WPB, ctx_num_cus(ctx))), dim3(64 * G::WPB), lds, s, d, F, B, dout, \
-                               dout_ld, dx, dx_ld, dt, dt_ld, ga, x, x_ld, su);                                      \
-            return launched("");                                                                                    \
-        }
-        DLRM_UPD(1, 2, 128) DLRM_UPD(1, 1, 128) DLRM_UPD(1, 1, 0) DLRM_UPD(2, 2, 128) DLRM_UPD(2, 1, 128) DLRM_UPD(2, 1, 0)
-#undef DLRM_UPD
-        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no kernel for this shape", SU::kName);
-    }
+    if (!done) return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "%s: no kernel for this shape", SU::kName);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return DLRM_OK;
+    const char* const form = p.kernel == InteractKernel::BwdUpdate ? ""
+                             : p.CPL == 8 ? (SU::kAdagrad ? "(8 columns per lane)" : "(split)")
+                                          : (p.WPS == 2 ? "(split)" : "(one wave per sample)");
+    return ctx_hip(ctx, e, (std::string(SU::kName) + form + " launch").c_str());
 }
 
 // The one launcher of the public step backward: the arguments every rule shares, then the rule's StepUpdate type (and,
-// where the rule takes fp32 tables, the element type).
+// where the rule takes fp32 tables, the element type).  The caller checked the shape (has_split_bwd: 16-B aligned
+// table rows among it), the 16-B alignment of dx / dt and of the rule's second stream, and bf16 tables for the rules
+// that need them.
 int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, const void* idx, int itype,
                     int64_t tstride, int base, int d, int B, const void* x, int64_t x_ld, const void* dout,
                     int64_t dout_ld, float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, const IndexerDev& ix,
                     const BoundRule& r) {
-    if (B == 0 || T_ == 0) return DLRM_OK;
+    const InteractPlan p = plan_site(InteractSite::StepBwd, true, T_, dtype, d, B, 1, x, x_ld, nullptr, 0, nullptr, 0, nullptr,
+                                     0, nullptr, r.kind);
+    if (p.kernel == InteractKernel::None && p.rc == DLRM_OK) return DLRM_OK;  // (a refusal: the rule's message below)
     const GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
+    const BwdArgs a{d, T_ + 1, B, dout, dout_ld, nullptr, 0, dx, dt, dx_ld, dt_ld, ga, x, x_ld};
     const StepUpdate su{ix.single, ix.cap, r.lr, ctx_error_word(ctx)};
-    const bool f32 = dtype == DLRM_F32;
     float* const* const state = (float* const*)r.state;
-#define DLRM_RULE(TY, ...) \
-    return launch_step_bwd_rule<TY>(ctx, ga, T_ + 1, d, B, x, x_ld, dout, dout_ld, dx, dx_ld, dt, dt_ld, __VA_ARGS__)
+    const auto run = [&](auto e, const auto& rule) { return launch_step_bwd_rule<decltype(e)>(ctx, p, a, rule); };
     switch (r.kind) {
-        case kRuleSplit: DLRM_RULE(uint16_t, SplitStepUpdate{su, (uint16_t* const*)r.state});
+        case kRuleSplit: return run(uint16_t{}, SplitStepUpdate{su, (uint16_t* const*)r.state});
         case kRuleStochastic:
-            DLRM_RULE(uint16_t, StochasticStepUpdate{su, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.step});
+            return run(uint16_t{}, StochasticStepUpdate{su, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.step});
         case kRuleAdagrad:
-            if (f32) DLRM_RULE(float, AdagradStepUpdate<false>{su, state, r.eps});
-            DLRM_RULE(uint16_t, AdagradStepUpdate<false>{su, state, r.eps});
+            return p.f32 ? run(float{}, AdagradStepUpdate<false>{su, state, r.eps})
+                         : run(uint16_t{}, AdagradStepUpdate<false>{su, state, r.eps});
         case kRuleRowwise:
-            if (f32) DLRM_RULE(float, AdagradStepUpdate<true>{su, state, r.eps});
-            DLRM_RULE(uint16_t, AdagradStepUpdate<true>{su, state, r.eps});
-        default:
-            if (f32) DLRM_RULE(float, su);
-            DLRM_RULE(uint16_t, su);
+            return p.f32 ? run(float{}, AdagradStepUpdate<true>{su, state, r.eps})
+                         : run(uint16_t{}, AdagradStepUpdate<true>{su, state, r.eps});
+        default: return p.f32 ? run(float{}, su) : run(uint16_t{}, su);
     }
-#undef DLRM_RULE
 }
 
 }  // namespace dlrm

@@ -39,8 +39,9 @@ Input families (all seeded, _rows):
             two.  Those pairs are compared bit for bit (no operand bit lost, the right k of the right
             pair); normal x normal pairs with assert_close.
 
-Which shape reaches which kernel (NB = ceil(F / 16) 16-row blocks; B in {1, 5, 9}: one sample, and a
-four-sample workgroup plus a tail):
+Which shape reaches which kernel (the rule: DESIGN.md section 22 and csrc/interact_plan.hpp, held row by row by
+tests/test_interact_plan_host.py; below, the shapes this module picks from it.  NB = ceil(F / 16) 16-row blocks;
+B in {1, 5, 9}: one sample, and a four-sample workgroup plus a tail):
   dlrm_interact_fwd         interact_fwd_kernel<NB = 1..6> for F in {2, 16 | 17, 27, 32 | 33 | 49 | 65 |
                             81, 96}; d = 128: the kernel compiled for it (pad_to = 8 or 64 there:
                             padding columns); d = 256;
