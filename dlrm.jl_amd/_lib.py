@@ -93,6 +93,9 @@ SIGNATURES = {
     "dlrm_indexer_set_parts": (_i32, [_vp, _vp, _i32]),
     "dlrm_sgd_update": (_i32, [_vp, _vp, _vp, _u32, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _i64, _i64, _f32]),
     "dlrm_adagrad_create": (_i32, [_vp, _vp, _i32, _pp, _pp]),
+    "dlrm_adagrad_create_sr": (_i32, [_vp, _vp, _i32, _pp, _i64, _pp]),
+    "dlrm_adagrad_seek": (_i32, [_vp, _vp, _i64]),
+    "dlrm_adagrad_step": (_i32, [_vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),
     "dlrm_adagrad_destroy": (_i32, [_vp]),
     "dlrm_adagrad_update": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _i64, _i64,
                                    _f32, _f32]),

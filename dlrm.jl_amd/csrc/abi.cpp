@@ -62,6 +62,10 @@ struct StatePtrs : StateDims {
 // Sparse Adagrad: fp32 state
 struct dlrm_adagrad : StatePtrs<float> {
     bool rowwise = false;  // one word per table row instead of one row
+    // the stochastic kind (dlrm_adagrad_create_sr): bf16 tables, the weights' store rounded with the seed and the step
+    bool stochastic = false;
+    uint64_t seed = 0;
+    uint64_t* d_step = nullptr;  // one device word, as dlrm_sr_sgd's
 };
 // The low halves of split-bf16 tables
 struct dlrm_split_sgd : StatePtrs<uint16_t> {};
@@ -83,7 +87,7 @@ struct RuleDesc {
                             // it has one
     unsigned bit;           // of dlrm_indexer_state, when its step backward stepped a build's once-hit rows
     ApplyFn* apply;         // the update's apply launch
-    ApplyFn* step_apply;    // the training step's
+    ApplyFn* step_apply;    // the training step's; NULL: the rule has no fused step (its entry point refuses the handle)
 };
 static const RuleDesc kRules[kNumRules] = {
     {"dlrm_sgd_update", "dlrm_step_bwd", "Descent", nullptr, nullptr, nullptr, 0u, launch_sgd_apply, launch_sgd_apply},
@@ -99,6 +103,14 @@ static const RuleDesc kRules[kNumRules] = {
     {"dlrm_sr_sgd_update", "dlrm_sr_step_bwd", "the stochastic rule", "the optimizer was",
      "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule rounds each row's complete step once",
      DLRM_IX_SINGLES_STOCHASTIC, launch_sr_sgd_apply, launch_sr_step_apply},
+    // (the Adagrad rules of a dlrm_adagrad_create_sr handle: no step backward, so no mark of their own and no build of
+    // another's mark to complete)
+    {"dlrm_adagrad_update", "dlrm_adagrad_step_bwd", "the stochastic element-wise Adagrad rule", "the optimizer state was",
+     "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule needs each row's complete sum", 0u,
+     launch_sr_adagrad_apply, nullptr},
+    {"dlrm_adagrad_update", "dlrm_adagrad_step_bwd", "the stochastic row-wise Adagrad rule", "the optimizer state was",
+     "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule needs each row's complete sum", 0u,
+     launch_sr_rowwise_adagrad_apply, nullptr},
 };
 
 // The rule of a call, from its handle and scalars
@@ -117,7 +129,10 @@ static BoundRule bind_rule(const dlrm_split_sgd* op, float lr) {
 }
 static BoundRule bind_rule(const dlrm_adagrad* op, float lr, float eps) {
     BoundRule r = bind_rule(lr);
-    r.kind = op->rowwise ? kRuleRowwise : kRuleAdagrad;
+    r.kind = op->stochastic ? (op->rowwise ? kRuleStochasticRowwise : kRuleStochasticAdagrad)
+                            : (op->rowwise ? kRuleRowwise : kRuleAdagrad);
+    r.seed = op->seed;
+    r.step = op->d_step;
     r.eps = eps;
     r.state = op->d_ptr;
     r.aligned16 = op->rowwise || op->aligned16;  // (a row-wise state word is loaded alone)
@@ -1099,7 +1114,7 @@ static int check_rule(dlrm_ctx* ctx, const dlrm_tables* tb, const BoundRule& r, 
 // another seed or step.
 static int check_completes(dlrm_ctx* ctx, const dlrm_indexer* ix, const BoundRule& r, const char* fn, const char* mode) {
     if (!ix->singles_done) return DLRM_OK;
-    const bool same_rule = ix->singles_rule == r.kind;
+    const bool same_rule = ix->singles_rule == r.kind;  // (never a rule without a step backward: it marks no build)
     if (same_rule && (r.kind != kRuleStochastic || ix->singles_handle == r.handle)) return DLRM_OK;
     const RuleDesc& by = kRules[ix->singles_rule];
     return ctx_fail(ctx, DLRM_E_STATE, "%s%s: a split backward (%s) already stepped this build's once-hit rows with %s%s",
@@ -1158,7 +1173,52 @@ int dlrm_adagrad_create(dlrm_ctx* ctx, const dlrm_tables* tb, int rowwise, float
     return rc;
 }
 
-int dlrm_adagrad_destroy(dlrm_adagrad* op) { return state_destroy(op); }
+int dlrm_adagrad_create_sr(dlrm_ctx* ctx, const dlrm_tables* tb, int rowwise, float* const* state, int64_t seed,
+                           dlrm_adagrad** out) {
+    CHECK_ARG(ctx && tb && out, "dlrm_adagrad_create_sr: null argument");
+    *out = nullptr;
+    CHECK_ARG(tb->dtype == DLRM_BF16, "dlrm_adagrad_create_sr: stochastic rounding is of bf16 tables (fp32: nothing to round)");
+    // the Philox counter holds the table in 16 bits and the column's block of four in 16 bits
+    CHECK_ARG(tb->T <= 65536 && (tb->D + 3) / 4 <= 65536, "dlrm_adagrad_create_sr: %d tables of dim %d (at most 65536 "
+              "tables, dim / 4 at most 65536)", tb->T, tb->D);
+    dlrm_adagrad* op = nullptr;
+    int rc = state_create(ctx, tb, false, state, &op, {"dlrm_adagrad_create_sr", "state", "state", "adagrad state"});
+    if (rc) return rc;
+    op->rowwise = rowwise != 0;
+    op->stochastic = true;
+    op->seed = (uint64_t)seed;
+    rc = ctx_hip(ctx, hipMalloc((void**)&op->d_step, sizeof(uint64_t)), "hipMalloc(adagrad step)");
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMemset(op->d_step, 0, sizeof(uint64_t)), "hipMemset(adagrad step)");
+    if (rc != DLRM_OK) {
+        (void)dlrm_adagrad_destroy(op);
+        return rc;
+    }
+    *out = op;
+    return DLRM_OK;
+}
+
+int dlrm_adagrad_destroy(dlrm_adagrad* op) {
+    if (op && op->d_step) (void)hipFree(op->d_step);
+    return state_destroy(op);
+}
+
+int dlrm_adagrad_seek(dlrm_ctx* ctx, dlrm_adagrad* op, int64_t step) {
+    CHECK_ARG(ctx && op, "dlrm_adagrad_seek: null ctx/optimizer");
+    CHECK_ARG(op->stochastic, "dlrm_adagrad_seek: the handle has no step (dlrm_adagrad_create_sr makes one that has)");
+    const int rc = hip_set(ctx);
+    if (rc) return rc;
+    return launch_sr_step_set(ctx, op->d_step, (uint64_t)step);
+}
+
+int dlrm_adagrad_step(dlrm_ctx* ctx, dlrm_adagrad* op, uint64_t* out) {
+    CHECK_ARG(ctx && op && out, "dlrm_adagrad_step: null ctx/optimizer/out");
+    CHECK_ARG(op->stochastic, "dlrm_adagrad_step: the handle has no step (dlrm_adagrad_create_sr makes one that has)");
+    int rc = hip_set(ctx);
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    if (rc == DLRM_OK)
+        rc = ctx_hip(ctx, hipMemcpy(out, op->d_step, sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy(adagrad step)");
+    return rc;
+}
 
 int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, unsigned flags,
                         const void* indices, int itype, int64_t table_stride, int index_base, int batch, int lookups,
@@ -1430,12 +1490,18 @@ int dlrm_split_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_split_sgd* 
 int dlrm_adagrad_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, STEP_ARGS, float lr,
                           float eps, unsigned flags) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_adagrad_step_bwd: null ctx/tables/optimizer/indexer");
+    if (op->stochastic)  // (nothing launched or written; the handle's step word stays)
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_adagrad_step_bwd: no fused training step with a stochastic handle "
+                        "(dlrm_adagrad_create_sr): dlrm_adagrad_update steps its tables");
     return step_bwd_impl(ctx, tb, ix, bind_rule(op, lr, eps), STEP_PASS, flags, nullptr);
 }
 
 int dlrm_adagrad_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, STEP_ARGS,
                                   float lr, float eps, dlrm_indexer* next, const void* next_indices, unsigned flags) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_adagrad_step_bwd_prepare: null ctx/tables/optimizer/indexer");
+    if (op->stochastic)  // (nothing launched or written; the handle's step word stays)
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_adagrad_step_bwd_prepare: no fused training step with a stochastic handle "
+                        "(dlrm_adagrad_create_sr): dlrm_adagrad_update steps its tables");
     return step_bwd_prepare_impl(ctx, tb, ix, bind_rule(op, lr, eps), STEP_PASS, next, next_indices, flags);
 }
 

@@ -91,10 +91,13 @@ __device__ __forceinline__ void add_vec(float* acc, const typename Vec<GT>::type
 //   StochasticDescent  W' = fmaf(-lr, G, w);  w = sr_bf16(W', R): Descent on bf16 tables whose store rounds W' up
 //                   or down with probability proportional to its distance to each bf16 neighbour (no state; R =
 //                   16 Philox bits of (seed, step, table, row, column), below)
+//   StochasticAdagrad, StochasticRowwiseAdagrad  the Adagrad rules on bf16 tables with that store: the parent's G, state
+//                   and W', w = sr_bf16(W', R) (below StochasticDescent)
 // A rule holds its parameters, its state's row address (state_row), its once-hit positions per lane group
 // (singles_ppg), the any-D kernels' write of one column (scalar_write) and the MODEs and table element types
-// it is instantiated for (kCarriesBuild, kBuildWithApply, kF32Tables).  The vector items below still branch on kState (0 none,
-// 1 a state row per table row, 2 a state word, 3 a row of low halves, 4 none and a stochastic store): written once over a per-rule row type
+// it is instantiated for (kCarriesBuild, kBuildWithApply, kF32Tables), and whether its store of the weights is the
+// stochastic one (kStochastic: rule_store then calls its store<NE>, and the kernels its load_step).  The vector items below still branch on kState (0 none,
+// 1 a state row per table row, 2 a state word, 3 a row of low halves, 4 none: StochasticDescent): written once over a per-rule row type
 // they no longer compiled to the same code.  The state is loaded where the table row
 // is (beside the grad rows: these items are bound by dependent round trips) and written once, with the row.
 
@@ -177,6 +180,7 @@ struct Descent {
     float lr;
     typedef float State;
     static constexpr int kState = 0;  // (the items' per-rule branches: 0 none, 1 a state row, 2 a state word, 3 low halves)
+    static constexpr bool kStochastic = false;  // (rule_store: the weights' store rounds to nearest)
     static constexpr bool kCarriesBuild = true;  // MODE >= 2: the next batch's build rides on its launches
     static constexpr bool kBuildWithApply = true;  // ... instantiated where its MODE 0 / 1 launches are
     static constexpr bool kF32Tables = true;
@@ -195,6 +199,7 @@ struct Adagrad {
     float* const* state;  // [T] device pointers, fp32 [nrows][D]
     typedef float State;
     static constexpr int kState = 1;
+    static constexpr bool kStochastic = false;
     // MODE >= 2 over the training step's fp32 dt, in a unit of its own (adagrad_step.hip:
     // launch_adagrad_step_apply), so adagrad.hip stays the MODE 0 / 1 unit it was
     static constexpr bool kCarriesBuild = true;
@@ -224,6 +229,7 @@ struct RowwiseAdagrad {
     float* const* state;  // [T] device pointers, fp32 [nrows]
     typedef float State;
     static constexpr int kState = 2;
+    static constexpr bool kStochastic = false;
     // (MODE >= 2: adagrad_rowwise_step.hip, launch_rowwise_adagrad_step_apply)
     static constexpr bool kCarriesBuild = true;
     static constexpr bool kBuildWithApply = false;
@@ -254,6 +260,7 @@ struct SplitDescent {
     uint16_t* const* lo;  // [T] device pointers, uint16 [nrows][D]: the low halves
     typedef uint16_t State;
     static constexpr int kState = 3;
+    static constexpr bool kStochastic = false;
     // MODE >= 2 over bf16 tables and the training step's fp32 dt, in a unit of their own (split_step.hip:
     // launch_split_step_apply), so split_sgd.hip stays the MODE 0 / 1 unit it was
     static constexpr bool kCarriesBuild = true;
@@ -318,6 +325,7 @@ struct StochasticDescent {
     uint32_t s0, s1;       // its value, by load_step
     typedef float State;
     static constexpr int kState = 4;
+    static constexpr bool kStochastic = true;  // (rule_store: its store<NE>; the kernels call its load_step)
     // MODE >= 2 over the training step's fp32 dt, in a unit of its own (sr_step.hip: launch_sr_step_apply), so
     // sr_sgd.hip stays the MODE 0 / 1 unit it was
     static constexpr bool kCarriesBuild = true;
@@ -362,10 +370,125 @@ struct StochasticDescent {
         stg<uint16_t>(row + c, sr_bf16(w, x[c & 3] & 0xffffu));
     }
 };
+// ---- the Adagrad rules with the stochastic store (bf16 tables): G, the state update and the fp32 result W' of every
+// element are the parent rule's at that write site (the same expressions in the same order: the items branch on the
+// parent's kState), the state is written with the parent's bits, and the element stored is sr_bf16(W', R) with the
+// R, the key and the counter defined above.  A rule is its parent's fields and SrWord: the seed's halves, the handle's
+// step word and its value; the word is read and advanced as StochasticDescent's is.
+struct SrWord {
+    uint32_t k0, k1;       // the seed's halves
+    const uint64_t* step;  // the handle's step word
+    uint32_t s0, s1;       // its value, by load_step
+    static constexpr bool kRederiveLane = true;  // (rederives_lane, below)
+    __device__ __forceinline__ void load_step() {
+        const uint64_t s = ldg<uint64_t>(step);
+#if defined(__HIP_DEVICE_COMPILE__)
+        s0 = __builtin_amdgcn_readfirstlane((uint32_t)s);
+        s1 = __builtin_amdgcn_readfirstlane((uint32_t)(s >> 32));
+#else  // host pass of the device code: never executed
+        s0 = (uint32_t)s;
+        s1 = (uint32_t)(s >> 32);
+#endif
+    }
+    // the output block of columns 4b .. 4b + 3 of row r of table t
+    __device__ __forceinline__ void block(uint32_t* x, int t, uint32_t r, int b) const {
+        x[0] = r;
+        x[1] = ((uint32_t)t << 16) | (uint32_t)b;
+        x[2] = s0;
+        x[3] = s1;
+        // the ten round keys are made here, at the write: left to the compiler they are hoisted out of the item loop
+        // into twenty scalar registers, which these kernels (at the scalar and the 168-vector-register limits beside a
+        // state stream) then spill
+        uint32_t ka = k0, kb = k1;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(ka), "+s"(kb));
+#endif
+        philox4x32_10(x, ka, kb);
+    }
+    // column c's 16 bits of its block x (by selects: a variable index would put x in scratch)
+    __device__ static __forceinline__ uint32_t bits_of(const uint32_t* x, int c) {
+        const uint32_t lo = (c & 1) ? x[1] : x[0], hi = (c & 1) ? x[3] : x[2];
+        return ((c & 2) ? hi : lo) & 0xffffu;
+    }
+    // the store of NE (4 or 8) elements f from column c0 (a multiple of 4) of row r of table t, at dst
+    template <int NE>
+    __device__ __forceinline__ void store(uint16_t* dst, int t, uint32_t r, int c0, const float* f) const {
+        typename Halves<NE>::type o;
+#pragma unroll
+        for (int k = 0; k < NE / 4; ++k) {
+            uint32_t x[4];
+            block(x, t, r, (c0 >> 2) + k);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[k * 4 + e] = sr_bf16(f[k * 4 + e], x[e] & 0xffffu);
+        }
+        stg<typename Halves<NE>::type>(dst, o);
+    }
+};
+
+struct StochasticAdagrad : Adagrad, SrWord {
+    static constexpr bool kStochastic = true;
+    static constexpr bool kCarriesBuild = false;  // (no fused training step with the rule: MODE 0 / 1 only)
+    static constexpr bool kF32Tables = false;     // fp32 tables: nothing to round
+    // the parent's count (the Philox rounds come at the write, after the loads) -- but for fp32 gradient rows of 16
+    // vectors (D = 64), whose MODE 1 kernel spilt 2 registers with it: half as many there (as StochasticDescent)
+    template <typename G> static constexpr int singles_ppg() {
+        return fewer_singles(Adagrad::template singles_ppg<G>(), G::NE == 4 && G::LPR == 16 ? 2 : 1);
+    }
+    template <typename TT, typename F>
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float* __restrict__ st, int64_t r, int D, int c, int t,
+                                                 F&& colsum) const {
+        static_assert(sizeof(TT) == 2, "stochastic rounding is of bf16 tables");
+        const float g = colsum(c);
+        float a = st[r * D + c], w = to_f32(row[c]);
+        adagrad_step<1>(lr, eps, &g, &a, &w);
+        st[r * D + c] = a;
+        uint32_t x[4];
+        block(x, t, (uint32_t)r, c >> 2);
+        stg<uint16_t>((uint16_t*)row + c, sr_bf16(w, bits_of(x, c)));
+    }
+};
+
+struct StochasticRowwiseAdagrad : RowwiseAdagrad, SrWord {
+    static constexpr bool kStochastic = true;
+    static constexpr bool kCarriesBuild = false;
+    static constexpr bool kF32Tables = false;
+    // (the parent's count, and half of it for fp32 gradient rows of 16 vectors: as StochasticAdagrad)
+    template <typename G> static constexpr int singles_ppg() {
+        return fewer_singles(RowwiseAdagrad::template singles_ppg<G>(), G::NE == 4 && G::LPR == 16 ? 2 : 1);
+    }
+    // (c = 0: the thread has the whole row; the squares in column order, then the step, a block per four columns)
+    template <typename TT, typename F>
+    __device__ __forceinline__ void scalar_write(TT* __restrict__ row, float* __restrict__ st, int64_t r, int D, int, int t,
+                                                 F&& colsum) const {
+        static_assert(sizeof(TT) == 2, "stochastic rounding is of bf16 tables");
+        float ss = 0.0f;
+        for (int k = 0; k < D; ++k) {
+            const float g = colsum(k);
+            ss = __builtin_fmaf(g, g, ss);
+        }
+        const float m = rowwise_m(st[r], ss, D);
+        const float s = rowwise_scale(lr, eps, m);
+        st[r] = m;
+        uint32_t x[4] = {0u, 0u, 0u, 0u};
+        for (int k = 0; k < D; ++k) {
+            if ((k & 3) == 0) block(x, t, (uint32_t)r, k >> 2);
+            const float w = __builtin_fmaf(-s, colsum(k), to_f32(row[k]));
+            stg<uint16_t>((uint16_t*)row + k, sr_bf16(w, bits_of(x, k)));
+        }
+    }
+};
+
+// Whether the apply kernel makes a lane's group constants again in every chunk and once-hit item (R::kRederiveLane):
+// the stochastic Adagrad rules, whose kernels hold a state stream and the Philox rounds under the 168 registers of
+// three workgroups per CU, and spilt two loop-invariant registers without it.  Every other rule: no, and its kernels
+// are what they were.
+template <typename R, typename = void> struct rederives_lane { static constexpr bool value = false; };
+template <typename R> struct rederives_lane<R, decltype((void)R::kRederiveLane)> { static constexpr bool value = R::kRederiveLane; };
+
 // a rule's write of NE weights f at column c0 of row r (at `row`) of table t
 template <typename TT, int NE, typename R>
 __device__ __forceinline__ void rule_store(const R& rule, TT* row, int t, uint32_t r, int c0, const float* f) {
-    if constexpr (R::kState == 4) {
+    if constexpr (R::kStochastic) {
         static_assert(sizeof(TT) == 2, "stochastic rounding is of bf16 tables");
         rule.template store<NE>((uint16_t*)row + c0, t, r, c0, f);
     } else {
@@ -444,7 +567,7 @@ __device__ __forceinline__ void run_chunk(const int32_t* __restrict__ perm, cons
         for (int j = 0; j < G::VPL; ++j) {
             adagrad_step<NE>(rule.lr, rule.eps, acc[j], sv[j], tv[j]);
             store_row<float, NE>(st + (int64_t)(uint32_t)a.z * D, (v + j * 64) * NE, sv[j]);
-            store_row<TT, NE>(row, (v + j * 64) * NE, tv[j]);
+            rule_store<TT, NE>(rule, row, t, (uint32_t)a.z, (v + j * 64) * NE, tv[j]);
         }
         return;
     }
@@ -628,7 +751,7 @@ __device__ __forceinline__ void slice_write(const R& rule, const f32x4& G, float
         if (mine) {
             adagrad_step<4>(rule.lr, rule.eps, g, sw, rw);
             store_row<float, 4>(srow, tid * 4, sw);
-            store_row<TT, 4>(row, tid * 4, rw);
+            rule_store<TT, 4>(rule, row, t, r, tid * 4, rw);
         }
         return;
     }

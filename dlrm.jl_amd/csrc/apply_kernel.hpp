@@ -2,7 +2,8 @@
 // any-D fallback kernels and their launchers, by update rule.  update.hip instantiates Descent
 // (every MODE), adagrad.hip and adagrad_rowwise.hip the Adagrad rules, split_sgd.hip the split rule and sr_sgd.hip
 // the stochastic rule (MODE 0 and 1), and split_step.hip, adagrad_step.hip, adagrad_rowwise_step.hip and sr_step.hip those four
-// rules' build-carrying launches (MODE 2 / 3 / 5): they compile side by side.
+// rules' build-carrying launches (MODE 2 / 3 / 5), and sr_adagrad.hip and sr_adagrad_rowwise.hip the Adagrad rules with the
+// stochastic store (MODE 0 and 1): they compile side by side.
 #pragma once
 #include "apply.hpp"
 
@@ -44,7 +45,25 @@ static inline int prep_wave_kind(const PrepArgs& pa) {
 // workgroups of a build (4 parts each)
 __host__ __device__ __forceinline__ int prep_groups(const PrepArgs& pa) { return (pa.T << pa.ix.vshift) / kWaveParts; }
 
-// R: the update rule (apply.hpp: Descent, Adagrad, RowwiseAdagrad, SplitDescent, StochasticDescent).
+// An item's place by the scan of the tables' counts (indexer.hpp locate).  A rule at the register limit (apply.hpp
+// rederives_lane) reads the counts through an opaque copy of their address, so the lane's address into them (the walk
+// over more than 256 tables) is made in the item, not held across the item loop.
+template <typename R>
+__device__ __forceinline__ void locate_item(const IndexerDev& ix, int T_, int which, const TableScan& sc, int id, int& table,
+                                            int& local) {
+    if constexpr (rederives_lane<R>::value) {
+        IndexerDev ixi = ix;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(ixi.counts));
+#endif
+        locate(ixi, T_, which, sc, id, table, local);
+    } else {
+        locate(ix, T_, which, sc, id, table, local);
+    }
+}
+
+// R: the update rule (apply.hpp: Descent, Adagrad, RowwiseAdagrad, SplitDescent, StochasticDescent and the two
+// stochastic Adagrad rules).
 template <typename TT, typename GT, int VPR, int MODE, typename R = Descent>
 __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev ix, TableDesc* __restrict__ tabs, int T_,
                                                                   int L, const GT* __restrict__ grad, int64_t grad_ld,
@@ -80,7 +99,7 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
         return;
 #endif
     }
-    if constexpr (R::kState == 4) rule.load_step();  // (the stochastic rule's step word, once per workgroup)
+    if constexpr (R::kStochastic) rule.load_step();  // (the stochastic rule's step word, once per workgroup)
     // a bounds error raised since the last dlrm_check_bounds (the lookup or the indexer build of
     // this step): the reference's gather throws before update!, so no table row is written.  (The
     // error word is loaded with the item counts, one round trip for both.)
@@ -165,13 +184,24 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
 #undef APPLY_END
 #define APPLY_END() do { ITEM_END(k_); } while (0)
 #endif
+        // the lane's place in its group, for the chunk and once-hit items.  A rule at the register limit (apply.hpp
+        // rederives_lane) takes them through an opaque copy per item, so what is derived from them (position
+        // offsets, row addresses) is made again in the item instead of being held in registers across the item loop.
+        [[maybe_unused]] int vi = v, gl0 = lane - v;
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (rederives_lane<R>::value) asm volatile("" : "+v"(vi), "+v"(gl0));
+#endif
         if (SG && item >= citems) {  // uniform: once-hit positions of one real table
             const int t = (item - citems) / per_t;
             const int p0 = ((item - citems) - t * per_t) * SP + gid * PPG;
             if (g >= G::RPW) continue;
             const TableDesc td = load_table(tabs, t);
-            run_singles<TT, GT, VPR, R>(sa, ix.cap, (TT*)td.data, rule.base(t), td.nrows, t, p0,
-                                        grad + grad_offset + (int64_t)t * D, grad_ld, Ld, rule, v, lane - v);
+            if constexpr (rederives_lane<R>::value)
+                run_singles<TT, GT, VPR, R>(sa, ix.cap, (TT*)td.data, rule.base(t), td.nrows, t, p0,
+                                            grad + grad_offset + (int64_t)t * D, grad_ld, Ld, rule, vi, gl0);
+            else
+                run_singles<TT, GT, VPR, R>(sa, ix.cap, (TT*)td.data, rule.base(t), td.nrows, t, p0,
+                                            grad + grad_offset + (int64_t)t * D, grad_ld, Ld, rule, v, lane - v);
             APPLY_END();
             continue;
         }
@@ -189,7 +219,7 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
                 t = (int)(ca.x / ix.cap);  // (the compact layout: entries of table t at [t cap, (t + 1) cap))
             } else {
                 int tc, cl;
-                locate(ix, T_, CNT_C, sC, fc, tc, cl);
+                locate_item<R>(ix, T_, CNT_C, sC, fc, tc, cl);
                 if (g >= G::RPW || tc < 0) continue;
                 const int64_t co = 2 * ((int64_t)tc * ix.cap + cl);
                 ca = ix.chunks[co];
@@ -197,8 +227,12 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
                 pbase = ix.perm + (int64_t)tc * ix.cap;
                 t = tc >> ix.vshift;
             }
-            run_chunk<TT, GT, VPR, R>(pbase, ca, cb, (TT*)tabs[t].data, rule.base(t), grad + grad_offset + (int64_t)t * D,
-                                      grad_ld, Ld, rule, v, lane - v, t);
+            if constexpr (rederives_lane<R>::value)
+                run_chunk<TT, GT, VPR, R>(pbase, ca, cb, (TT*)tabs[t].data, rule.base(t),
+                                          grad + grad_offset + (int64_t)t * D, grad_ld, Ld, rule, vi, gl0, t);
+            else
+                run_chunk<TT, GT, VPR, R>(pbase, ca, cb, (TT*)tabs[t].data, rule.base(t),
+                                          grad + grad_offset + (int64_t)t * D, grad_ld, Ld, rule, v, lane - v, t);
             APPLY_END();
             continue;
         }
@@ -212,7 +246,7 @@ __global__ __launch_bounds__(kApplyThreads, 3) void sgd_apply_kernel(IndexerDev 
             continue;
         }
         int th, sl;
-        locate(ix, T_, CNT_S, sS, item, th, sl);  // item < S: found, the same for every lane
+        locate_item<R>(ix, T_, CNT_S, sS, item, th, sl);  // item < S: found, the same for every lane
         const int4 sd = ix.hot_slice[(int64_t)th * ix.cap + sl];
         const int t = th >> ix.vshift;
         run_slice<TT, GT, VPR, R>(ix, th, sl, sd, (TT*)tabs[t].data, rule.base(t), grad + grad_offset + (int64_t)t * D,
@@ -237,7 +271,7 @@ __global__ __launch_bounds__(256) void sgd_chunks_scalar(IndexerDev ix, TableDes
         return;
     }
     if (*err) return;
-    if constexpr (R::kState == 4) rule.load_step();
+    if constexpr (R::kStochastic) rule.load_step();
     const int t = blockIdx.y;
     const int nchunks = ix.counts[(int64_t)t * 8 + CNT_C];
     const int64_t off = ix.part_off(t);
@@ -262,7 +296,7 @@ __global__ __launch_bounds__(256) void sgd_hot_scalar(IndexerDev ix, TableDesc* 
                                                       const GT* __restrict__ grad, int64_t grad_ld,
                                                       int64_t grad_offset, R rule, const unsigned* __restrict__ err) {
     if (*err) return;
-    if constexpr (R::kState == 4) rule.load_step();
+    if constexpr (R::kStochastic) rule.load_step();
     const int t = blockIdx.y;
     const int nhot = ix.counts[(int64_t)t * 8 + CNT_H];
     const int64_t off = ix.part_off(t);
@@ -288,7 +322,7 @@ __global__ __launch_bounds__(256) void sgd_singles_scalar(SinglesArgs sa, int64_
                                                           int64_t grad_offset, R rule,
                                                           const unsigned* __restrict__ err) {
     if (*err) return;
-    if constexpr (R::kState == 4) rule.load_step();
+    if constexpr (R::kStochastic) rule.load_step();
     const int t = blockIdx.y;
     const int W = R::scalar_threads(D);  // threads per position
     const int64_t total = (int64_t)sa.N * W;

@@ -26,7 +26,11 @@ constexpr int kStepIndexMaxN = 2048;  // the forward-launch indexer (interact.hi
 constexpr int kArgTables = 32;  // table pointers that travel by value in a forward kernel's arguments (common.hpp TabPtrs)
 // The optimizer rules of the update and of the training step (common.hpp BoundRule; interact_plan.hpp: the step
 // backward's forms per rule)
-enum { kRuleDescent = 0, kRuleSplit, kRuleAdagrad, kRuleRowwise, kRuleStochastic, kNumRules };
+// (the last two: the Adagrad rules with the stochastic store -- an update only, no step backward has them)
+enum {
+    kRuleDescent = 0, kRuleSplit, kRuleAdagrad, kRuleRowwise, kRuleStochastic, kRuleStochasticAdagrad,
+    kRuleStochasticRowwise, kNumRules
+};
 // the wave build (indexer.hpp wave_build_group) of the next batch (in the apply launch) or of a
 // prepared batch (dlrm_indexer_prepare), and the bag build's per-part sort: up to kWaveMaxN
 // positions per table, as 16 parts per 2048 positions (2^wave_vshift(N) parts per table; a part

@@ -330,7 +330,7 @@ struct BoundRule {
     // fp32 state rows (kRuleAdagrad) or words (kRuleRowwise); and whether every row of it is 16-B aligned
     void* state = nullptr;
     bool aligned16 = true;
-    uint64_t seed = 0;         // kRuleStochastic: the handle's seed ...
+    uint64_t seed = 0;         // kRuleStochastic and the stochastic Adagrad rules: the handle's seed ...
     uint64_t* step = nullptr;  // ... and its device step word
     const StateDims* handle = nullptr;  // the optimizer handle itself (Descent: none); the launchers do not read it
 };
@@ -415,6 +415,7 @@ typedef int ApplyFn(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool a
                     int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
                     const BoundRule& rule, const SinglesArgs& singles, const PrepArgs* prep);
 ApplyFn launch_sgd_apply, launch_split_sgd_apply, launch_adagrad_apply, launch_rowwise_adagrad_apply, launch_sr_sgd_apply;
+ApplyFn launch_sr_adagrad_apply, launch_sr_rowwise_adagrad_apply;  // (sr_adagrad.hip, sr_adagrad_rowwise.hip: as launch_sr_sgd_apply)
 ApplyFn launch_split_step_apply, launch_adagrad_step_apply, launch_rowwise_adagrad_step_apply, launch_sr_step_apply;
 // the stochastic rule's step word, by one-thread launches on the context's stream (sr_sgd.hip)
 int launch_sr_step_set(dlrm_ctx* ctx, uint64_t* step, uint64_t value);

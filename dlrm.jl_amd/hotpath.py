@@ -43,7 +43,10 @@ the operator path gives.  Opt-in: without the keyword `opt=SplitDescent` keeps t
 step pair with that rule (dlrm_step_fwd, then dlrm_adagrad_step_bwd / dlrm_adagrad_step_bwd_prepare): once-hit
 rows and their state are stepped inside the backward, only the repeated rows' dt rows are written, and
 `pipeline` "apply" / "side" work as they do for Descent.  Tables and state end up bit for bit what the
-operator path gives.  Opt-in again: without the keyword the Adagrad rules keep the operator path.
+operator path gives.  Opt-in again: without the keyword the Adagrad rules keep the operator path.  With a seed (`ADAGrad(η, ε, seed=s)`,
+`RowwiseADAGrad(η, ε, seed=s)`: the stochastically rounded store, bfloat16 tables) an Adagrad optimizer has the operator
+path only (dlrm_adagrad_update(PREBUILT) and the one-thread advance of its step): `adagrad_step=True` and `pipeline`
+are refused with it.
 
 `stochastic_step=True` with `opt=StochasticDescent(η, seed)` on bfloat16 tables: the fused step pair with that rule
 (dlrm_step_fwd, then dlrm_sr_step_bwd / dlrm_sr_step_bwd_prepare): once-hit rows are stepped and stochastically
@@ -86,7 +89,8 @@ class HotPath:
                              "rule's is fused_step=True (opt=SplitDescent(eta)), the Adagrad rules' adagrad_step=True "
                              "(opt=ADAGrad(eta, eps) or opt=RowwiseADAGrad(eta, eps)), the stochastic rule's "
                              "stochastic_step=True (opt=StochasticDescent(eta, seed)); Descent(lr) is fused without a "
-                             "keyword, and without its keyword a rule takes the operator route")
+                             "keyword, without its keyword a rule takes the operator route, and an Adagrad optimizer "
+                             "with a seed (the stochastic store) has that route only")
         self._rule_step = bool(given)  # this engine runs opt's fused step (split_step, adagrad_step, stochastic_step)
         self.rule_params = None
         if opt is not None:
@@ -154,7 +158,8 @@ class HotPath:
         if opt is not None:
             if mode is not None and not self._rule_step:
                 raise ValueError("HotPath: the pipelined steps need the fused step (pipeline must be None with opt, "
-                                 f"unless {own}=True turns on the fused step of {type(opt).__name__})")
+                                 + (f"unless {own}=True turns on the fused step of {type(opt).__name__})" if own else
+                                    f"and {opt!r} has no fused step)"))
             opt.handle_of(self.ts)  # the state, allocated before any graph capture
         # (pooled bags: "side" only -- the next batch's build beside this step's apply, `step_next`)
         self.pipeline = mode if (mode and ((self.step_api and self.L == 1) or (mode == "side" and self.L > 1))) else None

@@ -77,6 +77,9 @@ mutable struct Context
         split === nothing || (lr = split.eta)
         adagrad === nothing || split === nothing ||
             throw(ArgumentError("Context: one rule steps the tables, split = or adagrad ="))
+        adagrad === nothing || adagrad.seed === nothing ||
+            throw(ArgumentError("Context: adagrad = with a seed: the stochastic store has no fused step " *
+                                "(update! with that optimizer takes the operator route)"))
         adagrad === nothing || lr === nothing || Float32(lr) == adagrad.eta ||
             throw(ArgumentError("Context: lr = $lr beside adagrad = $(nameof(typeof(adagrad)))($(adagrad.eta), …)"))
         adagrad === nothing || (lr = adagrad.eta)
@@ -442,33 +445,46 @@ end
 abstract type AbstractHipADAGrad end
 
 """
-    HipADAGrad(η = 0.1, ϵ = 1e-8)
+    HipADAGrad(η = 0.1, ϵ = 1e-8; seed = nothing)
 
 `Flux.ADAGrad(η, ϵ)` for `HipEmbedding` tables: `A .+= G.^2; w .-= η .* G ./ (sqrt.(A) .+ ϵ)` on the
 rows a batch touches (an untouched row has `G = 0`, so dense and sparse agree).  The fp32 state
 (`D × N` per table, filled with `ϵ` as Flux does) is created on the device at the first `update!` of
 a table vector and kept per table vector, as Flux keys its `IdDict` by parameter;
 `adagrad_state(opt, tables)` returns it.
+
+`seed` (default `nothing`: round to nearest): an integer makes the store of every written weight stochastic, on
+2-byte (bf16) tables only (dlrm_adagrad_create_sr).  `G`, the state and the fp32 result of every element are the
+seedless rule's, bit for bit; the bf16 stored is that result rounded as `HipStochasticDescent` rounds, with the same
+Philox bits of (seed, step, table, row, column).  The step is a device counter per table vector, 0 at first use and
+one more after every `update!` (`adagrad_seek!` sets it, `adagrad_step` reads it).  The operator route only: a seeded
+optimizer is refused as a context's `adagrad =`.
 """
 mutable struct HipADAGrad <: AbstractHipADAGrad
     eta::Float32
     epsilon::Float32
+    seed::Union{Nothing,UInt64}
     state::IdDict{Any,Any}     # tables => (state matrices, dlrm_adagrad handle)
 end
-HipADAGrad(η = 0.1, ϵ = 1e-8) = HipADAGrad(Float32(η), Float32(ϵ), IdDict{Any,Any}())
+HipADAGrad(η = 0.1, ϵ = 1e-8; seed = nothing) =
+    HipADAGrad(Float32(η), Float32(ϵ), seed === nothing ? nothing : UInt64(seed), IdDict{Any,Any}())
 
 """
-    HipRowwiseADAGrad(η = 0.1, ϵ = 1e-8)
+    HipRowwiseADAGrad(η = 0.1, ϵ = 1e-8; seed = nothing)
 
 Row-wise Adagrad: `m[r] += mean(G[:, r].^2); w[:, r] .-= η .* G[:, r] ./ (sqrt(m[r]) + ϵ)`, one fp32
 word per table row (`1 × N` per table, zero at the start): 3.5 GB for the Terabyte set's 882.8 M rows.
+`seed`: the stochastically rounded store on bf16 tables, as `HipADAGrad`'s -- with bf16 rows and this rule's word
+per row, the Adagrad that fits that set on one GPU.
 """
 mutable struct HipRowwiseADAGrad <: AbstractHipADAGrad
     eta::Float32
     epsilon::Float32
+    seed::Union{Nothing,UInt64}
     state::IdDict{Any,Any}
 end
-HipRowwiseADAGrad(η = 0.1, ϵ = 1e-8) = HipRowwiseADAGrad(Float32(η), Float32(ϵ), IdDict{Any,Any}())
+HipRowwiseADAGrad(η = 0.1, ϵ = 1e-8; seed = nothing) =
+    HipRowwiseADAGrad(Float32(η), Float32(ϵ), seed === nothing ? nothing : UInt64(seed), IdDict{Any,Any}())
 
 rowwise(::HipADAGrad) = false
 rowwise(::HipRowwiseADAGrad) = true
@@ -488,11 +504,36 @@ function adagrad_state(opt::AbstractHipADAGrad, tables::AbstractVector{<:HipEmbe
         state = [init_state(opt, t) for t in tables]
         ptrs = [m.ptr for m in state]
         out = Ref{Ptr{Cvoid}}(C_NULL)
-        check(ctx, ccall((:dlrm_adagrad_create, libdlrm), Cint,
-                         (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
-                         ctx.ptr, tableset(tables), Cint(rowwise(opt)), ptrs, out))
+        if opt.seed === nothing
+            check(ctx, ccall((:dlrm_adagrad_create, libdlrm), Cint,
+                             (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                             ctx.ptr, tableset(tables), Cint(rowwise(opt)), ptrs, out))
+        else  # (the stochastic kind: the handle owns the step)
+            check(ctx, ccall((:dlrm_adagrad_create_sr, libdlrm), Cint,
+                             (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Int64, Ref{Ptr{Cvoid}}),
+                             ctx.ptr, tableset(tables), Cint(rowwise(opt)), ptrs, reinterpret(Int64, opt.seed), out))
+        end
         (state, out[])
     end
+end
+
+"The next `update!` of `tables` with a seeded `opt` uses `step` (asynchronous, in stream order)."
+function adagrad_seek!(opt::AbstractHipADAGrad, tables::AbstractVector{<:HipEmbedding}, step::Integer)
+    opt.seed === nothing && throw(ArgumentError("adagrad_seek!: the optimizer has no seed, so no step"))
+    ctx = first(tables).data.ctx
+    check(ctx, ccall((:dlrm_adagrad_seek, libdlrm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64),
+                     ctx.ptr, adagrad_state(opt, tables)[2], reinterpret(Int64, UInt64(step))))
+    return nothing
+end
+
+"The step the next `update!` of `tables` with a seeded `opt` will use (synchronises)."
+function adagrad_step(opt::AbstractHipADAGrad, tables::AbstractVector{<:HipEmbedding})
+    opt.seed === nothing && throw(ArgumentError("adagrad_step: the optimizer has no seed, so no step"))
+    ctx = first(tables).data.ctx
+    out = Ref{UInt64}(0)
+    check(ctx, ccall((:dlrm_adagrad_step, libdlrm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{UInt64}),
+                     ctx.ptr, adagrad_state(opt, tables)[2], out))
+    return out[]
 end
 
 #####

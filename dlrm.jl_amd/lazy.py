@@ -67,11 +67,19 @@ class HipTables:
     tables takes the operator route: the pullback writes every gradient row and update! with that optimizer
     object steps every row (dlrm_sr_sgd_update), at once -- unless stochastic_step=True, the rule's fused step
     (dlrm_sr_step_bwd), which behaves as the split rule's: the pullback steps and rounds the once-hit rows and
-    update! with that same optimizer object runs or defers the apply, after which the step word advances."""
+    update! with that same optimizer object runs or defers the apply, after which the step word advances.  opt: an
+    ADAGrad or RowwiseADAGrad with a seed (the stochastic store, bfloat16 tables) takes the operator route too
+    (dlrm_adagrad_update with its handle, at once); adagrad_step=True is refused with it."""
 
-    def __init__(self, tables, *, lr=None, index_base=1, defer_update=True, opt=None, stochastic_step=False):
+    def __init__(self, tables, *, lr=None, index_base=1, defer_update=True, opt=None, stochastic_step=False,
+                 adagrad_step=None):
         self._ts = as_table_set(tables) if not isinstance(tables, EmbeddingTableSet) else tables
         self.stochastic_step = bool(stochastic_step)
+        # adagrad_step: None (the default: an Adagrad optimizer's fused step where it has one) or True, which demands it
+        if adagrad_step and not (isinstance(opt, _AdagradBase) and opt.step_keyword == "adagrad_step"):
+            raise ValueError("HipTables: adagrad_step=True is the Adagrad rules' fused step (opt=ADAGrad(eta, eps) or "
+                             "opt=RowwiseADAGrad(eta, eps)); with a seed (the stochastic store) they have the operator "
+                             "route only")
         if self.stochastic_step and not isinstance(opt, StochasticDescent):
             raise ValueError("HipTables: stochastic_step=True is the stochastic rule's fused step "
                              "(opt=StochasticDescent(eta, seed))")
@@ -80,14 +88,17 @@ class HipTables:
                             "(Descent: lr=eta)")
         # the optimizer's fused step runs these tables' steps (the stochastic rule's: with its keyword only; without,
         # the operator route: the pullback writes every dt row and update! steps every row, lr stays None)
-        self._rule_step = opt is not None and (self.stochastic_step or not isinstance(opt, StochasticDescent))
+        # (an Adagrad optimizer with a seed has no fused step: the operator route as well)
+        self._rule_step = (opt is not None and opt.step_keyword is not None and
+                           (self.stochastic_step or not isinstance(opt, StochasticDescent)))
         if self._rule_step:
             if lr is not None and float(lr) != opt.eta:
                 raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}")
             lr = opt.eta
         elif opt is not None and lr is not None:
-            raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}: without stochastic_step=True the rule "
-                             "takes the operator route, so the pullback steps no row (lr must be None)")
+            raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}: without stochastic_step=True (and with a "
+                             "seeded Adagrad optimizer) the rule takes the operator route, so the pullback steps no "
+                             "row (lr must be None)")
         if opt is not None:
             opt.check_tables(self._ts.dtype)
         self.opt = opt

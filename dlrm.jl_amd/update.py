@@ -80,7 +80,8 @@ class _StatefulOpt:
     def state_of(self, tables):
         """The state tensors of `tables` (a table set), one per table: fp32 [nrows][D] accumulators
         (ADAGrad), fp32 [nrows] row accumulators (RowwiseADAGrad) or int16 [nrows][D] low halves
-        (SplitDescent); none for StochasticDescent, whose state is the handle's step.  Write into them to
+        (SplitDescent); none for StochasticDescent, whose state is the handle's step (a seeded Adagrad optimizer has both:
+        its step is `step_of`).  Write into them to
         preset the state."""
         return self._entry(tables)[1]
 
@@ -96,22 +97,50 @@ class _StatefulOpt:
 
 
 class _AdagradBase(_StatefulOpt):
-    """Sparse Adagrad over embedding tables (dlrm_adagrad_*)."""
+    """Sparse Adagrad over embedding tables (dlrm_adagrad_*).
+
+    seed (None: round to nearest, the rule as it always was): an integer in [0, 2^64) makes the store of every written
+    weight stochastic, on bfloat16 tables only (dlrm_adagrad_create_sr).  The gradient sum, the state update and the
+    fp32 result of every element are the seedless rule's, bit for bit, and so is the state written; the bfloat16
+    stored is that result rounded up or down as StochasticDescent rounds (`sr_round` restates it), so a step below
+    half an ulp of the weight accumulates instead of vanishing.  The step is a counter on the device, per table set:
+    0 at first use, one more after every update (a captured update advances it on every replay); `seek(tables, step)`
+    sets it and `step_of(tables)` reads it (synchronising).  A seeded optimizer has no fused training step: `HotPath`
+    and `HipTables` take it on the operator route, and `adagrad_step=True` is refused with it."""
     rowwise = False
     no_atomic = "an atomic add never holds the row's whole gradient sum, which the rule squares"
     step_keyword = "adagrad_step"
     step_entry = ("dlrm_adagrad_step_bwd", "dlrm_adagrad_step_bwd_prepare")
 
-    def __init__(self, eta=0.1, eps=1e-8):
+    def __init__(self, eta=0.1, eps=1e-8, seed=None):
         super().__init__()
+        name = type(self).__name__
+        if seed is not None:
+            if isinstance(seed, bool) or not isinstance(seed, int):
+                raise TypeError(f"{name}: seed is None or an integer in [0, 2^64), not {type(seed).__name__}")
+            if not 0 <= seed < 2 ** 64:
+                raise ValueError(f"{name}: seed is None or an integer in [0, 2^64)")
+            self.step_keyword = self.step_entry = None  # (no fused step with the stochastic store: the operator route)
         self.eta = float(eta)
         self.eps = float(eps)
+        self.seed = seed
 
     def step_params(self, fixed=None):
         return fixed or (self.eta, self.eps)
 
+    def check_tables(self, dtype):
+        if self.seed is not None and dtype != torch.bfloat16:
+            raise ValueError(f"{type(self).__name__} with a seed needs bfloat16 tables (fp32: nothing to round), not {dtype}")
+
+    def _init_state(self, table):
+        self.check_tables(table.dtype)
+        return self._zero_state(table)
+
     def _create(self, ts, ptrs, out):
-        return ts.ctx.lib.dlrm_adagrad_create(ts.ctx.bind(), ts.handle, int(self.rowwise), ptrs, out)
+        lib = ts.ctx.lib
+        if self.seed is None:
+            return lib.dlrm_adagrad_create(ts.ctx.bind(), ts.handle, int(self.rowwise), ptrs, out)
+        return lib.dlrm_adagrad_create_sr(ts.ctx.bind(), ts.handle, int(self.rowwise), ptrs, _as_i64(self.seed), out)
 
     def _destroy(self, lib, handle):
         lib.dlrm_adagrad_destroy(handle)
@@ -122,24 +151,49 @@ class _AdagradBase(_StatefulOpt):
                                            ptr(idx.data), idx.itype, idx.stride, index_base, idx.B, idx.L, ptr(grad),
                                            dtype_code(grad.dtype), grad.stride(0), grad_offset, self.eta, self.eps)
 
+    def _seeded(self, what):
+        if self.seed is None:
+            raise ValueError(f"{type(self).__name__}.{what}: the optimizer has no seed, so no step (seed=... makes "
+                             "its store stochastic)")
+
+    def seek(self, tables, step):
+        """With a seed: the next update of `tables` uses `step` (asynchronous, in stream order)."""
+        self._seeded("seek")
+        ts, _, h = self._entry(tables)
+        if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
+            raise ValueError(f"{type(self).__name__}.seek: step is an integer in [0, 2^64)")
+        ts.ctx.check(ts.ctx.lib.dlrm_adagrad_seek(ts.ctx.bind(), h, _as_i64(step)))
+
+    def step_of(self, tables):
+        """With a seed: the step the next update of `tables` will use (synchronises)."""
+        self._seeded("step_of")
+        ts, _, h = self._entry(tables)
+        out = ctypes.c_uint64()
+        ts.ctx.check(ts.ctx.lib.dlrm_adagrad_step(ts.ctx.bind(), h, ctypes.byref(out)))
+        return out.value
+
     def __repr__(self):
-        return f"{type(self).__name__}({self.eta}, {self.eps})"
+        tail = "" if self.seed is None else f", seed={self.seed}"
+        return f"{type(self).__name__}({self.eta}, {self.eps}{tail})"
 
 
 class ADAGrad(_AdagradBase):
     """Flux.ADAGrad(η, ϵ): A .+= g.^2; w .-= η .* g ./ (sqrt.(A) .+ ϵ), A starting at ϵ.  On
-    embedding tables only the rows a batch touches change (an untouched row has g = 0)."""
+    embedding tables only the rows a batch touches change (an untouched row has g = 0).  seed: the stochastically
+    rounded store on bfloat16 tables (see _AdagradBase)."""
 
-    def _init_state(self, table):
+    def _zero_state(self, table):
         return torch.full(table.shape, self.eps, dtype=torch.float32, device=table.device)
 
 
 class RowwiseADAGrad(_AdagradBase):
     """Row-wise Adagrad: one fp32 accumulator per table row, m[r] += mean_c(g[r][c]^2);
-    w[r] .-= η .* g[r] ./ (sqrt(m[r]) + ϵ), m starting at 0."""
+    w[r] .-= η .* g[r] ./ (sqrt(m[r]) + ϵ), m starting at 0.  seed: the stochastically rounded store on bfloat16
+    tables (see _AdagradBase): with bfloat16 rows and this rule's one word per row, the Adagrad that fits the largest
+    table sets."""
     rowwise = True
 
-    def _init_state(self, table):
+    def _zero_state(self, table):
         return torch.zeros((table.shape[0],), dtype=torch.float32, device=table.device)
 
 

@@ -384,6 +384,43 @@ int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagrad* opt, d
                         const void* grad, int grad_dtype, int64_t grad_ld, int64_t grad_offset,
                         float lr, float eps);
 
+/* ---- sparse Adagrad with a stochastically rounded store: either rule on DLRM_BF16 tables, the
+ * written weight rounded as dlrm_sr_sgd_update rounds it (below).  Round-to-nearest drops a step of
+ * lr G / (sqrt(m) + eps) under half a bf16 ulp of the weight every time -- after a few hundred hits
+ * of a row, every Adagrad step; the stochastic store keeps it in expectation at no memory beside the
+ * rule's fp32 state.  The row-wise kind is the one that fits the largest table sets (bf16 rows plus
+ * one fp32 word per row).
+ *
+ * dlrm_adagrad_create_sr makes a dlrm_adagrad of the stochastic kind (rowwise as in
+ * dlrm_adagrad_create, the same state arrays with the same initial values) holding `seed` and one
+ * 64-bit device step word, zero at creation.  dlrm_adagrad_update with it: for every touched row,
+ * G, the state update and the fp32 result W' of every element are exactly what the plain handle's
+ * update computes before its store converts W' (the same expressions, reduction orders and
+ * hardware sqrt / rcp), the state is written with the same bits, and the element stored is
+ * sr_bf16(W', R) with dlrm_sr_sgd's R, Inf / NaN handling and Philox key / counter unchanged (key =
+ * the seed's halves, counter = (row, table << 16 | column >> 2, step lo, step hi), column c takes
+ * the low 16 bits of word c & 3).  R depends on (seed, step, table, row, column) alone, not on the
+ * indexer's form, chunk limit, parts, launch or lane.  The step word has dlrm_sr_sgd's contract:
+ * every launch of a call reads one value and a one-thread launch after the call's last adds one,
+ * in stream order (a captured update advances on every replay); it advances when the call returned
+ * DLRM_OK and launched, also when a raised bounds flag suppressed the writes, and not on an
+ * argument or state error.  dlrm_adagrad_seek / dlrm_adagrad_step set (asynchronous) and read
+ * (synchronising) the word; on a handle of dlrm_adagrad_create they return DLRM_E_ARG.
+ *
+ * Otherwise as dlrm_adagrad_update: touched rows written once, untouched rows keep their bits
+ * (weights and state), a set bounds flag leaves both unwritten, DLRM_UPDATE_PREBUILT is honoured,
+ * DLRM_UPDATE_ATOMIC returns DLRM_E_UNSUPPORTED, a split indexer whose singles are not done is
+ * taken whole.  fp32 tables return DLRM_E_ARG (nothing to round), at create and at update; more
+ * than 65536 tables or dim / 4 > 65536 returns DLRM_E_ARG at create (the counter's fields).
+ * There is no fused training step with these rules: dlrm_adagrad_step_bwd(_prepare) with such a
+ * handle returns DLRM_E_UNSUPPORTED, and dlrm_adagrad_update(PREBUILT) with one on an indexer in
+ * state DLRM_IX_SINGLES_DONE (whichever rule marked it) returns DLRM_E_STATE; neither launches,
+ * writes or moves the step word. */
+int dlrm_adagrad_create_sr(dlrm_ctx* ctx, const dlrm_tables* tables, int rowwise,
+                           float* const* state, int64_t seed, dlrm_adagrad** out);
+int dlrm_adagrad_seek(dlrm_ctx* ctx, dlrm_adagrad* opt, int64_t step);
+int dlrm_adagrad_step(dlrm_ctx* ctx, dlrm_adagrad* opt, uint64_t* out);
+
 /* ---- split-bf16 tables: update!(Descent(lr), ...) as an exact fp32 step on bf16 rows.
  * The reference names the layout (src/train/train.jl:117, `mantissa_trick`) and never builds it.
  *

@@ -6,7 +6,11 @@ workload a Descent-bf16 leg steps another bf16 copy, so the three rules of bf16 
 and SplitDescent -- are timed side by side in the same run (bf16_ratio: a leg's time to the Descent leg on bf16
 tables).  The stochastic rule moves Descent's bytes: its ratio is the cost of Philox at the write sites plus the
 one-thread launch that advances its step, and the sr-step-launch leg times such a one-thread launch alone
-(dlrm_sr_sgd_seek, the same kernel shape, in the same captured chain of 200).
+(dlrm_sr_sgd_seek, the same kernel shape, in the same captured chain of 200).  The Adagrad rules with the stochastic
+store (ADAGrad-sr, RowwiseADAGrad-sr: a seeded optimizer, dlrm_adagrad_create_sr) each step a bf16 copy too, beside
+their seedless rules on bf16 tables (on an fp32 workload the legs ADAGrad-bf16 and RowwiseADAGrad-bf16, on a bf16
+one ADAGrad and RowwiseADAGrad themselves); sr_cost_us is a stochastic leg's median over its seedless leg's on bf16
+tables, the yardstick being StochasticDescent's over Descent's from the same run.
 
 Each leg is a captured graph of 200 launches, replayed until the timed window exceeds 0.5 s; the
 legs alternate, five repeats.  One JSON line per run: per shape and leg the median / min / max us
@@ -57,6 +61,17 @@ def bench_shape(pkg, dev, name):
     sr_opt = pkg.StochasticDescent(1e-6, seed=7)
     opts["StochasticDescent"] = (sr_opt, sr, pkg.maplookup_pullback(D, sr, p, dt))
     opts["sr-step-launch"] = (sr_opt, sr, None)  # (no update: the one-thread launch alone)
+    # the Adagrad rules on bf16 tables, round to nearest and stochastic: a bf16 copy per leg
+    seedless = {}  # stochastic leg -> its seedless leg on bf16 tables
+    for name, rule in (("ADAGrad", pkg.ADAGrad), ("RowwiseADAGrad", pkg.RowwiseADAGrad)):
+        seedless[name + "-sr"] = name
+        if dtype == torch.float32:
+            c = pkg.EmbeddingTableSet([t.data.clone() for t in hi])
+            opts[name + "-bf16"] = (rule(1e-6), c, pkg.maplookup_pullback(D, c, p, dt))
+            seedless[name + "-sr"] = name + "-bf16"
+        c = pkg.EmbeddingTableSet([t.data.clone() for t in hi])
+        opts[name + "-sr"] = (rule(1e-6, seed=7), c, pkg.maplookup_pullback(D, c, p, dt))
+    seedless["StochasticDescent"] = "Descent-bf16" if dtype == torch.float32 else "Descent"
     graphs = {}
     s = torch.cuda.Stream()
     for leg, (opt, tabs, gr_views) in opts.items():
@@ -96,6 +111,9 @@ def bench_shape(pkg, dev, name):
     state_bytes = {"Descent": 0, "ADAGrad": 2 * unique * D * 4, "RowwiseADAGrad": 2 * unique * 4,
                    "SplitDescent": 2 * unique * D * 2, "Descent-bf16": 0, "StochasticDescent": 0}
     table_esize = {"SplitDescent": 2, "Descent-bf16": 2, "StochasticDescent": 2}
+    for name in ("ADAGrad", "RowwiseADAGrad"):
+        for leg in (name + "-bf16", name + "-sr"):
+            state_bytes[leg], table_esize[leg] = state_bytes[name], 2
     out = {"unique_rows": unique, "legs": {}}
     for leg in opts:
         v = us[leg]
@@ -113,6 +131,9 @@ def bench_shape(pkg, dev, name):
     b16_base = out["legs"]["Descent-bf16" if dtype == torch.float32 else "Descent"]["us_median"]
     for leg in ("StochasticDescent", "SplitDescent"):
         out["legs"][leg]["bf16_ratio"] = round(out["legs"][leg]["us_median"] / b16_base, 4)
+    for leg, ref in seedless.items():  # what the stochastic store costs each rule on bf16 tables
+        out["legs"][leg]["seedless"] = ref
+        out["legs"][leg]["sr_cost_us"] = round(out["legs"][leg]["us_median"] - out["legs"][ref]["us_median"], 3)
     return out
 
 
