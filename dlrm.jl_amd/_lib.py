@@ -23,6 +23,7 @@ UPDATE_ATOMIC, UPDATE_PREBUILT = 1, 2
 STEP_BWD_ONLY, STEP_APPLY_ONLY = 1, 2
 IX_BUILT, IX_SPLIT, IX_PREPARED, IX_SINGLES_DONE, IX_SINGLES_SPLIT = 1, 2, 4, 8, 16
 IX_SINGLES_ADAGRAD, IX_SINGLES_ROWWISE, IX_SINGLES_STOCHASTIC = 32, 64, 128
+IX_SINGLES_SR_ADAGRAD, IX_SINGLES_SR_ROWWISE = 256, 512
 COMM_ID_BYTES = 128
 
 
@@ -153,6 +154,10 @@ SIGNATURES = {
                                 _vp, _i64, _f32, _u32]),
     "dlrm_sr_step_bwd_prepare": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _vp,
                                         _i64, _vp, _i64, _f32, _vp, _vp, _u32]),
+    "dlrm_sr_adagrad_step_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _vp,
+                                        _i64, _vp, _i64, _f32, _f32, _u32]),
+    "dlrm_sr_adagrad_step_bwd_prepare": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _i64,
+                                                _i32, _vp, _i64, _vp, _i64, _f32, _f32, _vp, _vp, _u32]),
 }
 
 _lib = None

@@ -87,7 +87,7 @@ struct RuleDesc {
                             // it has one
     unsigned bit;           // of dlrm_indexer_state, when its step backward stepped a build's once-hit rows
     ApplyFn* apply;         // the update's apply launch
-    ApplyFn* step_apply;    // the training step's; NULL: the rule has no fused step (its entry point refuses the handle)
+    ApplyFn* step_apply;    // the training step's
 };
 static const RuleDesc kRules[kNumRules] = {
     {"dlrm_sgd_update", "dlrm_step_bwd", "Descent", nullptr, nullptr, nullptr, 0u, launch_sgd_apply, launch_sgd_apply},
@@ -103,14 +103,14 @@ static const RuleDesc kRules[kNumRules] = {
     {"dlrm_sr_sgd_update", "dlrm_sr_step_bwd", "the stochastic rule", "the optimizer was",
      "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule rounds each row's complete step once",
      DLRM_IX_SINGLES_STOCHASTIC, launch_sr_sgd_apply, launch_sr_step_apply},
-    // (the Adagrad rules of a dlrm_adagrad_create_sr handle: no step backward, so no mark of their own and no build of
-    // another's mark to complete)
-    {"dlrm_adagrad_update", "dlrm_adagrad_step_bwd", "the stochastic element-wise Adagrad rule", "the optimizer state was",
-     "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule needs each row's complete sum", 0u,
-     launch_sr_adagrad_apply, nullptr},
-    {"dlrm_adagrad_update", "dlrm_adagrad_step_bwd", "the stochastic row-wise Adagrad rule", "the optimizer state was",
-     "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule needs each row's complete sum", 0u,
-     launch_sr_rowwise_adagrad_apply, nullptr},
+    // (the Adagrad rules of a dlrm_adagrad_create_sr handle: a step backward of their own, dlrm_sr_adagrad_step_bwd --
+    // dlrm_adagrad_step_bwd refuses the handle)
+    {"dlrm_adagrad_update", "dlrm_sr_adagrad_step_bwd", "the stochastic element-wise Adagrad rule", "the optimizer state was",
+     "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule needs each row's complete sum",
+     DLRM_IX_SINGLES_SR_ADAGRAD, launch_sr_adagrad_apply, launch_sr_adagrad_step_apply},
+    {"dlrm_adagrad_update", "dlrm_sr_adagrad_step_bwd", "the stochastic row-wise Adagrad rule", "the optimizer state was",
+     "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule needs each row's complete sum",
+     DLRM_IX_SINGLES_SR_ROWWISE, launch_sr_rowwise_adagrad_apply, launch_sr_rowwise_adagrad_step_apply},
 };
 
 // The rule of a call, from its handle and scalars
@@ -1110,12 +1110,13 @@ static int check_rule(dlrm_ctx* ctx, const dlrm_tables* tb, const BoundRule& r, 
 
 // Who may complete whose backward.  A split backward stepped the build's once-hit rows with its rule and left their dt
 // rows unwritten: only the same rule finishes what it started (dlrm_*_update(PREBUILT) and dlrm_*step_bwd(APPLY_ONLY)
-// alike) -- another rule's rows hold another step -- and for the stochastic rule only the same handle: another one has
-// another seed or step.
+// alike) -- another rule's rows hold another step -- and for the stochastic rule and the seeded Adagrad rules only the
+// same handle: another one has another seed or step (and, Adagrad, another state).
 static int check_completes(dlrm_ctx* ctx, const dlrm_indexer* ix, const BoundRule& r, const char* fn, const char* mode) {
     if (!ix->singles_done) return DLRM_OK;
-    const bool same_rule = ix->singles_rule == r.kind;  // (never a rule without a step backward: it marks no build)
-    if (same_rule && (r.kind != kRuleStochastic || ix->singles_handle == r.handle)) return DLRM_OK;
+    const bool same_rule = ix->singles_rule == r.kind;
+    const bool seeded = r.kind == kRuleStochastic || r.kind == kRuleStochasticAdagrad || r.kind == kRuleStochasticRowwise;
+    if (same_rule && (!seeded || ix->singles_handle == r.handle)) return DLRM_OK;
     const RuleDesc& by = kRules[ix->singles_rule];
     return ctx_fail(ctx, DLRM_E_STATE, "%s%s: a split backward (%s) already stepped this build's once-hit rows with %s%s",
                     fn, mode, by.step_fn, by.name, same_rule ? " of another handle" : "");
@@ -1515,6 +1516,23 @@ int dlrm_sr_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_sr_sgd* op, dl
                              dlrm_indexer* next, const void* next_indices, unsigned flags) {
     CHECK_ARG(ctx && tb && op && ix, "dlrm_sr_step_bwd_prepare: null ctx/tables/optimizer/indexer");
     return step_bwd_prepare_impl(ctx, tb, ix, bind_rule(op, lr), STEP_PASS, next, next_indices, flags);
+}
+// (a seeded handle's pair: dlrm_adagrad_step_bwd's refusal of such a handle stays as it is)
+int dlrm_sr_adagrad_step_bwd(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, STEP_ARGS, float lr,
+                             float eps, unsigned flags) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_sr_adagrad_step_bwd: null ctx/tables/optimizer/indexer");
+    CHECK_ARG(op->stochastic, "dlrm_sr_adagrad_step_bwd: the handle has no seed (dlrm_adagrad_create_sr makes one that "
+              "has; dlrm_adagrad_step_bwd takes this one)");
+    return step_bwd_impl(ctx, tb, ix, bind_rule(op, lr, eps), STEP_PASS, flags, nullptr);
+}
+
+int dlrm_sr_adagrad_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, STEP_ARGS,
+                                     float lr, float eps, dlrm_indexer* next, const void* next_indices,
+                                     unsigned flags) {
+    CHECK_ARG(ctx && tb && op && ix, "dlrm_sr_adagrad_step_bwd_prepare: null ctx/tables/optimizer/indexer");
+    CHECK_ARG(op->stochastic, "dlrm_sr_adagrad_step_bwd_prepare: the handle has no seed (dlrm_adagrad_create_sr makes "
+              "one that has; dlrm_adagrad_step_bwd_prepare takes this one)");
+    return step_bwd_prepare_impl(ctx, tb, ix, bind_rule(op, lr, eps), STEP_PASS, next, next_indices, flags);
 }
 #undef STEP_ARGS
 #undef STEP_PASS

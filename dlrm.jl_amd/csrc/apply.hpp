@@ -427,7 +427,10 @@ struct SrWord {
 
 struct StochasticAdagrad : Adagrad, SrWord {
     static constexpr bool kStochastic = true;
-    static constexpr bool kCarriesBuild = false;  // (no fused training step with the rule: MODE 0 / 1 only)
+    // MODE >= 2 over the training step's fp32 dt, in a unit of its own (sr_adagrad_step.hip), so sr_adagrad.hip stays
+    // the MODE 0 / 1 unit it was
+    static constexpr bool kCarriesBuild = true;
+    static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = false;     // fp32 tables: nothing to round
     // the parent's count (the Philox rounds come at the write, after the loads) -- but for fp32 gradient rows of 16
     // vectors (D = 64), whose MODE 1 kernel spilt 2 registers with it: half as many there (as StochasticDescent)
@@ -450,7 +453,8 @@ struct StochasticAdagrad : Adagrad, SrWord {
 
 struct StochasticRowwiseAdagrad : RowwiseAdagrad, SrWord {
     static constexpr bool kStochastic = true;
-    static constexpr bool kCarriesBuild = false;
+    static constexpr bool kCarriesBuild = true;  // (sr_adagrad_rowwise_step.hip, as StochasticAdagrad)
+    static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = false;
     // (the parent's count, and half of it for fp32 gradient rows of 16 vectors: as StochasticAdagrad)
     template <typename G> static constexpr int singles_ppg() {

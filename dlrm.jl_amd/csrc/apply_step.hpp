@@ -1,12 +1,13 @@
 // apply_step.hpp -- the apply launch of the training step with the split rule (dlrm_split_step_bwd[_prepare]), a
-// sparse Adagrad rule (dlrm_adagrad_step_bwd[_prepare]) or the stochastic rule (dlrm_sr_step_bwd[_prepare]) when it
-// carries the next batch's split indexer build.
+// sparse Adagrad rule (dlrm_adagrad_step_bwd[_prepare]), the stochastic rule (dlrm_sr_step_bwd[_prepare]) or a seeded
+// Adagrad rule (dlrm_sr_adagrad_step_bwd[_prepare]) when it carries the next batch's split indexer build.
 //
 // apply_kernel.hpp's launch in MODE 2 / 3 / 5 (the build's workgroups first, then chunks and hot slices; no
 // once-hit items: the step backward stepped those rows) with the rule at its write sites.  Only what the step
 // needs is instantiated: fp32 (a rule with kF32Tables) and bf16 tables, the step's fp32 dt rows.  MODE 0 and 1 stay
 // in split_sgd.hip, adagrad.hip, adagrad_rowwise.hip and sr_sgd.hip; split_step.hip, adagrad_step.hip,
-// adagrad_rowwise_step.hip and sr_step.hip include this, one rule each, and compile beside update.hip.
+// adagrad_rowwise_step.hip, sr_step.hip, sr_adagrad_step.hip and sr_adagrad_rowwise_step.hip include this, one rule
+// each, and compile beside update.hip.
 #pragma once
 #include "apply_kernel.hpp"
 

@@ -406,17 +406,19 @@ struct PrepArgs;
 //  - the update's (update.hip, split_sgd.hip, adagrad.hip, adagrad_rowwise.hip, sr_sgd.hip): MODE 0 / 1, any gradient
 //    type and L; only Descent's takes `prep` (the others' callers pass NULL).  The stochastic rule's ends with the
 //    one-thread advance of the step word (nothing to launch: it leaves the word alone);
-//  - the training step's (split_step.hip, adagrad_step.hip, adagrad_rowwise_step.hip, sr_step.hip; Descent's is its
-//    update's): the step's fp32 dt rows (gdtype = DLRM_F32, L = 1); with `prep` and no once-hit items the next
-//    batch's build rides on the launch (MODE 2 / 3 / 5) where the shape's vector kernel exists, otherwise the
-//    update's launch and, with `prep`, the build's own.  The stochastic rule's advances the step word once either way,
-//    after the launch that read it.
+//  - the training step's (split_step.hip, adagrad_step.hip, adagrad_rowwise_step.hip, sr_step.hip, sr_adagrad_step.hip,
+//    sr_adagrad_rowwise_step.hip; Descent's is its update's): the step's fp32 dt rows (gdtype = DLRM_F32, L = 1);
+//    with `prep` and no once-hit items the next batch's build rides on the launch (MODE 2 / 3 / 5) where the shape's
+//    vector kernel exists, otherwise the update's launch and, with `prep`, the build's own.  The stochastic rule's and
+//    the seeded Adagrad rules' advance the step word once either way, after the launch that read it.
 typedef int ApplyFn(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T, int D, int tdtype,
                     int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
                     const BoundRule& rule, const SinglesArgs& singles, const PrepArgs* prep);
 ApplyFn launch_sgd_apply, launch_split_sgd_apply, launch_adagrad_apply, launch_rowwise_adagrad_apply, launch_sr_sgd_apply;
 ApplyFn launch_sr_adagrad_apply, launch_sr_rowwise_adagrad_apply;  // (sr_adagrad.hip, sr_adagrad_rowwise.hip: as launch_sr_sgd_apply)
 ApplyFn launch_split_step_apply, launch_adagrad_step_apply, launch_rowwise_adagrad_step_apply, launch_sr_step_apply;
+// (sr_adagrad_step.hip, sr_adagrad_rowwise_step.hip)
+ApplyFn launch_sr_adagrad_step_apply, launch_sr_rowwise_adagrad_step_apply;
 // the stochastic rule's step word, by one-thread launches on the context's stream (sr_sgd.hip)
 int launch_sr_step_set(dlrm_ctx* ctx, uint64_t* step, uint64_t value);
 int launch_sr_step_advance(dlrm_ctx* ctx, uint64_t* step);  // step += 1

@@ -389,6 +389,19 @@ struct StochasticStepUpdate : StepUpdate {
     static constexpr const char* kName = "sr_step_bwd";
 };
 
+// The same for the sparse Adagrad rules with the stochastic store on bf16 tables (apply.hpp StochasticAdagrad /
+// StochasticRowwiseAdagrad; dlrm_sr_adagrad_step_bwd): AdagradStepUpdate's arithmetic and state write, the weights
+// stored by SrWord::store -- sr_bf16(W', R), R as the apply's once-hit item draws it, generated at the write.  The
+// parent's fields, then the seed's halves and the pointer to the handle's step word (read once per workgroup).  A
+// struct of its own again.
+template <bool RW>
+struct StochasticAdagradStepUpdate : AdagradStepUpdate<RW> {
+    uint32_t k0, k1;       // the seed's halves
+    const uint64_t* step;  // the handle's step word
+    static constexpr bool kStochastic = true;
+    static constexpr const char* kName = "sr_adagrad_step_bwd";
+};
+
 // the d = 128 rule kernels' per-table pointers to the second stream in LDS, and the row-wise two-wave form's
 // exchange of each wave's sums of squares (function-local arrays: only their instantiations hold them)
 template <typename E, int N> __device__ __forceinline__ E** rule_tab() {
@@ -931,7 +944,9 @@ __device__ __forceinline__ void bwd_split_tracked(int F, int B, const float* __r
 // the split rule's on bf16 tables, its branches `if constexpr (SU::kSplit)`; AdagradStepUpdate (dlrm_adagrad_step_bwd)
 // the sparse Adagrad rules' on fp32 and bf16 tables, `if constexpr (AG == 1)` the element-wise rule and `(AG == 2)`
 // the row-wise one; StochasticStepUpdate (dlrm_sr_step_bwd) the stochastic rule's on bf16 tables, `if constexpr
-// (SU::kStochastic)`: Descent's write with the rule's store.  The rules other than Descent exist in the step's
+// (SU::kStochastic)`: Descent's write with the rule's store; StochasticAdagradStepUpdate (dlrm_sr_adagrad_step_bwd) the
+// seeded Adagrad rules' on bf16 tables: the `AG` branches, ending in SrWord's store.
+// The rules other than Descent exist in the step's
 // default geometries only, NB = 1 and 2
 // (step_bwd_form below).  (The body stays the kernel's own text: as an inlined function template it no longer
 // compiled to the same code.)
@@ -1034,9 +1049,13 @@ __global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) vo
     if (su.single && blockIdx.x == 0 && threadIdx.x == 0) snapshot_error(su.err, frozen ? 1u : 0u);
     // the stochastic rule with the step word's value: read once per workgroup, into two scalars
     StochasticDescent sr{};
-    if constexpr (SU::kStochastic) {
+    SrWord sw{};  // (the seeded Adagrad rules: the same word, their store)
+    if constexpr (SU::kStochastic && AG == 0) {
         sr = StochasticDescent{su.lr, su.k0, su.k1, su.step, 0u, 0u};
         sr.load_step();
+    } else if constexpr (SU::kStochastic) {
+        sw = SrWord{su.k0, su.k1, su.step, 0u, 0u};
+        sw.load_step();
     }
     if (tdl_ok) {
         tds[threadIdx.x] = tdl;
@@ -1221,7 +1240,9 @@ __global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) vo
             // columns (8 columns per lane: each at its write), the row-wise rule's word
             // (with up to 16 features the state is loaded at each row's write instead: four in flight took the
             // NB = 1 forms below Descent's 8 waves per SIMD)
-            constexpr bool ST4 = NB > 1 && CPL == 4;
+            // (the seeded row-wise rule's one-wave form too: four words in flight beside the Philox rounds spilt 3
+            // registers at its 128)
+            constexpr bool ST4 = NB > 1 && CPL == 4 && !(SU::kStochastic && AG == 2 && WPS == 1);
             // row-wise: the four tile rows' sums of squares of G = 0 + g, in the order of the apply's once-hit item
             // (apply.hpp run_singles, fp32 gradient rows: apply lane v holds columns 4v..4v+3) -- a lane's fma
             // chain from 0 over four columns in column order, then the xor butterfly over the row's lanes from
@@ -1347,6 +1368,10 @@ __global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) vo
 #pragma unroll
                             for (int e = 0; e < CPL; e += 4)
                                 stg_nt<f32x4_t>(srow + e, f32x4_t{av[e], av[e + 1], av[e + 2], av[e + 3]});
+                            if constexpr (SU::kStochastic)  // (W' as the parent makes it, the rule's store)
+                                sw.template store<CPL>((uint16_t*)tds[f - 1].data + (int64_t)urow[I][r] * d + n0, f - 1,
+                                                       urow[I][r], n0, tw);
+                            else
                             store_row<T, CPL, true>((T*)tds[f - 1].data + (int64_t)urow[I][r] * d, n0, tw);
                         } else if constexpr (AG == 2) {
                             // m += ss / D, w -= (lr / (sqrt(m) + eps)) G: apply.hpp's helpers, one lane stores m
@@ -1358,6 +1383,10 @@ __global__ __launch_bounds__(64 * WPS * SPB, CPL == 8 ? 3 : (NB > 2 ? 2 : 4)) vo
                             const float sc = rowwise_scale(su.lr, su.eps, m);
 #pragma unroll
                             for (int e = 0; e < CPL; ++e) wv[e] = __builtin_fmaf(-sc, 0.0f + v[e], tw[e]);
+                            if constexpr (SU::kStochastic)
+                                sw.template store<CPL>((uint16_t*)tds[f - 1].data + (int64_t)urow[I][r] * d + n0, f - 1,
+                                                       urow[I][r], n0, wv);
+                            else
                             store_row<T, CPL, true>((T*)tds[f - 1].data + (int64_t)urow[I][r] * d, n0, wv);
                             if (c == 0 && h == 0) stg<float>(st_base(r) + urow[I][r], m);
                         } else if constexpr (SU::kStochastic) {
@@ -1740,6 +1769,7 @@ int launch_step_fwd(dlrm_ctx* ctx, const TableDesc* tabs, bool tabs_aligned16, i
 // the kRule* of a StepUpdate type
 template <typename SU>
 constexpr int rule_of() {
+    if (SU::kStochastic && SU::kAdagrad != 0) return SU::kAdagrad == 2 ? kRuleStochasticRowwise : kRuleStochasticAdagrad;
     return SU::kSplit ? kRuleSplit
                       : (SU::kStochastic ? kRuleStochastic
                                          : (SU::kAdagrad == 2 ? kRuleRowwise : (SU::kAdagrad == 1 ? kRuleAdagrad : kRuleDescent)));
@@ -1810,6 +1840,7 @@ int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, con
     const BwdArgs a{d, T_ + 1, B, dout, dout_ld, nullptr, 0, dx, dt, dx_ld, dt_ld, ga, x, x_ld};
     const StepUpdate su{ix.single, ix.cap, r.lr, ctx_error_word(ctx)};
     float* const* const state = (float* const*)r.state;
+    const uint32_t k0 = (uint32_t)r.seed, k1 = (uint32_t)(r.seed >> 32);
     const auto run = [&](auto e, const auto& rule) { return launch_step_bwd_rule<decltype(e)>(ctx, p, a, rule); };
     switch (r.kind) {
         case kRuleSplit: return run(uint16_t{}, SplitStepUpdate{su, (uint16_t* const*)r.state});
@@ -1822,6 +1853,11 @@ int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, con
             return p.f32 ? run(float{}, AdagradStepUpdate<true>{su, state, r.eps})
                          : run(uint16_t{}, AdagradStepUpdate<true>{su, state, r.eps});
         default: return p.f32 ? run(float{}, su) : run(uint16_t{}, su);
+        // (the seeded Adagrad rules last: their kernels are emitted behind every other of the unit)
+        case kRuleStochasticAdagrad:
+            return run(uint16_t{}, StochasticAdagradStepUpdate<false>{{su, state, r.eps}, k0, k1, r.step});
+        case kRuleStochasticRowwise:
+            return run(uint16_t{}, StochasticAdagradStepUpdate<true>{{su, state, r.eps}, k0, k1, r.step});
     }
 }
 

@@ -84,6 +84,13 @@ constexpr bool step_bwd_form(int rule, bool f32, int NB, int WPS, int CPL, int S
     if (descent) return true;
     if (CPL == 8 && NB == 1) return false;
     if (rule == kRuleSplit || rule == kRuleStochastic) return !f32;
+    // the seeded Adagrad rules (dlrm_sr_adagrad_step_bwd): their parents' forms on bf16 tables, but the two that the
+    // Philox rounds at the write take below the parent -- the row-wise 8-column form (the
+    // parent sits at the form's 168 VGPRs: 8 of them spilt) and the element-wise one-wave form with up to 16 features
+    // (70 VGPRs against 63: 7 waves per SIMD against 8); those shapes keep the two-wave form or the gather backward
+    if (rule == kRuleStochasticRowwise) return !f32 && CPL == 4 && step_bwd_form(kRuleRowwise, false, NB, WPS, CPL, SPB);
+    if (rule == kRuleStochasticAdagrad)
+        return !f32 && !(NB == 1 && WPS == 1) && step_bwd_form(kRuleAdagrad, false, NB, WPS, CPL, SPB);
     return rule == kRuleRowwise ? NB == 2 : !(NB == 1 && WPS == 1 && f32);
 }
 
@@ -168,7 +175,8 @@ inline InteractPlan plan_interact(InteractSite site, const InteractShape& s, con
         // dispatch_apply); the any-D kernels sum a row's squares in column order, which no lane layout here reproduces.
         const bool forms = !k.bwd_nosplit && d_split;
         if (!descent && rule != kRuleSplit && !forms) return refuse();
-        if (rule == kRuleRowwise && !(d >= 8 && (d & (d - 1)) == 0)) return refuse();
+        const bool rowwise = rule == kRuleRowwise || rule == kRuleStochasticRowwise;
+        if (rowwise && !(d >= 8 && (d & (d - 1)) == 0)) return refuse();
         p.f32 = p.f32 && rule != kRuleSplit;
         p.gather = true;
         if (!forms) {  // one super-block of T rows in flight: two (the gather backward's choice) spill here

@@ -44,9 +44,16 @@ step pair with that rule (dlrm_step_fwd, then dlrm_adagrad_step_bwd / dlrm_adagr
 rows and their state are stepped inside the backward, only the repeated rows' dt rows are written, and
 `pipeline` "apply" / "side" work as they do for Descent.  Tables and state end up bit for bit what the
 operator path gives.  Opt-in again: without the keyword the Adagrad rules keep the operator path.  With a seed (`ADAGrad(η, ε, seed=s)`,
-`RowwiseADAGrad(η, ε, seed=s)`: the stochastically rounded store, bfloat16 tables) an Adagrad optimizer has the operator
-path only (dlrm_adagrad_update(PREBUILT) and the one-thread advance of its step): `adagrad_step=True` and `pipeline`
-are refused with it.
+`RowwiseADAGrad(η, ε, seed=s)`: the stochastically rounded store, bfloat16 tables) an Adagrad optimizer takes the
+operator path (dlrm_adagrad_update(PREBUILT) and the one-thread advance of its step) and `adagrad_step=True` and
+`pipeline` are refused with it -- unless `sr_adagrad_step=True` (below).
+
+`sr_adagrad_step=True` with `opt=ADAGrad(η, ε, seed=s)` or `opt=RowwiseADAGrad(η, ε, seed=s)` on bfloat16 tables: the
+fused step pair with that rule (dlrm_step_fwd, then dlrm_sr_adagrad_step_bwd / dlrm_sr_adagrad_step_bwd_prepare):
+once-hit rows and their state are stepped inside the backward and the weights stochastically rounded there, only the
+repeated rows' dt rows are written, and `pipeline` "apply" / "side" work as under `adagrad_step=True`.  The backward
+and the apply read one value of the optimizer's step word, which advances after the apply; tables and state end up
+bit for bit what the operator path gives from the same step.
 
 `stochastic_step=True` with `opt=StochasticDescent(η, seed)` on bfloat16 tables: the fused step pair with that rule
 (dlrm_step_fwd, then dlrm_sr_step_bwd / dlrm_sr_step_bwd_prepare): once-hit rows are stepped and stochastically
@@ -71,7 +78,8 @@ from .update import SparseIndexer, _StatefulOpt
 class HotPath:
     def __init__(self, tables, batch, lookups=1, *, lr=0.1, index_base=0, deterministic=True,
                  overlap_indexer=None, pad_to=1, fused=True, materialize_ys=None, pipeline=False, chunk=None,
-                 parts=None, opt=None, fused_step=False, adagrad_step=False, stochastic_step=False):
+                 parts=None, opt=None, fused_step=False, adagrad_step=False, stochastic_step=False,
+                 sr_adagrad_step=False):
         if opt is not None and not isinstance(opt, _StatefulOpt):
             raise TypeError("HotPath: opt is an ADAGrad, RowwiseADAGrad, SplitDescent or StochasticDescent "
                             "(None: Descent(lr))")
@@ -82,16 +90,18 @@ class HotPath:
         # The optimizer's fused step pair (its step_entry) is opt-in by the optimizer's own keyword (its step_keyword);
         # without it opt= takes the operator route.  Any other rule's keyword is refused.
         given = {k for k, v in (("fused_step", fused_step), ("adagrad_step", adagrad_step),
-                                ("stochastic_step", stochastic_step)) if v}
-        own = None if opt is None else opt.step_keyword
+                                ("stochastic_step", stochastic_step), ("sr_adagrad_step", sr_adagrad_step)) if v}
+        own = None if opt is None else (opt.step_keyword or opt.sr_step_keyword)
         if given - {own}:
             raise ValueError(f"HotPath: {' / '.join(sorted(given - {own}))}=True is another rule's fused step: the split "
                              "rule's is fused_step=True (opt=SplitDescent(eta)), the Adagrad rules' adagrad_step=True "
                              "(opt=ADAGrad(eta, eps) or opt=RowwiseADAGrad(eta, eps)), the stochastic rule's "
-                             "stochastic_step=True (opt=StochasticDescent(eta, seed)); Descent(lr) is fused without a "
-                             "keyword, without its keyword a rule takes the operator route, and an Adagrad optimizer "
-                             "with a seed (the stochastic store) has that route only")
-        self._rule_step = bool(given)  # this engine runs opt's fused step (split_step, adagrad_step, stochastic_step)
+                             "stochastic_step=True (opt=StochasticDescent(eta, seed)), an Adagrad optimizer's with a "
+                             "seed (the stochastic store) sr_adagrad_step=True (opt=ADAGrad(eta, eps, seed=s) or "
+                             "opt=RowwiseADAGrad(eta, eps, seed=s)); Descent(lr) is fused without a keyword, and without "
+                             "its keyword a rule takes the operator route")
+        # this engine runs opt's fused step (split_step, adagrad_step, stochastic_step, sr_adagrad_step)
+        self._rule_step = bool(given)
         self.rule_params = None
         if opt is not None:
             opt.check_tables(self.ts.dtype)
@@ -182,6 +192,7 @@ class HotPath:
     split_step = property(lambda self: self._rule_step and self.opt.step_keyword == "fused_step")
     adagrad_step = property(lambda self: self._rule_step and self.opt.step_keyword == "adagrad_step")
     stochastic_step = property(lambda self: self._rule_step and self.opt.step_keyword == "stochastic_step")
+    sr_adagrad_step = property(lambda self: self._rule_step and self.opt.sr_step_keyword == "sr_adagrad_step")
 
     # -- pieces --------------------------------------------------------------------------
     def _check(self, rc):
@@ -262,12 +273,14 @@ class HotPath:
         (flags: _lib.STEP_BWD_ONLY / STEP_APPLY_ONLY run one of its two launches).  fused_step:
         dlrm_split_step_bwd, the same with the split rule and the optimizer's eta; adagrad_step:
         dlrm_adagrad_step_bwd, with the optimizer's rule, eta and eps; stochastic_step: dlrm_sr_step_bwd, with the
-        optimizer's eta, seed and step word (advanced after the launch that runs the apply)."""
+        optimizer's eta, seed and step word (advanced after the launch that runs the apply); sr_adagrad_step:
+        dlrm_sr_adagrad_step_bwd, with the seeded optimizer's rule, eta, eps, seed and step word."""
         h = self.ctx.bind()
         x = self._fwd_x if x is None else x
         idx = self._fwd_idx if idx is None else idx
         if self._rule_step:  # the optimizer's pair, handle and scalars (rule_params: an owner's, fixed for both launches)
-            entry, head, params = self.opt.step_entry, (self.opt.handle_of(self.ts),), self.opt.step_params(self.rule_params)
+            entry = self.opt.step_entry or self.opt.sr_step_entry
+            head, params = (self.opt.handle_of(self.ts),), self.opt.step_params(self.rule_params)
         else:
             entry, head, params = ("dlrm_step_bwd", "dlrm_step_bwd_prepare"), (), (self.lr,)
         args = (h, self.ts.handle, *head, self.indexer.handle, ptr(idx.data), idx.itype, idx.stride, self.index_base,

@@ -20,7 +20,9 @@
 # dlrm_split_step_bwd / dlrm_split_step_bwd_prepare; `Context(0; fused = true, adagrad = HipADAGrad(η, ϵ))` or
 # `adagrad = HipRowwiseADAGrad(η, ϵ)` with that Adagrad rule, through dlrm_adagrad_step_bwd / _prepare;
 # `Context(0; fused = true, stochastic = HipStochasticDescent(η; seed))` with the stochastic rule on 2-byte tables,
-# through dlrm_sr_step_bwd / dlrm_sr_step_bwd_prepare.)
+# through dlrm_sr_step_bwd / dlrm_sr_step_bwd_prepare; `Context(0; fused = true, sr_adagrad = HipADAGrad(η, ϵ; seed))` or
+# `sr_adagrad = HipRowwiseADAGrad(η, ϵ; seed)` with that seeded Adagrad rule on 2-byte tables, through
+# dlrm_sr_adagrad_step_bwd / dlrm_sr_adagrad_step_bwd_prepare.)
 #
 # and `_Train.train!` / `DLRMModel` stay unchanged.  Dense inputs x (bottom-MLP output) and the
 # interaction output cross PCIe here because the MLPs stay on the CPU in the reference; the
@@ -67,8 +69,13 @@ mutable struct Context
     # stochastic (fused): a HipStochasticDescent likewise (dlrm_sr_step_bwd): the pullback steps and rounds the
     # once-hit rows, update! with that same optimizer runs or defers the apply, after which its step word advances
     stochastic::Any
+    # sr_adagrad (fused): a HipADAGrad or HipRowwiseADAGrad with a seed (the stochastic store on 2-byte tables): kept in
+    # `adagrad` (state, η, ϵ and update!'s checks are that keyword's), this flag selecting dlrm_sr_adagrad_step_bwd --
+    # the pullback steps the once-hit rows and their state and rounds their weights, the step word advances after the apply
+    sr_adagrad::Bool
     function Context(device::Integer; stream::Ptr{Cvoid} = C_NULL, fused::Bool = false, lr = nothing,
-                     defer_update::Bool = true, split = nothing, adagrad = nothing, stochastic = nothing)
+                     defer_update::Bool = true, split = nothing, adagrad = nothing, stochastic = nothing,
+                     sr_adagrad = nothing)
         out = Ref{Ptr{Cvoid}}(C_NULL)
         rc = ccall((:dlrm_ctx_create, libdlrm), Cint, (Cint, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), device, stream, out)
         rc == 0 || throw(DLRMError(rc, "dlrm_ctx_create"))
@@ -78,8 +85,15 @@ mutable struct Context
         adagrad === nothing || split === nothing ||
             throw(ArgumentError("Context: one rule steps the tables, split = or adagrad ="))
         adagrad === nothing || adagrad.seed === nothing ||
-            throw(ArgumentError("Context: adagrad = with a seed: the stochastic store has no fused step " *
-                                "(update! with that optimizer takes the operator route)"))
+            throw(ArgumentError("Context: adagrad = with a seed: the stochastic store's fused step is sr_adagrad = " *
+                                "(without it update! with that optimizer takes the operator route)"))
+        sr_adagrad === nothing || (split === nothing && adagrad === nothing && stochastic === nothing) ||
+            throw(ArgumentError("Context: one rule steps the tables, split =, adagrad =, stochastic = or sr_adagrad ="))
+        sr_adagrad === nothing || (sr_adagrad isa AbstractHipADAGrad && sr_adagrad.seed !== nothing) ||
+            throw(ArgumentError("Context: sr_adagrad = HipADAGrad(η, ϵ; seed) or HipRowwiseADAGrad(η, ϵ; seed): the " *
+                                "seedless rules' fused step is adagrad ="))
+        seeded = sr_adagrad !== nothing
+        seeded && (adagrad = sr_adagrad)
         adagrad === nothing || lr === nothing || Float32(lr) == adagrad.eta ||
             throw(ArgumentError("Context: lr = $lr beside adagrad = $(nameof(typeof(adagrad)))($(adagrad.eta), …)"))
         adagrad === nothing || (lr = adagrad.eta)
@@ -89,7 +103,7 @@ mutable struct Context
             throw(ArgumentError("Context: lr = $lr beside stochastic = HipStochasticDescent($(stochastic.eta))"))
         stochastic === nothing || (lr = stochastic.eta)
         ctx = new(out[], fused, lr === nothing ? nothing : Float32(lr), defer_update, split, adagrad,
-                  adagrad === nothing ? nothing : Float32(adagrad.epsilon), stochastic)
+                  adagrad === nothing ? nothing : Float32(adagrad.epsilon), stochastic, seeded)
         finalizer(c -> ccall((:dlrm_ctx_destroy, libdlrm), Cint, (Ptr{Cvoid},), c.ptr), ctx)
         return ctx
     end
@@ -657,7 +671,9 @@ end
 # The training step's backward / apply launches of a fused step `st` (dlrm_step_bwd and _prepare), or, on a
 # context built with `split = HipSplitDescent(η)`, the split rule's (dlrm_split_step_bwd and _prepare), or, with
 # `adagrad = HipADAGrad(η, ϵ) | HipRowwiseADAGrad(η, ϵ)`, that rule's (dlrm_adagrad_step_bwd and _prepare), or, with
-# `stochastic = HipStochasticDescent(η; seed)`, the stochastic rule's (dlrm_sr_step_bwd and _prepare).
+# `stochastic = HipStochasticDescent(η; seed)`, the stochastic rule's (dlrm_sr_step_bwd and _prepare), or, with
+# `sr_adagrad = HipADAGrad(η, ϵ; seed) | HipRowwiseADAGrad(η, ϵ; seed)`, that seeded rule's (dlrm_sr_adagrad_step_bwd and
+# _prepare: dlrm_adagrad_step_bwd's arguments).
 function _step_bwd(ctx, st, delta_ld, flags)
     d, B = size(st.x)
     if ctx.stochastic !== nothing
@@ -677,6 +693,15 @@ function _step_bwd(ctx, st, delta_ld, flags)
                      ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
                      st.x.ptr, d, st.delta.ptr, delta_ld, st.padding, st.dx.ptr, d, st.dt.ptr,
                      size(st.dt, 1), ctx.lr, flags)
+    end
+    if ctx.sr_adagrad
+        _, h = adagrad_state(ctx.adagrad, st.tables)
+        return ccall((:dlrm_sr_adagrad_step_bwd, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid}, Int64,
+                      Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cfloat, Cuint),
+                     ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
+                     st.x.ptr, d, st.delta.ptr, delta_ld, st.padding, st.dx.ptr, d, st.dt.ptr,
+                     size(st.dt, 1), ctx.lr, ctx.eps, flags)
     end
     if ctx.adagrad !== nothing
         _, h = adagrad_state(ctx.adagrad, st.tables)
@@ -715,6 +740,16 @@ function _step_bwd_prepare(ctx, st, nix, next, flags)
                      ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
                      st.x.ptr, d, st.delta.ptr, size(st.delta, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
                      size(st.dt, 1), ctx.lr, nix.ptr, next.data.ptr, flags)
+    end
+    if ctx.sr_adagrad
+        _, h = adagrad_state(ctx.adagrad, st.tables)
+        return ccall((:dlrm_sr_adagrad_step_bwd_prepare, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Ptr{Cvoid},
+                      Int64, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cfloat,
+                      Ptr{Cvoid}, Ptr{Cvoid}, Cuint),
+                     ctx.ptr, tableset(st.tables), h, st.ix.ptr, st.idx.data.ptr, DLRM_I32, st.idx.batch, 1, B,
+                     st.x.ptr, d, st.delta.ptr, size(st.delta, 1), st.padding, st.dx.ptr, d, st.dt.ptr,
+                     size(st.dt, 1), ctx.lr, ctx.eps, nix.ptr, next.data.ptr, flags)
     end
     if ctx.adagrad !== nothing
         _, h = adagrad_state(ctx.adagrad, st.tables)

@@ -27,6 +27,8 @@ pullback is dlrm_split_step_bwd(DLRM_STEP_BWD_ONLY), update! with that optimizer
 (dlrm_adagrad_step_bwd).  `HipTables(tables, opt=StochasticDescent(η, seed), stochastic_step=True)` on bfloat16
 tables is the same chain with the stochastic rule (dlrm_sr_step_bwd): the optimizer's step word advances after the
 apply launch, run at once or deferred; without the keyword that optimizer takes the operator route.
+`HipTables(tables, opt=ADAGrad(η, ε, seed=s), sr_adagrad_step=True)` (or `RowwiseADAGrad`) on bfloat16 tables is the same
+chain with the seeded Adagrad rule (dlrm_sr_adagrad_step_bwd); without the keyword the operator route.
 
 Three launches per step, bit for bit the result of `HotPath.step` and of the five-launch chain.
 
@@ -69,12 +71,19 @@ class HipTables:
     (dlrm_sr_step_bwd), which behaves as the split rule's: the pullback steps and rounds the once-hit rows and
     update! with that same optimizer object runs or defers the apply, after which the step word advances.  opt: an
     ADAGrad or RowwiseADAGrad with a seed (the stochastic store, bfloat16 tables) takes the operator route too
-    (dlrm_adagrad_update with its handle, at once); adagrad_step=True is refused with it."""
+    (dlrm_adagrad_update with its handle, at once) and adagrad_step=True is refused with it -- unless
+    sr_adagrad_step=True, that optimizer's fused step (dlrm_sr_adagrad_step_bwd), which behaves as the seedless
+    rules': the pullback steps the once-hit rows, their state and rounds their weights, update! with that same
+    optimizer object (and the η and ε it had here) runs or defers the apply, after which the step word advances."""
 
     def __init__(self, tables, *, lr=None, index_base=1, defer_update=True, opt=None, stochastic_step=False,
-                 adagrad_step=None):
+                 adagrad_step=None, sr_adagrad_step=False):
         self._ts = as_table_set(tables) if not isinstance(tables, EmbeddingTableSet) else tables
         self.stochastic_step = bool(stochastic_step)
+        self.sr_adagrad_step = bool(sr_adagrad_step)
+        if self.sr_adagrad_step and not (isinstance(opt, _AdagradBase) and opt.sr_step_keyword == "sr_adagrad_step"):
+            raise ValueError("HipTables: sr_adagrad_step=True is the fused step of an Adagrad optimizer with a seed "
+                             "(opt=ADAGrad(eta, eps, seed=s) or opt=RowwiseADAGrad(eta, eps, seed=s))")
         # adagrad_step: None (the default: an Adagrad optimizer's fused step where it has one) or True, which demands it
         if adagrad_step and not (isinstance(opt, _AdagradBase) and opt.step_keyword == "adagrad_step"):
             raise ValueError("HipTables: adagrad_step=True is the Adagrad rules' fused step (opt=ADAGrad(eta, eps) or "
@@ -88,17 +97,17 @@ class HipTables:
                             "(Descent: lr=eta)")
         # the optimizer's fused step runs these tables' steps (the stochastic rule's: with its keyword only; without,
         # the operator route: the pullback writes every dt row and update! steps every row, lr stays None)
-        # (an Adagrad optimizer with a seed has no fused step: the operator route as well)
-        self._rule_step = (opt is not None and opt.step_keyword is not None and
-                           (self.stochastic_step or not isinstance(opt, StochasticDescent)))
+        # (an Adagrad optimizer with a seed: its fused step with sr_adagrad_step=True, else the operator route as well)
+        self._rule_step = self.sr_adagrad_step or (opt is not None and opt.step_keyword is not None and
+                                                   (self.stochastic_step or not isinstance(opt, StochasticDescent)))
         if self._rule_step:
             if lr is not None and float(lr) != opt.eta:
                 raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}")
             lr = opt.eta
         elif opt is not None and lr is not None:
-            raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}: without stochastic_step=True (and with a "
-                             "seeded Adagrad optimizer) the rule takes the operator route, so the pullback steps no "
-                             "row (lr must be None)")
+            raise ValueError(f"HipTables: lr={lr} beside opt={opt!r}: without stochastic_step=True (a seeded Adagrad "
+                             "optimizer: sr_adagrad_step=True) the rule takes the operator route, so the pullback steps "
+                             "no row (lr must be None)")
         if opt is not None:
             opt.check_tables(self._ts.dtype)
         self.opt = opt
@@ -189,7 +198,7 @@ class HipTables:
         hp = self._hp.get(batch)
         if hp is None:
             # the optimizer and its own keyword; without its fused step (the operator route) a plain step engine
-            rule = {"opt": self.opt, self.opt.step_keyword: True} if self._rule_step else {}
+            rule = {"opt": self.opt, self.opt.step_keyword or self.opt.sr_step_keyword: True} if self._rule_step else {}
             hp = HotPath(self._ts, batch, 1, lr=0.0 if self.lr is None else self.lr, index_base=self.index_base, **rule)
             hp.rule_params = self._opt_params
             if self.opt is not None and not self._rule_step:

@@ -56,6 +56,9 @@ class _StatefulOpt:
     # None: the optimizer's own, read at the call).
     step_keyword = None
     step_entry = None
+    # (a seeded Adagrad optimizer's fused step: a keyword and a pair of its own, `_AdagradBase`; None everywhere else)
+    sr_step_keyword = None
+    sr_step_entry = None
     no_atomic = None  # why the rule has no atomic mode (none of these has one)
 
     def step_params(self, fixed=None):
@@ -105,8 +108,9 @@ class _AdagradBase(_StatefulOpt):
     stored is that result rounded up or down as StochasticDescent rounds (`sr_round` restates it), so a step below
     half an ulp of the weight accumulates instead of vanishing.  The step is a counter on the device, per table set:
     0 at first use, one more after every update (a captured update advances it on every replay); `seek(tables, step)`
-    sets it and `step_of(tables)` reads it (synchronising).  A seeded optimizer has no fused training step: `HotPath`
-    and `HipTables` take it on the operator route, and `adagrad_step=True` is refused with it."""
+    sets it and `step_of(tables)` reads it (synchronising).  A seeded optimizer's fused training step is
+    `sr_adagrad_step=True` (dlrm_sr_adagrad_step_bwd; `sr_step_keyword` / `sr_step_entry`): without it `HotPath` and
+    `HipTables` take the optimizer on the operator route, and `adagrad_step=True` is refused with it."""
     rowwise = False
     no_atomic = "an atomic add never holds the row's whole gradient sum, which the rule squares"
     step_keyword = "adagrad_step"
@@ -120,7 +124,11 @@ class _AdagradBase(_StatefulOpt):
                 raise TypeError(f"{name}: seed is None or an integer in [0, 2^64), not {type(seed).__name__}")
             if not 0 <= seed < 2 ** 64:
                 raise ValueError(f"{name}: seed is None or an integer in [0, 2^64)")
-            self.step_keyword = self.step_entry = None  # (no fused step with the stochastic store: the operator route)
+            # the stochastic store's fused step is not the seedless rule's: a keyword and entry points of its own
+            # (dlrm_adagrad_step_bwd refuses a seeded handle), opt-in as every rule's
+            self.step_keyword = self.step_entry = None
+            self.sr_step_keyword = "sr_adagrad_step"
+            self.sr_step_entry = ("dlrm_sr_adagrad_step_bwd", "dlrm_sr_adagrad_step_bwd_prepare")
         self.eta = float(eta)
         self.eps = float(eps)
         self.seed = seed

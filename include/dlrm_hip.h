@@ -303,10 +303,13 @@ int dlrm_indexer_set_parts(dlrm_ctx* ctx, dlrm_indexer* indexer, int parts);
  * dlrm_adagrad_step_bwd's with an element-wise / a row-wise handle, and only an Adagrad apply with a
  * handle of that kind may complete it; SINGLES_STOCHASTIC, set with it: that backward was
  * dlrm_sr_step_bwd's, and only the stochastic rule's apply with the same dlrm_sr_sgd handle may
- * complete it.  (The Julia shim's pullback state, DLRMHip.jl `st.bwd`.) */
+ * complete it; SINGLES_SR_ADAGRAD / SINGLES_SR_ROWWISE, set with it: that backward was
+ * dlrm_sr_adagrad_step_bwd's with an element-wise / a row-wise dlrm_adagrad_create_sr handle, and
+ * only that rule's apply with the same handle may complete it.  (The Julia shim's pullback state,
+ * DLRMHip.jl `st.bwd`.) */
 enum { DLRM_IX_BUILT = 1, DLRM_IX_SPLIT = 2, DLRM_IX_PREPARED = 4, DLRM_IX_SINGLES_DONE = 8,
        DLRM_IX_SINGLES_SPLIT = 16, DLRM_IX_SINGLES_ADAGRAD = 32, DLRM_IX_SINGLES_ROWWISE = 64,
-       DLRM_IX_SINGLES_STOCHASTIC = 128 };
+       DLRM_IX_SINGLES_STOCHASTIC = 128, DLRM_IX_SINGLES_SR_ADAGRAD = 256, DLRM_IX_SINGLES_SR_ROWWISE = 512 };
 int dlrm_indexer_state(const dlrm_indexer* indexer, unsigned* state);
 
 /* Backward of a training step without a materialized ys (see above). */
@@ -412,10 +415,12 @@ int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagrad* opt, d
  * DLRM_UPDATE_ATOMIC returns DLRM_E_UNSUPPORTED, a split indexer whose singles are not done is
  * taken whole.  fp32 tables return DLRM_E_ARG (nothing to round), at create and at update; more
  * than 65536 tables or dim / 4 > 65536 returns DLRM_E_ARG at create (the counter's fields).
- * There is no fused training step with these rules: dlrm_adagrad_step_bwd(_prepare) with such a
- * handle returns DLRM_E_UNSUPPORTED, and dlrm_adagrad_update(PREBUILT) with one on an indexer in
- * state DLRM_IX_SINGLES_DONE (whichever rule marked it) returns DLRM_E_STATE; neither launches,
- * writes or moves the step word. */
+ * The fused training step with these rules has entry points of its own, dlrm_sr_adagrad_step_bwd
+ * (_prepare) below: dlrm_adagrad_step_bwd(_prepare) with such a handle returns
+ * DLRM_E_UNSUPPORTED, and dlrm_adagrad_update(PREBUILT) with one on an indexer in state
+ * DLRM_IX_SINGLES_DONE returns DLRM_E_STATE unless dlrm_sr_adagrad_step_bwd marked the build with
+ * this very handle (it then applies the repeated rows); the refusals neither launch, write nor
+ * move the step word. */
 int dlrm_adagrad_create_sr(dlrm_ctx* ctx, const dlrm_tables* tables, int rowwise,
                            float* const* state, int64_t seed, dlrm_adagrad** out);
 int dlrm_adagrad_seek(dlrm_ctx* ctx, dlrm_adagrad* opt, int64_t step);
@@ -683,6 +688,49 @@ int dlrm_sr_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_sr_sgd* op
                              const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
                              float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr,
                              dlrm_indexer* next_indexer, const void* next_indices, unsigned flags);
+
+/* ---- the training step with a sparse Adagrad rule and the stochastic store (see
+ * dlrm_adagrad_create_sr above): dlrm_adagrad_step_bwd and dlrm_adagrad_step_bwd_prepare with a
+ * handle of dlrm_adagrad_create_sr on DLRM_BF16 tables, after the same forward.
+ *   dlrm_sr_adagrad_step_bwd = dlrm_interact_bwd_gather + dlrm_adagrad_update(opt, PREBUILT) at
+ *   the same (seed, step): dx, every element of every table row and every state word or row end up
+ *   bit-identical to that pair's.  A once-hit row is stepped inside the backward with
+ *   dlrm_adagrad_step_bwd's arithmetic (G = 0 + g, the same reduction orders); its state is
+ *   written with the seedless bits and its weights as sr_bf16(W', R), the R of (seed, step, t, r, c)
+ *   generated at the write; its dt row is never written.  The apply launch steps the repeated rows
+ *   from their dt rows with the same rule.
+ * Arguments and flags are dlrm_adagrad_step_bwd's.  opt must come from dlrm_adagrad_create_sr: a
+ * handle of dlrm_adagrad_create, tables that are not DLRM_BF16, or a handle created for another
+ * table count / dim return DLRM_E_ARG, launch nothing and leave the step word alone.
+ * The step word has dlrm_sr_step_bwd's contract: the backward launch and the apply launch read the
+ * same value; the word advances by one, in stream order, after the launch that runs the apply --
+ * flags 0, DLRM_STEP_APPLY_ONLY, or dlrm_adagrad_update(PREBUILT) completing a DLRM_STEP_BWD_ONLY
+ * backward.  DLRM_STEP_BWD_ONLY alone does not advance it.  It advances when the call returned
+ * DLRM_OK and launched (also under a raised bounds flag, which leaves tables and state
+ * unwritten), not on an argument or state error.
+ * Fallbacks are dlrm_adagrad_step_bwd's on bf16 tables: a shape without a split backward, state
+ * rows that are not 16-B aligned (element-wise), dim other than 128 and not <= 64, the row-wise
+ * rule with up to 16 features or a dim that is not a power of two >= 8 run
+ * dlrm_interact_bwd_gather and let the rule's apply take the once-hit rows -- the same bits, since
+ * R does not depend on the launch that writes a row.  _prepare on a shape without an in-apply build
+ * runs the plain step.
+ * The indexer remembers the rule and the handle (DLRM_IX_SINGLES_SR_ADAGRAD /
+ * DLRM_IX_SINGLES_SR_ROWWISE), and only that handle completes the backward, through
+ * dlrm_sr_adagrad_step_bwd(APPLY_ONLY) or dlrm_adagrad_update(PREBUILT), which then applies the
+ * repeated rows.  Every pairing with another rule's step backward or update(PREBUILT), in either
+ * direction, another handle of the same kind, and a second backward on one build return
+ * DLRM_E_STATE, launch nothing and leave every step word alone. */
+int dlrm_sr_adagrad_step_bwd(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagrad* opt, dlrm_indexer* indexer,
+                             const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                             const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
+                             float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr, float eps,
+                             unsigned flags);
+int dlrm_sr_adagrad_step_bwd_prepare(dlrm_ctx* ctx, dlrm_tables* tables, dlrm_adagrad* opt,
+                                     dlrm_indexer* indexer,
+                                     const void* indices, int itype, int64_t table_stride, int index_base, int batch,
+                                     const void* x, int64_t x_ld, const void* dout, int64_t dout_ld, int padding,
+                                     float* dx, int64_t dx_ld, float* dt, int64_t dt_ld, float lr, float eps,
+                                     dlrm_indexer* next_indexer, const void* next_indices, unsigned flags);
 
 /* ---- table-sharded exchange over RCCL ------------------------------------
  * DLRM.jl is one process: maplookup hands its output straight to the interaction (model.jl:161-163).
