@@ -14,6 +14,7 @@ from .embedding import (DefaultStrategy, EmbeddingTableSet, PackedIndices, Preal
                         lookup, maplookup)
 from .evaluate import Evaluator, eval_reference
 from .hotpath import HotPath
+from .quant import Q8Inference, QuantizedTableSet, dequantize_rows, quantize_rows
 from .lazy import DeferredUpdate, HipTables, LazyGrad, LazyLookup
 from .interact import (POST_INTERACTION_PAD_TO_MUL, DotInteraction, cdiv, dot_back, dot_interaction, fast_vcat,
                        interaction_sizes, rrule, rrule_dot_interaction, rrule_self_batched_mul, rrule_triangular_slice,
@@ -34,4 +35,5 @@ __all__ = [
     "self_batched_mul", "rrule_self_batched_mul", "step_pipeline", "step_chunk", "step_parts", "zipf_perm", "HipTables", "LazyLookup",
     "LazyGrad", "DeferredUpdate", "ADAGrad", "RowwiseADAGrad", "SplitDescent", "split_f32", "merge_split",
     "StochasticDescent", "sr_round", "sr_bits", "philox4x32_10", "Evaluator", "eval_reference",
+    "QuantizedTableSet", "Q8Inference", "quantize_rows", "dequantize_rows",
 ]

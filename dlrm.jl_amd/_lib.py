@@ -75,6 +75,13 @@ SIGNATURES = {
     "dlrm_interact_fwd": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32]),
     "dlrm_lookup_interact_fwd": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64,
                                          _i32]),
+    "dlrm_q8_tables_create": (_i32, [_vp, _i32, _i32, _pp, _pp, _pi64, _pp]),
+    "dlrm_q8_tables_destroy": (_i32, [_vp]),
+    "dlrm_q8_quantize": (_i32, [_vp, _vp, _vp]),
+    "dlrm_q8_dequantize": (_i32, [_vp, _vp, _vp]),
+    "dlrm_q8_maplookup": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64]),
+    "dlrm_q8_lookup_interact_fwd": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64,
+                                            _i32]),
     "dlrm_interact_bwd": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64]),
     "dlrm_interact_bwd_gather": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _i32,
                                         _vp, _i64, _vp, _i64]),

@@ -22,6 +22,7 @@
 
 #include "common.hpp"
 #include "apply.hpp"
+#include "q8.hpp"
 
 using namespace dlrm;
 
@@ -47,6 +48,16 @@ struct dlrm_tables {
     TableDesc* d_desc = nullptr;
     std::vector<TableDesc> h_desc;
     bool aligned16 = true;
+};
+
+// int8 row-quantized tables: the caller's code and {scale, bias} arrays
+struct dlrm_q8_tables {
+    dlrm_ctx* ctx = nullptr;
+    int T = 0, D = 0;
+    Q8Desc* d_desc = nullptr;
+    std::vector<Q8Desc> h_desc;
+    int64_t rows = 0;  // of every table
+    int q_align = 16;  // the largest power of two <= 16 that divides every q pointer (q8_plan.hpp)
 };
 
 // An optimizer's state of one table set: the caller's per-table pointers, uploaded once
@@ -655,6 +666,118 @@ int dlrm_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_tables* tb, const void* i
                           index_base, batch, lookups, ys, ys_ld, d, tb->h_desc.data());
     if (rc) return rc;
     return launch_interact_fwd(ctx, tb->dtype, d, F, batch, x, x_ld, ys, ys_ld, out, out_ld, padding);
+}
+
+// ------------------------------------------------------------- int8 row-quantized tables
+int dlrm_q8_tables_create(dlrm_ctx* ctx, int num_tables, int dim, uint8_t* const* q, float* const* sb,
+                          const int64_t* nrows, dlrm_q8_tables** out) {
+    CHECK_ARG(ctx && out, "dlrm_q8_tables_create: null argument");
+    *out = nullptr;
+    CHECK_ARG(num_tables >= 0 && dim > 0, "dlrm_q8_tables_create: num_tables=%d dim=%d", num_tables, dim);
+    CHECK_ARG(num_tables == 0 || (q && sb && nrows), "dlrm_q8_tables_create: null q/sb/nrows");
+    for (int t = 0; t < num_tables; ++t) {
+        CHECK_ARG(nrows[t] >= 0 && nrows[t] < 0xFFFFFFFFll && (nrows[t] == 0 || (q[t] && sb[t])),
+                  "dlrm_q8_tables_create: table %d has nrows=%lld", t, (long long)nrows[t]);
+        CHECK_ARG((uintptr_t)sb[t] % 8 == 0, "dlrm_q8_tables_create: sb[%d] is not 8-B aligned", t);
+    }
+    dlrm_q8_tables* qt = new (std::nothrow) dlrm_q8_tables();
+    if (!qt) return DLRM_E_NOMEM;
+    qt->ctx = ctx;
+    qt->T = num_tables;
+    qt->D = dim;
+    qt->h_desc.resize(num_tables);
+    for (int t = 0; t < num_tables; ++t) {
+        qt->h_desc[t] = Q8Desc{q[t], (float2*)sb[t], nrows[t], qt->rows};
+        qt->rows += nrows[t];
+        while (qt->q_align > 1 && (uintptr_t)q[t] % (unsigned)qt->q_align) qt->q_align >>= 1;
+    }
+    int rc = hip_set(ctx);
+    if (rc == DLRM_OK && num_tables > 0) {
+        rc = ctx_hip(ctx, hipMalloc((void**)&qt->d_desc, sizeof(Q8Desc) * num_tables), "hipMalloc(q8 tables)");
+        if (rc == DLRM_OK)
+            rc = ctx_hip(ctx, hipMemcpy(qt->d_desc, qt->h_desc.data(), sizeof(Q8Desc) * num_tables, hipMemcpyHostToDevice),
+                         "hipMemcpy(q8 tables)");
+    }
+    if (rc != DLRM_OK) {
+        if (qt->d_desc) (void)hipFree(qt->d_desc);
+        delete qt;
+        return rc;
+    }
+    *out = qt;
+    return DLRM_OK;
+}
+
+int dlrm_q8_tables_destroy(dlrm_q8_tables* q8) {
+    if (!q8) return DLRM_OK;
+    if (q8->d_desc) (void)hipFree(q8->d_desc);
+    delete q8;
+    return DLRM_OK;
+}
+
+// the two sets describe the same rows
+static int check_q8_pair(dlrm_ctx* ctx, const dlrm_tables* tb, const dlrm_q8_tables* q8, const char* fn) {
+    CHECK_ARG(tb->T == q8->T && tb->D == q8->D, "%s: %d tables of dim %d against %d quantized tables of dim %d", fn, tb->T,
+              tb->D, q8->T, q8->D);
+    for (int t = 0; t < tb->T; ++t)
+        CHECK_ARG(tb->h_desc[t].nrows == q8->h_desc[t].nrows, "%s: table %d has %lld rows against %lld quantized rows", fn,
+                  t, (long long)tb->h_desc[t].nrows, (long long)q8->h_desc[t].nrows);
+    return DLRM_OK;
+}
+
+int dlrm_q8_quantize(dlrm_ctx* ctx, const dlrm_tables* src, dlrm_q8_tables* dst) {
+    CHECK_ARG(ctx && src && dst, "dlrm_q8_quantize: null ctx/tables");
+    const int rc = check_q8_pair(ctx, src, dst, "dlrm_q8_quantize");
+    if (rc) return rc;
+    return launch_q8_quantize(ctx, src->d_desc, src->dtype, src->aligned16, dst->d_desc, dst->q_align, dst->T, dst->D,
+                              dst->rows);
+}
+
+int dlrm_q8_dequantize(dlrm_ctx* ctx, const dlrm_q8_tables* src, dlrm_tables* dst) {
+    CHECK_ARG(ctx && src && dst, "dlrm_q8_dequantize: null ctx/tables");
+    const int rc = check_q8_pair(ctx, dst, src, "dlrm_q8_dequantize");
+    if (rc) return rc;
+    return launch_q8_dequantize(ctx, src->d_desc, src->q_align, dst->d_desc, dst->dtype, dst->aligned16, src->T, src->D,
+                                src->rows);
+}
+
+static int check_q8_indices(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const void* indices, int itype, int64_t tstride,
+                            int batch, int lookups, int dtype) {
+    CHECK_ARG(dtype == DLRM_F32 || dtype == DLRM_BF16, "unknown dtype %d", dtype);
+    CHECK_ARG(itype == DLRM_I32 || itype == DLRM_I64, "unknown index type %d", itype);
+    CHECK_ARG(batch >= 0 && lookups >= 1, "batch=%d lookups=%d", batch, lookups);
+    CHECK_ARG((int64_t)batch * lookups < (1ll << 31), "batch*lookups exceeds 2^31");
+    CHECK_ARG(batch == 0 || q8->T == 0 || indices, "null indices");
+    CHECK_ARG(q8->T <= 1 || tstride >= (int64_t)batch * lookups, "table_stride %lld < batch*lookups %lld",
+              (long long)tstride, (long long)batch * lookups);
+    return DLRM_OK;
+}
+
+int dlrm_q8_maplookup(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const void* indices, int itype, int64_t table_stride,
+                      int index_base, int batch, int lookups, int dtype, void* out, int64_t out_ld, int64_t out_offset) {
+    CHECK_ARG(ctx && q8, "dlrm_q8_maplookup: null ctx/tables");
+    const int rc = check_q8_indices(ctx, q8, indices, itype, table_stride, batch, lookups, dtype);
+    if (rc) return rc;
+    CHECK_ARG(batch == 0 || q8->T == 0 || out, "dlrm_q8_maplookup: null out");
+    CHECK_ARG(out_offset >= 0 && out_ld >= out_offset + (int64_t)q8->T * q8->D,
+              "dlrm_q8_maplookup: out_ld %lld < out_offset %lld + T*D %lld", (long long)out_ld, (long long)out_offset,
+              (long long)q8->T * q8->D);
+    return launch_q8_maplookup(ctx, q8->d_desc, q8->q_align, q8->T, q8->D, indices, itype, table_stride, index_base,
+                               batch, lookups, dtype, out, out_ld, out_offset);
+}
+
+int dlrm_q8_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const void* indices, int itype,
+                                int64_t table_stride, int index_base, int batch, int lookups, int dtype, const void* x,
+                                int64_t x_ld, void* out, int64_t out_ld, int padding) {
+    CHECK_ARG(ctx && q8, "dlrm_q8_lookup_interact_fwd: null ctx/tables");
+    const int rc = check_q8_indices(ctx, q8, indices, itype, table_stride, batch, lookups, dtype);
+    if (rc) return rc;
+    const int d = q8->D, F = q8->T + 1;
+    const int64_t P = (int64_t)F * (F - 1) / 2;
+    CHECK_ARG(padding >= 0 && x_ld >= d && out_ld >= d + P + padding,
+              "dlrm_q8_lookup_interact_fwd: leading dimensions too small");
+    CHECK_ARG(batch == 0 || (x && out), "dlrm_q8_lookup_interact_fwd: null buffer");
+    return launch_q8_lookup_interact_fwd(ctx, q8->h_desc.data(), q8->q_align, q8->T, d, indices, itype, table_stride,
+                                         index_base, batch, lookups, dtype, x, x_ld, out, out_ld, padding);
 }
 
 int dlrm_interact_bwd(dlrm_ctx* ctx, int dtype, int d, int num_features, int batch, const void* dout, int64_t dout_ld,

@@ -225,6 +225,8 @@ class DLRMModel:
         self.loss = None
         self.prob = None
         self._dz = self._head_prob = None
+        self._pad_to = hot_kw.get("pad_to", 1)
+        self._q8 = None  # (the QuantizedTableSet last scored with, its Q8Inference)
         bottom.flatten()  # one Descent launch per MLP
         top.flatten()
 
@@ -238,27 +240,49 @@ class DLRMModel:
         self.prob = self.top.forward(out.float()).reshape(-1)
         return self.prob
 
-    def predict(self, dense, sparse):
+    def quantize(self):
+        """The model's tables as int8 rows with a per-row scale and bias (`QuantizedTableSet.from_tables`): what
+        `predict(..., q8=)` and `test(..., q8=)` score.  The tables are quantized as the lookup reads them (for
+        `SplitDescent` the bf16 high halves of the merged values)."""
+        from .quant import QuantizedTableSet
+        return QuantizedTableSet.from_tables(self.tables)
+
+    def _q8_engine(self, q8):
+        from .quant import Q8Inference
+        if self._q8 is None or self._q8[0] is not q8:
+            if len(q8) != len(self.tables) or q8.D != self.tables.D:
+                raise ValueError("q8 does not match the model's tables (count, feature size)")
+            self._q8 = (q8, Q8Inference(q8, self.hot.B, self.hot.L, d=self.hot.d, dtype=self.tdtype,
+                                        index_base=self.hot.index_base, pad_to=self._pad_to))
+        return self._q8[1]
+
+    def predict(self, dense, sparse, q8=None):
         """The model call for evaluation: the logits [B][1] of a batch (the sigmoid is `Evaluator.add`'s, with
         dlrm_bce_head's expression).  Bottom MLP, `HotPath.infer`, top MLP: nothing a training step keeps is
-        touched -- no indexer, no saved activation, no optimizer state -- so it can run between two steps."""
+        touched -- no indexer, no saved activation, no optimizer state -- so it can run between two steps.
+        q8: a `QuantizedTableSet` of the model's tables (`quantize()`); the hot-path forward is then
+        `Q8Inference.infer` over it."""
         if not isinstance(sparse, PackedIndices):
             sparse = PackedIndices(sparse, device=self.tables.device)
         x = self.bottom.infer(dense)
-        out = self.hot.infer(x.to(self.tdtype), sparse)
+        if q8 is None:
+            out = self.hot.infer(x.to(self.tdtype), sparse)
+        else:
+            out = self._q8_engine(q8).infer(x.to(self.tdtype), sparse)
         return self.top.infer(out.float(), logits=True)
 
-    def test(self, data, record=None, evaluator=None, probs=None):
+    def test(self, data, record=None, evaluator=None, probs=None, q8=None):
         """The reference's `test(model, data; record, strategy)` (src/train/utils.jl:31-46): for every
         (labels, dense, sparse) of `data` (a `DACLoader`, or any iterable of such batches of the model's batch
         size), `predict` and one `Evaluator.add`; one synchronisation, at the end.  Appends the accuracy
         (correct / total) to `record` and returns `Evaluator.result()`: dict(total, correct, accuracy, logloss,
         auc, positives, negatives).  evaluator: an `Evaluator` to use (reset first; its state holds this pass
-        afterwards); probs: a list that receives every batch's probabilities (a device tensor each)."""
+        afterwards); probs: a list that receives every batch's probabilities (a device tensor each); q8: score
+        the quantized tables (`predict`'s q8)."""
         dev = self.tables.device
         ev = Evaluator(dev) if evaluator is None else evaluator.reset()
         for labels, dense, sparse in data:
-            z = self.predict(dense, sparse)
+            z = self.predict(dense, sparse, q8=q8)
             check_labels(labels, z)
             p = None
             if probs is not None:

@@ -1304,4 +1304,97 @@ function test(model, data, ev::HipEval; record = Float32[], strategy)
     return r
 end
 
+#####
+##### int8 row-quantized tables (inference and evaluation; include/dlrm_hip.h)
+#####
+
+"""
+    HipQ8Tables(tables::AbstractVector{<:HipEmbedding})
+
+The tables as int8 rows with a per-row `{scale, bias}`: codes `q[t]` (`D × N` of `UInt8`) and `sb[t]`
+(`2 × N` of `Float32`), allocated here and filled by one `dlrm_q8_quantize` launch.  `v = (q * scale) + bias`
+in two fp32 roundings; `|v - w| <= (0.5 + 2^-10) scale + 2^-22 max(|lo|, |hi|)` per element.
+"""
+mutable struct HipQ8Tables{D}
+    ctx::Context
+    q::Vector{DeviceMatrix{UInt8}}
+    sb::Vector{DeviceMatrix{Float32}}
+    ptr::Ptr{Cvoid}
+end
+function HipQ8Tables(tables::AbstractVector{<:HipEmbedding{Static{D},T}}) where {D,T}
+    ctx = first(tables).data.ctx
+    poll_bounds!(tables)
+    flush!(tables)
+    q = [DeviceMatrix{UInt8}(ctx, D, size(t, 2)) for t in tables]
+    sb = [DeviceMatrix{Float32}(ctx, 2, size(t, 2)) for t in tables]
+    qp, sp = [m.ptr for m in q], [m.ptr for m in sb]
+    rows = Int64[size(t, 2) for t in tables]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ctx, ccall((:dlrm_q8_tables_create, libdlrm), Cint,
+                     (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ref{Ptr{Cvoid}}),
+                     ctx.ptr, length(tables), D, qp, sp, rows, out))
+    q8 = HipQ8Tables{D}(ctx, q, sb, out[])
+    finalizer(x -> ccall((:dlrm_q8_tables_destroy, libdlrm), Cint, (Ptr{Cvoid},), x.ptr), q8)
+    check(ctx, ccall((:dlrm_q8_quantize, libdlrm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     ctx.ptr, tableset(tables), q8.ptr))
+    return q8
+end
+Base.length(q8::HipQ8Tables) = length(q8.q)
+nbytes(q8::HipQ8Tables) = sum(prod(size(m)) for m in q8.q) + 4 * sum(prod(size(m)) for m in q8.sb)
+
+"""
+    dequantize!(tables, q8)
+
+The way back: writes `v` (or `bf16(v)`) into an existing table set of the same shape.
+"""
+function dequantize!(tables::AbstractVector{<:HipEmbedding{Static{D}}}, q8::HipQ8Tables{D}) where {D}
+    flush!(tables)
+    check(q8.ctx, ccall((:dlrm_q8_dequantize, libdlrm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                        q8.ctx.ptr, q8.ptr, tableset(tables)))
+    return tables
+end
+
+# maplookup(PreallocationStrategy(P), q8, sparse): the dequantizing gather, rows of T
+function _maplookup(q8::HipQ8Tables{D}, sparse, P::Integer, ::Type{T} = Float32) where {D,T}
+    ctx = q8.ctx
+    idx = sparse isa PackedIndices ? sparse : pack(ctx, sparse)
+    ys = DeviceMatrix{T}(ctx, P + D * length(q8), idx.batch)
+    check(ctx, ccall((:dlrm_q8_maplookup, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Int64, Int64),
+                     ctx.ptr, q8.ptr, idx.data.ptr, DLRM_I32, idx.batch * idx.lookups, 1,
+                     idx.batch, idx.lookups, dtype_code(T), ys.ptr, size(ys, 1), P))
+    return ys, idx
+end
+EmbeddingTables.maplookup(s::PreallocationStrategy, q8::HipQ8Tables, sparse) =
+    first(_maplookup(q8, sparse, prealloc_rows(s)))
+
+"""
+    infer(dot::HipDotInteraction, x::DeviceMatrix, q8::HipQ8Tables, sparse)
+
+The inference forward on quantized rows: one launch (`dlrm_q8_lookup_interact_fwd`) where the fused kernel
+exists, else the gather and `dlrm_interact_fwd`, with the same bits.
+"""
+function infer(dot::HipDotInteraction, x::DeviceMatrix{T}, q8::HipQ8Tables{D}, sparse) where {D,T}
+    ctx = q8.ctx
+    idx = sparse isa PackedIndices ? sparse : pack(ctx, sparse)
+    d, B = size(x)
+    F = length(q8) + 1
+    width, padding = interaction_sizes(d, F, dot.pad_to)
+    out = DeviceMatrix{T}(ctx, width, B)
+    rc = ccall((:dlrm_q8_lookup_interact_fwd, libdlrm), Cint,
+               (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Int64,
+                Ptr{Cvoid}, Int64, Cint),
+               ctx.ptr, q8.ptr, idx.data.ptr, DLRM_I32, idx.batch * idx.lookups, 1, B, idx.lookups,
+               dtype_code(T), x.ptr, d, out.ptr, width, padding)
+    if rc == Cint(-4)  # DLRM_E_UNSUPPORTED: no fused kernel for this shape
+        ys, _ = _maplookup(q8, idx, d, T)
+        check(ctx, ccall((:dlrm_interact_fwd, libdlrm), Cint,
+                         (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cint),
+                         ctx.ptr, dtype_code(T), d, F, B, x.ptr, d, ys.ptr, size(ys, 1), out.ptr, width, padding))
+    else
+        check(ctx, rc)
+    end
+    return out
+end
+
 end # module

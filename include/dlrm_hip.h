@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DLRM_HIP_ABI_VERSION 2
+#define DLRM_HIP_ABI_VERSION 3
 
 typedef enum {
     DLRM_OK = 0,
@@ -842,6 +842,52 @@ int dlrm_dac_loader_next(dlrm_dac_loader* loader, void* consumer_stream, int* sl
 int dlrm_dac_loader_release(dlrm_dac_loader* loader, int slot, void* consumer_stream);
 int dlrm_dac_loader_stop(dlrm_dac_loader* loader);
 int dlrm_dac_loader_destroy(dlrm_dac_loader* loader);
+
+/* ---- int8 row-quantized tables (inference and evaluation) ------------------------------
+ * A quantized table t is two caller-owned device arrays: codes q[nrows[t]][dim] of uint8, row-major,
+ * and sb[nrows[t]] of float2 {scale, bias} (passed as float*, 8-B aligned).  They are separate so that
+ * rows stay 16-B aligned whenever dim % 16 == 0 (a dim = 128 row is one 128-B line).
+ * Quantizing a row w[0..dim) (bf16 elements first converted to fp32), every operation a separately
+ * rounded fp32 operation:
+ *   lo = min_c w[c]   hi = max_c w[c]   range = hi - lo
+ *   scale = range / 255.0f                      inv = range > 0 ? 255.0f / range : 0.0f   (IEEE division)
+ *   q[c]  = (uint8) min(255, max(0, rintf((w[c] - lo) * inv)))   (ties to even)      bias = lo
+ * Dequantizing is two roundings, never an fma:  v[c] = ((float)q[c] * scale) + bias; a bf16 consumer gets
+ * v[c] rounded to nearest even, once.  Every element of a finite row with a finite range satisfies
+ *   |v - w| <= (0.5 + 2^-10) * scale + 2^-22 * max(|lo|, |hi|);
+ * for any other row nothing faults and what is stored is unspecified.  Min and max are exact in any order,
+ * so the quantizer is bitwise reproducible.  No reference counterpart (DLRM.jl trains and scores fp32).
+ * create: no device work but the upload of the descriptors; the arrays stay caller-owned.
+ * quantize: src is fp32 or bf16; table count, dim and row counts must match (else DLRM_E_ARG); one launch
+ *           over every table, 64-bit row offsets.
+ * dequantize: writes v (fp32) or bf16(v) into an existing table set of the same shape: the way back.
+ * The launching calls allocate nothing and do not synchronise (hipGraph-capturable); an out-of-range
+ * index never faults, contributes a zero row and raises the flag dlrm_check_bounds reads. */
+typedef struct dlrm_q8_tables dlrm_q8_tables;
+int dlrm_q8_tables_create(dlrm_ctx* ctx, int num_tables, int dim, uint8_t* const* q, float* const* sb,
+                          const int64_t* nrows, dlrm_q8_tables** out);
+int dlrm_q8_tables_destroy(dlrm_q8_tables* q8);
+int dlrm_q8_quantize(dlrm_ctx* ctx, const dlrm_tables* src, dlrm_q8_tables* dst);
+int dlrm_q8_dequantize(dlrm_ctx* ctx, const dlrm_q8_tables* src, dlrm_tables* dst);
+
+/* dlrm_maplookup reading quantized rows: out (of `dtype`) receives exactly what dlrm_maplookup over the
+ * dlrm_q8_dequantize'd set of that dtype writes -- one-hot: v converted to dtype; lookups > 1: the rows as
+ * that set holds them (v, or bf16(v)), seeded with the first, added in k order in fp32, converted once.  Any dim >= 1; 16 codes per lane where
+ * dim % 16 == 0 and the code rows and the output rows are 16-B aligned, one code per lane otherwise, with
+ * the same results. */
+int dlrm_q8_maplookup(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const void* indices, int itype,
+                      int64_t table_stride, int index_base, int batch, int lookups, int dtype,
+                      void* out, int64_t out_ld, int64_t out_offset);
+
+/* The inference forward on quantized rows in ONE launch, no ys: out (of `dtype`, as x) receives exactly
+ * what dlrm_q8_maplookup(out_offset = d, into a ys) + dlrm_interact_fwd write.  Requires q8->dim == d.
+ * Returns DLRM_E_UNSUPPORTED, with nothing launched, where there is no fused kernel; the caller then
+ * takes those two calls.  The fused kernel exists exactly for: lookups == 1; 1 <= num_tables <= 31;
+ * d % 4 == 0 (fp32) or d % 8 == 0 (bf16); every q pointer 4-B (fp32) or 8-B (bf16) aligned; x 16-B aligned
+ * with x_ld % 4 == 0 (fp32) or x_ld % 8 == 0 (bf16).  out and out_ld need no alignment. */
+int dlrm_q8_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const void* indices, int itype,
+                                int64_t table_stride, int index_base, int batch, int lookups, int dtype,
+                                const void* x, int64_t x_ld, void* out, int64_t out_ld, int padding);
 
 #ifdef __cplusplus
 }
