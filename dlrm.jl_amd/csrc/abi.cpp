@@ -453,12 +453,18 @@ int dlrm_memcpy_h2d_async(dlrm_ctx* ctx, void* dst, const void* src, size_t byte
 
 int dlrm_host_register(void* ptr, size_t bytes) {
     if (!ptr || bytes == 0) return DLRM_E_ARG;
-    return hipHostRegister(ptr, bytes, hipHostRegisterDefault) == hipSuccess ? DLRM_OK : DLRM_E_HIP;
+    if (hipHostRegister(ptr, bytes, hipHostRegisterDefault) == hipSuccess) return DLRM_OK;
+    // a refusal is an answer, not a fault (callers fall back to pinned staging): take it off the
+    // thread's last-error slot, where the next kernel launch's hipGetLastError would report it
+    (void)hipGetLastError();
+    return DLRM_E_HIP;
 }
 
 int dlrm_host_unregister(void* ptr) {
     if (!ptr) return DLRM_E_ARG;
-    return hipHostUnregister(ptr) == hipSuccess ? DLRM_OK : DLRM_E_HIP;
+    if (hipHostUnregister(ptr) == hipSuccess) return DLRM_OK;
+    (void)hipGetLastError();  // as above
+    return DLRM_E_HIP;
 }
 
 int dlrm_memcpy_d2h(dlrm_ctx* ctx, void* dst, const void* src, size_t bytes) {

@@ -156,8 +156,9 @@ class DACLoader:
     while the caller computes (34.6 M samples/s beside the eager hot-path step, against 30.7 M
     with `native=False`, where the same staging is driven from the caller's thread).  With `direct=True` the dataset's memory is page-locked once
     (dlrm_host_register) and each batch is one async DMA straight out of it (falls back to staging
-    when registration is refused, e.g. a read-only file mapping or a dataset over
-    DIRECT_MAX_BYTES).  Measured on MI355X (tools/bench_dac_loader.py, B = 2048): staging 53 M
+    when registration is refused, e.g. a read-only file mapping, a dataset over DIRECT_MAX_BYTES,
+    or a machine that page-locks no memory a process already has, as some virtual machines do;
+    `loader.direct` tells which form runs).  Measured on MI355X (tools/bench_dac_loader.py, B = 2048): staging 53 M
     records/s, direct 20 M records/s, because copies out of registered memory are slower than out
     of hipHostMalloc buffers, so staging is the default.
 

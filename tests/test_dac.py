@@ -6,6 +6,7 @@ test/data/criteo.jl: record write/read round trip, sharded maps == monolithic ma
 reindexed binary == parseline + reindex of every original line.  The checker is
 oracle/dac_oracle.py (a line-by-line Python restatement of criteo.jl).
 """
+import ctypes
 import os
 
 import numpy as np
@@ -116,6 +117,18 @@ def reindexed(pkg, ref_records):
     return data, maps
 
 
+def _host_register_works(pkg, gpu):
+    """Whether this machine page-locks memory a process already has (hipHostRegister): some, such
+    as virtual machines with the GPU passed through, refuse every such request."""
+    lib = pkg.runtime.context(gpu).lib
+    probe = np.zeros(1 << 16, dtype=np.uint8)
+    addr = ctypes.c_void_p(probe.ctypes.data)
+    if lib.dlrm_host_register(addr, probe.nbytes) != pkg._lib.OK:
+        return False
+    lib.dlrm_host_unregister(addr)
+    return True
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("itype,direct,native", [(torch.int32, False, True), (torch.int64, False, True),
                                                  (torch.int32, True, False), (torch.int32, False, False)])
@@ -123,6 +136,8 @@ def test_dac_loader_batches_match_load(pkg, gpu, reindexed, itype, direct, nativ
     """native: the C++ prefetch thread; direct: the dataset page-locked, one DMA per batch; else
     pinned staging driven from Python.  Two epochs (the loader restarts), the second one
     abandoned after one batch and then a third run in full."""
+    if direct and not _host_register_works(pkg, gpu):
+        pytest.skip("hipHostRegister is not supported here")
     data, _ = reindexed
     loader = pkg.DACLoader(data, 64, gpu, index_dtype=itype, direct=direct, native=native)
     assert loader.direct == direct and loader.native == native
@@ -135,6 +150,26 @@ def test_dac_loader_batches_match_load(pkg, gpu, reindexed, itype, direct, nativ
             next(iter(loader))
     it.close()
     assert len(loader) == 250 // 64  # whole batches only (criteo.jl:326-329)
+    seen = 0
+    for i, b in enumerate(loader):
+        labels, dense, sparse = dac_oracle.load_batch(data[i * 64:(i + 1) * 64])
+        assert np.array_equal(b.labels.cpu().numpy(), labels)
+        assert np.array_equal(b.dense.cpu().numpy(), dense)
+        assert np.array_equal(b.sparse.cpu().numpy(), sparse.astype(np.int64))
+        seen += 1
+    assert seen == 3
+    loader.close()
+
+
+@pytest.mark.gpu
+def test_refused_host_register_falls_back_to_staging(pkg, gpu, reindexed, tmp_path):
+    """A refused page-lock request is an answer, not a fault: `direct=True` then stages through
+    pinned buffers, and the refusal must not surface as the next kernel launch's error.  The
+    refusal here is that of a read-only file mapping (DACLoader's docstring)."""
+    reindexed[0].tofile(tmp_path / "dac.bin")
+    data = pkg.dac.load(tmp_path / "dac.bin")
+    loader = pkg.DACLoader(data, 64, gpu, direct=True, native=False)
+    assert not loader.direct and not loader.native
     seen = 0
     for i, b in enumerate(loader):
         labels, dense, sparse = dac_oracle.load_batch(data[i * 64:(i + 1) * 64])
