@@ -14,6 +14,7 @@ from .embedding import (DefaultStrategy, EmbeddingTableSet, PackedIndices, Preal
                         lookup, maplookup)
 from .evaluate import Evaluator, eval_reference
 from .hotpath import HotPath
+from .mlp_bf16 import Bf16MLP, mlp_bf16_plan, mlp_bf16_reference
 from .quant import Q8Inference, QuantizedTableSet, dequantize_rows, quantize_rows
 from .lazy import DeferredUpdate, HipTables, LazyGrad, LazyLookup
 from .interact import (POST_INTERACTION_PAD_TO_MUL, DotInteraction, cdiv, dot_back, dot_interaction, fast_vcat,
@@ -36,4 +37,5 @@ __all__ = [
     "LazyGrad", "DeferredUpdate", "ADAGrad", "RowwiseADAGrad", "SplitDescent", "split_f32", "merge_split",
     "StochasticDescent", "sr_round", "sr_bits", "philox4x32_10", "Evaluator", "eval_reference",
     "QuantizedTableSet", "Q8Inference", "quantize_rows", "dequantize_rows",
+    "Bf16MLP", "mlp_bf16_plan", "mlp_bf16_reference",
 ]

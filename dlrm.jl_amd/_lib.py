@@ -45,6 +45,7 @@ _vp, _i32, _i64, _f32, _u32, _sz = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int6
                                     ctypes.c_uint, ctypes.c_size_t)
 _pp = ctypes.POINTER(ctypes.c_void_p)
 _pi64 = ctypes.POINTER(ctypes.c_int64)
+_pi32 = ctypes.POINTER(ctypes.c_int)
 
 # name -> (restype, argtypes); must match include/dlrm_hip.h (checked by tests/test_abi.py)
 SIGNATURES = {
@@ -82,6 +83,11 @@ SIGNATURES = {
     "dlrm_q8_maplookup": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64]),
     "dlrm_q8_lookup_interact_fwd": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64,
                                             _i32]),
+    "dlrm_mlp_bf16_plan": (_i32, [_i32, _pi32, _i32, _i32, _i32, _pi32, _pi32, _pi64, _pi64, _pi32, _pi32]),
+    "dlrm_mlp_bf16_create": (_i32, [_vp, _i32, _pi32, _pp]),
+    "dlrm_mlp_bf16_destroy": (_i32, [_vp]),
+    "dlrm_mlp_bf16_pack": (_i32, [_vp, _vp, _pp, _pi64, _pp]),
+    "dlrm_mlp_bf16_infer": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _i32, _i64, _i32]),
     "dlrm_interact_bwd": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64]),
     "dlrm_interact_bwd_gather": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _i32,
                                         _vp, _i64, _vp, _i64]),

@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "apply.hpp"
 #include "q8.hpp"
+#include "mlp_bf16.hpp"
 
 using namespace dlrm;
 
@@ -58,6 +59,15 @@ struct dlrm_q8_tables {
     std::vector<Q8Desc> h_desc;
     int64_t rows = 0;  // of every table
     int q_align = 16;  // the largest power of two <= 16 that divides every q pointer (q8_plan.hpp)
+};
+
+// A Dense chain for the fused bf16 inference: the widths and the packed weights and biases (mlp_plan.hpp), owned
+struct dlrm_mlp_bf16 {
+    dlrm_ctx* ctx = nullptr;
+    std::vector<int> sizes;  // layers + 1
+    void* packed = nullptr;
+    int64_t packed_bytes = 0;
+    bool is_packed = false;  // dlrm_mlp_bf16_pack has run
 };
 
 // An optimizer's state of one table set: the caller's per-table pointers, uploaded once
@@ -784,6 +794,90 @@ int dlrm_q8_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const v
     CHECK_ARG(batch == 0 || (x && out), "dlrm_q8_lookup_interact_fwd: null buffer");
     return launch_q8_lookup_interact_fwd(ctx, q8->h_desc.data(), q8->q_align, q8->T, d, indices, itype, table_stride,
                                          index_base, batch, lookups, dtype, x, x_ld, out, out_ld, padding);
+}
+
+// ------------------------------------------------------------- fused bf16 MLP inference
+// (DLRM_MLP_MT = 16 / 32: the comparison knob that takes the plan's tile height out of its rule's hands)
+static int mlp_force_mt() {
+    static const int mt = env_int("DLRM_MLP_MT", 0);
+    return mt == 16 || mt == 32 ? mt : 0;
+}
+
+int dlrm_mlp_bf16_plan(int layers, const int* sizes, int batch, int x_dtype, int out_dtype, int* mt, int* grid,
+                       int64_t* lds_bytes, int64_t* packed_bytes, int* kp, int* np) {
+    MlpPlan p;
+    const int rc = plan_mlp(layers, sizes, batch, x_dtype, out_dtype, mlp_force_mt(), &p);
+    if (rc != DLRM_OK) return rc;
+    if (mt) *mt = p.MT;
+    if (grid) *grid = p.grid;
+    if (lds_bytes) *lds_bytes = p.lds_bytes;
+    if (packed_bytes) *packed_bytes = p.packed_bytes;
+    for (int l = 0; l < layers; ++l) {
+        if (kp) kp[l] = p.Kp[l];
+        if (np) np[l] = p.Np[l];
+    }
+    return DLRM_OK;
+}
+
+int dlrm_mlp_bf16_create(dlrm_ctx* ctx, int layers, const int* sizes, dlrm_mlp_bf16** out) {
+    CHECK_ARG(ctx && sizes && out, "dlrm_mlp_bf16_create: null argument");
+    *out = nullptr;
+    MlpPlan p;
+    int rc = plan_mlp(layers, sizes, 0, DLRM_F32, DLRM_F32, 0, &p);
+    if (rc != DLRM_OK)
+        return ctx_fail(ctx, rc, "dlrm_mlp_bf16_create: %d layers: 1 .. %d of widths 1 .. %d have a kernel", layers,
+                        kMlpMaxLayers, kMlpMaxWidth);
+    dlrm_mlp_bf16* m = new (std::nothrow) dlrm_mlp_bf16();
+    if (!m) return DLRM_E_NOMEM;
+    m->ctx = ctx;
+    m->sizes.assign(sizes, sizes + layers + 1);
+    m->packed_bytes = p.packed_bytes;
+    rc = hip_set(ctx);
+    if (rc == DLRM_OK) rc = mlp_bf16_prepare(ctx);
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMalloc(&m->packed, (size_t)p.packed_bytes), "hipMalloc(mlp_bf16 packed)");
+    if (rc != DLRM_OK) {
+        delete m;
+        return rc;
+    }
+    *out = m;
+    return DLRM_OK;
+}
+
+int dlrm_mlp_bf16_destroy(dlrm_mlp_bf16* mlp) {
+    if (!mlp) return DLRM_OK;
+    if (mlp->packed) (void)hipFree(mlp->packed);
+    delete mlp;
+    return DLRM_OK;
+}
+
+int dlrm_mlp_bf16_pack(dlrm_ctx* ctx, dlrm_mlp_bf16* mlp, const float* const* W, const int64_t* w_ld,
+                       const float* const* b) {
+    CHECK_ARG(ctx && mlp && W && w_ld && b, "dlrm_mlp_bf16_pack: null argument");
+    const int layers = (int)mlp->sizes.size() - 1;
+    for (int l = 0; l < layers; ++l) {
+        CHECK_ARG(W[l] && b[l], "dlrm_mlp_bf16_pack: layer %d has no weights or no bias", l);
+        CHECK_ARG(w_ld[l] >= mlp->sizes[l], "dlrm_mlp_bf16_pack: layer %d: w_ld %lld < its %d inputs", l,
+                  (long long)w_ld[l], mlp->sizes[l]);
+    }
+    MlpPlan p;
+    int rc = plan_mlp(layers, mlp->sizes.data(), 0, DLRM_F32, DLRM_F32, 0, &p);
+    if (rc == DLRM_OK) rc = launch_mlp_bf16_pack(ctx, p, mlp->packed, W, w_ld, b);
+    if (rc == DLRM_OK) mlp->is_packed = true;
+    return rc;
+}
+
+int dlrm_mlp_bf16_infer(dlrm_ctx* ctx, const dlrm_mlp_bf16* mlp, int batch, const void* x, int x_dtype, int64_t x_ld,
+                        void* out, int out_dtype, int64_t out_ld, int last_relu) {
+    CHECK_ARG(ctx && mlp, "dlrm_mlp_bf16_infer: null ctx/mlp");
+    const int layers = (int)mlp->sizes.size() - 1;
+    MlpPlan p;
+    const int rc = plan_mlp(layers, mlp->sizes.data(), batch, x_dtype, out_dtype, mlp_force_mt(), &p);
+    if (rc != DLRM_OK) return ctx_fail(ctx, rc, "dlrm_mlp_bf16_infer: batch=%d x_dtype=%d out_dtype=%d", batch, x_dtype, out_dtype);
+    CHECK_ARG(x_ld >= mlp->sizes[0] && out_ld >= mlp->sizes[layers], "dlrm_mlp_bf16_infer: x_ld %lld / out_ld %lld too small",
+              (long long)x_ld, (long long)out_ld);
+    CHECK_ARG(batch == 0 || (x && out), "dlrm_mlp_bf16_infer: null buffer");
+    if (!mlp->is_packed) return ctx_fail(ctx, DLRM_E_STATE, "dlrm_mlp_bf16_infer: dlrm_mlp_bf16_pack has not run");
+    return launch_mlp_bf16_chain(ctx, p, mlp->packed, batch, x, x_dtype, x_ld, out, out_dtype, out_ld, last_relu != 0);
 }
 
 int dlrm_interact_bwd(dlrm_ctx* ctx, int dtype, int d, int num_features, int batch, const void* dout, int64_t dout_ld,

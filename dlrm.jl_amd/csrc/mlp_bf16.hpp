@@ -1,0 +1,17 @@
+// mlp_bf16.hpp — the fused bf16 MLP inference chain: mlp_bf16.hip's launchers (called by abi.cpp).
+#pragma once
+#include "common.hpp"
+#include "mlp_plan.hpp"
+
+namespace dlrm {
+
+// Raises the chain kernels' dynamic-LDS limit to kMlpLdsMax - kMlpStaticLds: off the launch path (a create's job).
+int mlp_bf16_prepare(dlrm_ctx* ctx);
+// One launch for every layer: W[l] fp32 [N][K] with leading dimension w_ld[l], b[l] fp32 [N] -> packed (mlp_plan.hpp).
+int launch_mlp_bf16_pack(dlrm_ctx* ctx, const MlpPlan& p, void* packed, const float* const* W, const int64_t* w_ld,
+                         const float* const* b);
+// One launch for the whole chain; p is the plan of this batch and these dtypes.
+int launch_mlp_bf16_chain(dlrm_ctx* ctx, const MlpPlan& p, const void* packed, int batch, const void* x, int x_dtype,
+                          int64_t x_ld, void* out, int out_dtype, int64_t out_ld, bool last_relu);
+
+}  // namespace dlrm

@@ -62,6 +62,7 @@ class DenseMLP:
         self.flat_param = self.flat_grad = None
         self._ws = {}  # (layer, batch) -> dlrm_relu_bwd_bias scratch
         self._context = None
+        self._bf16 = None  # the packed bf16 chain (bf16_chain)
 
     def flatten(self):
         """Re-homes every weight/bias AND its gradient as views of two flat fp32 buffers with the
@@ -117,9 +118,22 @@ class DenseMLP:
         self._logits = logits and self.sigmoid_last
         return acts[-1]
 
-    def infer(self, x, *, logits=False):
+    def bf16_chain(self):
+        """The MLP's packed bf16 form (`mlp_bf16.Bf16MLP`), built and packed on first use; `.repack()` it after the
+        weights change."""
+        if self._bf16 is None:
+            from .mlp_bf16 import Bf16MLP
+            self._bf16 = Bf16MLP(self)
+        return self._bf16
+
+    def infer(self, x, *, logits=False, bf16=False, out_dtype=None):
         """`forward` without keeping anything: the activations of the last training forward (what its
-        backward reads) stay as they are."""
+        backward reads) stay as they are.  bf16: the whole chain in one launch on bf16 operands
+        (`bf16_chain().infer`, x float32 or bfloat16, the result of `out_dtype`, default float32), from the
+        weights as last packed; a chain without that kernel raises."""
+        if bf16:
+            y = self.bf16_chain().infer(x, out_dtype=out_dtype)
+            return torch.sigmoid(y) if self.sigmoid_last and not logits else y
         n = len(self.W)
         for i in range(n):
             if i == n - 1 and self.sigmoid_last:
@@ -256,14 +270,28 @@ class DLRMModel:
                                         index_base=self.hot.index_base, pad_to=self._pad_to))
         return self._q8[1]
 
-    def predict(self, dense, sparse, q8=None):
+    def repack(self):
+        """Packs both MLPs' current weights for `predict(..., mlp="bf16")` (two launches): after training steps."""
+        self.bottom.bf16_chain().repack()
+        self.top.bf16_chain().repack()
+
+    def predict(self, dense, sparse, q8=None, mlp=None):
         """The model call for evaluation: the logits [B][1] of a batch (the sigmoid is `Evaluator.add`'s, with
         dlrm_bce_head's expression).  Bottom MLP, `HotPath.infer`, top MLP: nothing a training step keeps is
         touched -- no indexer, no saved activation, no optimizer state -- so it can run between two steps.
         q8: a `QuantizedTableSet` of the model's tables (`quantize()`); the hot-path forward is then
-        `Q8Inference.infer` over it."""
+        `Q8Inference.infer` over it.
+        mlp="bf16": each MLP is one fused bf16 launch (`DenseMLP.infer(bf16=True)`) on the weights as last packed
+        (`repack()`): the bottom chain writes x in the tables' dtype, the top chain reads the hot path's output in
+        that dtype and writes the fp32 logits, so no conversion is launched.  Composes with q8."""
+        if mlp not in (None, "fp32", "bf16"):
+            raise ValueError(f'mlp is "fp32" or "bf16", not {mlp!r}')
         if not isinstance(sparse, PackedIndices):
             sparse = PackedIndices(sparse, device=self.tables.device)
+        if mlp == "bf16":
+            x = self.bottom.infer(dense, bf16=True, out_dtype=self.tdtype)
+            out = self.hot.infer(x, sparse) if q8 is None else self._q8_engine(q8).infer(x, sparse)
+            return self.top.infer(out, logits=True, bf16=True)
         x = self.bottom.infer(dense)
         if q8 is None:
             out = self.hot.infer(x.to(self.tdtype), sparse)
@@ -271,18 +299,20 @@ class DLRMModel:
             out = self._q8_engine(q8).infer(x.to(self.tdtype), sparse)
         return self.top.infer(out.float(), logits=True)
 
-    def test(self, data, record=None, evaluator=None, probs=None, q8=None):
+    def test(self, data, record=None, evaluator=None, probs=None, q8=None, mlp=None):
         """The reference's `test(model, data; record, strategy)` (src/train/utils.jl:31-46): for every
         (labels, dense, sparse) of `data` (a `DACLoader`, or any iterable of such batches of the model's batch
         size), `predict` and one `Evaluator.add`; one synchronisation, at the end.  Appends the accuracy
         (correct / total) to `record` and returns `Evaluator.result()`: dict(total, correct, accuracy, logloss,
         auc, positives, negatives).  evaluator: an `Evaluator` to use (reset first; its state holds this pass
         afterwards); probs: a list that receives every batch's probabilities (a device tensor each); q8: score
-        the quantized tables (`predict`'s q8)."""
+        the quantized tables (`predict`'s q8); mlp: `predict`'s mlp ("bf16": the MLPs are packed once, here)."""
         dev = self.tables.device
         ev = Evaluator(dev) if evaluator is None else evaluator.reset()
+        if mlp == "bf16":
+            self.repack()
         for labels, dense, sparse in data:
-            z = self.predict(dense, sparse, q8=q8)
+            z = self.predict(dense, sparse, q8=q8, mlp=mlp)
             check_labels(labels, z)
             p = None
             if probs is not None:

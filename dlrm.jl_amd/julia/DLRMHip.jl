@@ -1397,4 +1397,55 @@ function infer(dot::HipDotInteraction, x::DeviceMatrix{T}, q8::HipQ8Tables{D}, s
     return out
 end
 
+#####
+##### fused bf16 MLP inference: a Dense chain in one launch (include/dlrm_hip.h)
+#####
+
+"""
+    HipBf16MLP(ctx, weights, biases)
+
+A chain of Dense layers for scoring: `weights[l]` is Flux's `out × in` `Float32` matrix, `biases[l]` its
+`out` vector.  The weights are uploaded, rounded to bf16 and packed in MFMA operand order by one launch;
+`infer!` then runs the whole chain in one launch (relu on every layer but the last).
+"""
+mutable struct HipBf16MLP
+    ctx::Context
+    sizes::Vector{Cint}
+    ptr::Ptr{Cvoid}
+end
+function HipBf16MLP(ctx::Context, weights::AbstractVector{<:AbstractMatrix{Float32}},
+                    biases::AbstractVector{<:AbstractVector{Float32}})
+    sizes = Cint[size(first(weights), 2); [size(w, 1) for w in weights]]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ctx, ccall((:dlrm_mlp_bf16_create, libdlrm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}, Ref{Ptr{Cvoid}}),
+                     ctx.ptr, length(weights), sizes, out))
+    mlp = HipBf16MLP(ctx, sizes, out[])
+    finalizer(x -> ccall((:dlrm_mlp_bf16_destroy, libdlrm), Cint, (Ptr{Cvoid},), x.ptr), mlp)
+    # Julia's (out, in) column-major is C [in][out]: the kernel reads C [out][in], the transpose
+    ws = [upload!(DeviceMatrix{Float32}(ctx, size(w, 2), size(w, 1)), permutedims(w)) for w in weights]
+    bs = [upload!(DeviceMatrix{Float32}(ctx, length(b), 1), reshape(collect(b), :, 1)) for b in biases]
+    wp, bp = [m.ptr for m in ws], [m.ptr for m in bs]
+    lds = Int64[size(m, 1) for m in ws]
+    check(ctx, ccall((:dlrm_mlp_bf16_pack, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Ptr{Cvoid}}),
+                     ctx.ptr, mlp.ptr, wp, lds, bp))
+    check(ctx, ccall((:dlrm_sync, libdlrm), Cint, (Ptr{Cvoid},), ctx.ptr))  # (the staging copies go out of scope)
+    return mlp
+end
+
+"""
+    infer!(out::DeviceMatrix, mlp::HipBf16MLP, x::DeviceMatrix; last_relu = false)
+
+`out` (`sizes[end] × B`) = the chain applied to `x` (`sizes[1] × B`), either of `Float32` or a 2-byte bf16 type.
+"""
+function infer!(out::DeviceMatrix{TO}, mlp::HipBf16MLP, x::DeviceMatrix{TX}; last_relu::Bool = false) where {TO,TX}
+    B = size(x, 2)
+    @assert size(x, 1) == mlp.sizes[1] && size(out) == (mlp.sizes[end], B)
+    check(mlp.ctx, ccall((:dlrm_mlp_bf16_infer, libdlrm), Cint,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Cint, Int64, Cint),
+                         mlp.ctx.ptr, mlp.ptr, B, x.ptr, dtype_code(TX), size(x, 1), out.ptr, dtype_code(TO),
+                         size(out, 1), Cint(last_relu)))
+    return out
+end
+
 end # module

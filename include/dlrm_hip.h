@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DLRM_HIP_ABI_VERSION 3
+#define DLRM_HIP_ABI_VERSION 4
 
 typedef enum {
     DLRM_OK = 0,
@@ -888,6 +888,37 @@ int dlrm_q8_maplookup(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const void* indic
 int dlrm_q8_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const void* indices, int itype,
                                 int64_t table_stride, int index_base, int batch, int lookups, int dtype,
                                 const void* x, int64_t x_ld, void* out, int64_t out_ld, int padding);
+
+/* ---- fused bf16 MLP inference: a whole Dense chain in one launch -------------------------
+ * A chain of `layers` Dense layers, a_{l+1} = act_l(a_l W_l^T + b_l), with sizes[0 .. layers] the widths
+ * (layer l: W_l is [sizes[l+1]][sizes[l]], Flux's orientation).  Arithmetic: W_l and the input rounded to
+ * bf16 (ties to even); products exact, accumulated in fp32 (v_mfma_f32_16x16x32_bf16); the fp32 bias added
+ * in fp32; relu on every layer but the last, whose activation is relu (last_relu != 0) or the identity;
+ * every hidden activation rounded to bf16 and kept in LDS; the last layer's fp32 value stored as it is
+ * (out fp32) or rounded once (out bf16).  Scoring only: there is no backward, and training keeps its fp32
+ * GEMMs.  No reference counterpart (DLRM.jl's Dense layers are Float32 on OneDNN).
+ * plan:    pure host, no device call.  The tile height mt (16 or 32 batch rows per workgroup of 256 threads),
+ *          the grid ceil(batch / mt), the dynamic LDS bytes 2 * mt * (wmax + 8) * 2 with wmax the largest
+ *          kp[l], the bytes of the packed buffer, and per layer kp[l] = ceil32(sizes[l]) and
+ *          np[l] = ceil16(sizes[l+1]) (kp, np: `layers` ints each, or NULL).  DLRM_E_UNSUPPORTED for more than
+ *          8 layers or a width whose ceil16 exceeds 1024; DLRM_E_ARG for layers <= 0, a width <= 0, a
+ *          negative batch or a dtype that is neither DLRM_F32 nor DLRM_BF16.
+ * create:  allocates the packed buffer, owned by the handle: layer l's weights as bf16
+ *          [np/16][kp/32][64 lanes][8], lane (c = lane % 16, q = lane / 16) of block (nb, kb) holding
+ *          W[16 nb + c][32 kb + 8 q .. 8 q + 7], zero where padded; then the fp32 biases [np], zero-padded.
+ * pack:    one launch fills it from fp32 device arrays W[l] (leading dimension w_ld[l] >= sizes[l]) and
+ *          b[l]; call it again after the weights change.  W, w_ld, b: host arrays of `layers` entries.
+ * infer:   one launch: x is [batch][x_ld] of x_dtype, out [batch][out_ld] of out_dtype; DLRM_E_STATE before
+ *          the first pack.  pack and infer allocate nothing and do not synchronise (hipGraph-capturable). */
+typedef struct dlrm_mlp_bf16 dlrm_mlp_bf16;
+int dlrm_mlp_bf16_plan(int layers, const int* sizes, int batch, int x_dtype, int out_dtype, int* mt, int* grid,
+                       int64_t* lds_bytes, int64_t* packed_bytes, int* kp, int* np);
+int dlrm_mlp_bf16_create(dlrm_ctx* ctx, int layers, const int* sizes, dlrm_mlp_bf16** out);
+int dlrm_mlp_bf16_destroy(dlrm_mlp_bf16* mlp);
+int dlrm_mlp_bf16_pack(dlrm_ctx* ctx, dlrm_mlp_bf16* mlp, const float* const* W, const int64_t* w_ld,
+                       const float* const* b);
+int dlrm_mlp_bf16_infer(dlrm_ctx* ctx, const dlrm_mlp_bf16* mlp, int batch, const void* x, int x_dtype,
+                        int64_t x_ld, void* out, int out_dtype, int64_t out_ld, int last_relu);
 
 #ifdef __cplusplus
 }
