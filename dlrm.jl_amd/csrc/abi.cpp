@@ -80,20 +80,23 @@ struct StatePtrs : StateDims {
     E** d_ptr = nullptr;
     std::vector<E*> h_ptr;
 };
+// What a seeded handle rounds with: its seed and one device word, the step (step_word_* below)
+struct StepWord {
+    uint64_t seed = 0;
+    uint64_t* d_step = nullptr;
+};
 // Sparse Adagrad: fp32 state
 struct dlrm_adagrad : StatePtrs<float> {
     bool rowwise = false;  // one word per table row instead of one row
     // the stochastic kind (dlrm_adagrad_create_sr): bf16 tables, the weights' store rounded with the seed and the step
     bool stochastic = false;
-    uint64_t seed = 0;
-    uint64_t* d_step = nullptr;  // one device word, as dlrm_sr_sgd's
+    StepWord sr;
 };
 // The low halves of split-bf16 tables
 struct dlrm_split_sgd : StatePtrs<uint16_t> {};
-// Stochastically rounded SGD on bf16 tables: no per-row state, a seed and one device word, the step
+// Stochastically rounded SGD on bf16 tables: no per-row state
 struct dlrm_sr_sgd : StateDims {
-    uint64_t seed = 0;
-    uint64_t* d_step = nullptr;
+    StepWord sr;
 };
 
 // An optimizer rule on the host: what every call site asks of one, indexed by kRule* (common.hpp).  The arithmetic
@@ -111,27 +114,30 @@ struct RuleDesc {
     ApplyFn* step_apply;    // the training step's
 };
 static const RuleDesc kRules[kNumRules] = {
-    {"dlrm_sgd_update", "dlrm_step_bwd", "Descent", nullptr, nullptr, nullptr, 0u, launch_sgd_apply, launch_sgd_apply},
+    {"dlrm_sgd_update", "dlrm_step_bwd", "Descent", nullptr, nullptr, nullptr, 0u, launch_rule_apply<Descent>,
+     launch_rule_apply<Descent>},
     {"dlrm_split_sgd_update", "dlrm_split_step_bwd", "the split rule", "the low halves were",
      "split tables are bf16 (the high halves)", "a row's two halves are stepped together", DLRM_IX_SINGLES_SPLIT,
-     launch_split_sgd_apply, launch_split_step_apply},
+     launch_rule_apply<SplitDescent>, launch_rule_step_apply<SplitDescent>},
     // (the two Adagrad rules share their entry points: the kind comes from the handle)
     {"dlrm_adagrad_update", "dlrm_adagrad_step_bwd", "the element-wise Adagrad rule", "the optimizer state was", nullptr,
-     "the rule needs each row's complete sum", DLRM_IX_SINGLES_ADAGRAD, launch_adagrad_apply, launch_adagrad_step_apply},
+     "the rule needs each row's complete sum", DLRM_IX_SINGLES_ADAGRAD, launch_rule_apply<Adagrad>,
+     launch_rule_step_apply<Adagrad>},
     {"dlrm_adagrad_update", "dlrm_adagrad_step_bwd", "the row-wise Adagrad rule", "the optimizer state was", nullptr,
-     "the rule needs each row's complete sum", DLRM_IX_SINGLES_ROWWISE, launch_rowwise_adagrad_apply,
-     launch_rowwise_adagrad_step_apply},
+     "the rule needs each row's complete sum", DLRM_IX_SINGLES_ROWWISE, launch_rule_apply<RowwiseAdagrad>,
+     launch_rule_step_apply<RowwiseAdagrad>},
     {"dlrm_sr_sgd_update", "dlrm_sr_step_bwd", "the stochastic rule", "the optimizer was",
      "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule rounds each row's complete step once",
-     DLRM_IX_SINGLES_STOCHASTIC, launch_sr_sgd_apply, launch_sr_step_apply},
+     DLRM_IX_SINGLES_STOCHASTIC, launch_rule_apply<StochasticDescent>, launch_rule_step_apply<StochasticDescent>},
     // (the Adagrad rules of a dlrm_adagrad_create_sr handle: a step backward of their own, dlrm_sr_adagrad_step_bwd --
     // dlrm_adagrad_step_bwd refuses the handle)
     {"dlrm_adagrad_update", "dlrm_sr_adagrad_step_bwd", "the stochastic element-wise Adagrad rule", "the optimizer state was",
      "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule needs each row's complete sum",
-     DLRM_IX_SINGLES_SR_ADAGRAD, launch_sr_adagrad_apply, launch_sr_adagrad_step_apply},
+     DLRM_IX_SINGLES_SR_ADAGRAD, launch_rule_apply<StochasticAdagrad>, launch_rule_step_apply<StochasticAdagrad>},
     {"dlrm_adagrad_update", "dlrm_sr_adagrad_step_bwd", "the stochastic row-wise Adagrad rule", "the optimizer state was",
      "stochastic rounding is of bf16 tables (fp32: nothing to round)", "the rule needs each row's complete sum",
-     DLRM_IX_SINGLES_SR_ROWWISE, launch_sr_rowwise_adagrad_apply, launch_sr_rowwise_adagrad_step_apply},
+     DLRM_IX_SINGLES_SR_ROWWISE, launch_rule_apply<StochasticRowwiseAdagrad>,
+     launch_rule_step_apply<StochasticRowwiseAdagrad>},
 };
 
 // The rule of a call, from its handle and scalars
@@ -152,8 +158,8 @@ static BoundRule bind_rule(const dlrm_adagrad* op, float lr, float eps) {
     BoundRule r = bind_rule(lr);
     r.kind = op->stochastic ? (op->rowwise ? kRuleStochasticRowwise : kRuleStochasticAdagrad)
                             : (op->rowwise ? kRuleRowwise : kRuleAdagrad);
-    r.seed = op->seed;
-    r.step = op->d_step;
+    r.seed = op->sr.seed;
+    r.step = op->sr.d_step;
     r.eps = eps;
     r.state = op->d_ptr;
     r.aligned16 = op->rowwise || op->aligned16;  // (a row-wise state word is loaded alone)
@@ -163,8 +169,8 @@ static BoundRule bind_rule(const dlrm_adagrad* op, float lr, float eps) {
 static BoundRule bind_rule(const dlrm_sr_sgd* op, float lr) {
     BoundRule r = bind_rule(lr);
     r.kind = kRuleStochastic;
-    r.seed = op->seed;
-    r.step = op->d_step;
+    r.seed = op->sr.seed;
+    r.step = op->sr.d_step;
     r.handle = op;
     return r;
 }
@@ -342,6 +348,40 @@ static int state_destroy(OP* op) {
     if (op->d_ptr) (void)hipFree(op->d_ptr);
     delete op;
     return DLRM_OK;
+}
+
+// A seeded handle's StepWord.  fn: the entry point, what: the word in the HIP messages ("hipMalloc(WHAT)").
+// The Philox counter holds the table in 16 bits and the column's block of four in 16 bits
+static int step_word_limits(dlrm_ctx* ctx, const dlrm_tables* tb, const char* fn) {
+    CHECK_ARG(tb->T <= 65536 && (tb->D + 3) / 4 <= 65536, "%s: %d tables of dim %d (at most 65536 tables, dim / 4 at most "
+              "65536)", fn, tb->T, tb->D);
+    return DLRM_OK;
+}
+// (the caller set the device, and frees the word when this fails)
+static int step_word_create(dlrm_ctx* ctx, StepWord& w, int64_t seed, const char* what) {
+    char msg[2][48];
+    snprintf(msg[0], sizeof(msg[0]), "hipMalloc(%s)", what);
+    snprintf(msg[1], sizeof(msg[1]), "hipMemset(%s)", what);
+    w.seed = (uint64_t)seed;
+    int rc = ctx_hip(ctx, hipMalloc((void**)&w.d_step, sizeof(uint64_t)), msg[0]);
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMemset(w.d_step, 0, sizeof(uint64_t)), msg[1]);
+    return rc;
+}
+static void step_word_free(StepWord& w) {
+    if (w.d_step) (void)hipFree(w.d_step);
+}
+static int step_word_seek(dlrm_ctx* ctx, const StepWord& w, int64_t step) {
+    const int rc = hip_set(ctx);
+    if (rc) return rc;
+    return launch_sr_step_set(ctx, w.d_step, (uint64_t)step);
+}
+static int step_word_read(dlrm_ctx* ctx, const StepWord& w, uint64_t* out, const char* what) {
+    char msg[48];
+    snprintf(msg, sizeof(msg), "hipMemcpy(%s)", what);
+    int rc = hip_set(ctx);
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMemcpy(out, w.d_step, sizeof(uint64_t), hipMemcpyDeviceToHost), msg);
+    return rc;
 }
 
 extern "C" {
@@ -1338,8 +1378,7 @@ static int check_rule(dlrm_ctx* ctx, const dlrm_tables* tb, const BoundRule& r, 
 static int check_completes(dlrm_ctx* ctx, const dlrm_indexer* ix, const BoundRule& r, const char* fn, const char* mode) {
     if (!ix->singles_done) return DLRM_OK;
     const bool same_rule = ix->singles_rule == r.kind;
-    const bool seeded = r.kind == kRuleStochastic || r.kind == kRuleStochasticAdagrad || r.kind == kRuleStochasticRowwise;
-    if (same_rule && (!seeded || ix->singles_handle == r.handle)) return DLRM_OK;
+    if (same_rule && (!r.step || ix->singles_handle == r.handle)) return DLRM_OK;  // (r.step: a seeded rule's word)
     const RuleDesc& by = kRules[ix->singles_rule];
     return ctx_fail(ctx, DLRM_E_STATE, "%s%s: a split backward (%s) already stepped this build's once-hit rows with %s%s",
                     fn, mode, by.step_fn, by.name, same_rule ? " of another handle" : "");
@@ -1402,17 +1441,14 @@ int dlrm_adagrad_create_sr(dlrm_ctx* ctx, const dlrm_tables* tb, int rowwise, fl
     CHECK_ARG(ctx && tb && out, "dlrm_adagrad_create_sr: null argument");
     *out = nullptr;
     CHECK_ARG(tb->dtype == DLRM_BF16, "dlrm_adagrad_create_sr: stochastic rounding is of bf16 tables (fp32: nothing to round)");
-    // the Philox counter holds the table in 16 bits and the column's block of four in 16 bits
-    CHECK_ARG(tb->T <= 65536 && (tb->D + 3) / 4 <= 65536, "dlrm_adagrad_create_sr: %d tables of dim %d (at most 65536 "
-              "tables, dim / 4 at most 65536)", tb->T, tb->D);
+    int rc = step_word_limits(ctx, tb, "dlrm_adagrad_create_sr");
+    if (rc) return rc;
     dlrm_adagrad* op = nullptr;
-    int rc = state_create(ctx, tb, false, state, &op, {"dlrm_adagrad_create_sr", "state", "state", "adagrad state"});
+    rc = state_create(ctx, tb, false, state, &op, {"dlrm_adagrad_create_sr", "state", "state", "adagrad state"});
     if (rc) return rc;
     op->rowwise = rowwise != 0;
     op->stochastic = true;
-    op->seed = (uint64_t)seed;
-    rc = ctx_hip(ctx, hipMalloc((void**)&op->d_step, sizeof(uint64_t)), "hipMalloc(adagrad step)");
-    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMemset(op->d_step, 0, sizeof(uint64_t)), "hipMemset(adagrad step)");
+    rc = step_word_create(ctx, op->sr, seed, "adagrad step");
     if (rc != DLRM_OK) {
         (void)dlrm_adagrad_destroy(op);
         return rc;
@@ -1422,26 +1458,20 @@ int dlrm_adagrad_create_sr(dlrm_ctx* ctx, const dlrm_tables* tb, int rowwise, fl
 }
 
 int dlrm_adagrad_destroy(dlrm_adagrad* op) {
-    if (op && op->d_step) (void)hipFree(op->d_step);
+    if (op) step_word_free(op->sr);
     return state_destroy(op);
 }
 
 int dlrm_adagrad_seek(dlrm_ctx* ctx, dlrm_adagrad* op, int64_t step) {
     CHECK_ARG(ctx && op, "dlrm_adagrad_seek: null ctx/optimizer");
     CHECK_ARG(op->stochastic, "dlrm_adagrad_seek: the handle has no step (dlrm_adagrad_create_sr makes one that has)");
-    const int rc = hip_set(ctx);
-    if (rc) return rc;
-    return launch_sr_step_set(ctx, op->d_step, (uint64_t)step);
+    return step_word_seek(ctx, op->sr, step);
 }
 
 int dlrm_adagrad_step(dlrm_ctx* ctx, dlrm_adagrad* op, uint64_t* out) {
     CHECK_ARG(ctx && op && out, "dlrm_adagrad_step: null ctx/optimizer/out");
     CHECK_ARG(op->stochastic, "dlrm_adagrad_step: the handle has no step (dlrm_adagrad_create_sr makes one that has)");
-    int rc = hip_set(ctx);
-    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    if (rc == DLRM_OK)
-        rc = ctx_hip(ctx, hipMemcpy(out, op->d_step, sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy(adagrad step)");
-    return rc;
+    return step_word_read(ctx, op->sr, out, "adagrad step");
 }
 
 int dlrm_adagrad_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_adagrad* op, dlrm_indexer* ix, unsigned flags,
@@ -1470,20 +1500,16 @@ int dlrm_sr_sgd_create(dlrm_ctx* ctx, const dlrm_tables* tb, int64_t seed, dlrm_
     CHECK_ARG(ctx && tb && out, "dlrm_sr_sgd_create: null argument");
     *out = nullptr;
     CHECK_ARG(tb->dtype == DLRM_BF16, "dlrm_sr_sgd_create: stochastic rounding is of bf16 tables (fp32: nothing to round)");
-    // the Philox counter holds the table in 16 bits and the column's block of four in 16 bits
-    CHECK_ARG(tb->T <= 65536 && (tb->D + 3) / 4 <= 65536, "dlrm_sr_sgd_create: %d tables of dim %d (at most 65536 tables, "
-              "dim / 4 at most 65536)", tb->T, tb->D);
+    int rc = step_word_limits(ctx, tb, "dlrm_sr_sgd_create");
+    if (rc) return rc;
     dlrm_sr_sgd* op = new (std::nothrow) dlrm_sr_sgd();
     if (!op) return DLRM_E_NOMEM;
     op->T = tb->T;
     op->D = tb->D;
-    op->seed = (uint64_t)seed;
-    int rc = hip_set(ctx);
-    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMalloc((void**)&op->d_step, sizeof(uint64_t)), "hipMalloc(sr step)");
-    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMemset(op->d_step, 0, sizeof(uint64_t)), "hipMemset(sr step)");
+    rc = hip_set(ctx);
+    if (rc == DLRM_OK) rc = step_word_create(ctx, op->sr, seed, "sr step");
     if (rc != DLRM_OK) {
-        if (op->d_step) (void)hipFree(op->d_step);
-        delete op;
+        (void)dlrm_sr_sgd_destroy(op);
         return rc;
     }
     *out = op;
@@ -1492,7 +1518,7 @@ int dlrm_sr_sgd_create(dlrm_ctx* ctx, const dlrm_tables* tb, int64_t seed, dlrm_
 
 int dlrm_sr_sgd_destroy(dlrm_sr_sgd* op) {
     if (!op) return DLRM_OK;
-    if (op->d_step) (void)hipFree(op->d_step);
+    step_word_free(op->sr);
     delete op;
     return DLRM_OK;
 }
@@ -1507,17 +1533,12 @@ int dlrm_sr_sgd_update(dlrm_ctx* ctx, dlrm_tables* tb, dlrm_sr_sgd* op, dlrm_ind
 
 int dlrm_sr_sgd_seek(dlrm_ctx* ctx, dlrm_sr_sgd* op, int64_t step) {
     CHECK_ARG(ctx && op, "dlrm_sr_sgd_seek: null ctx/optimizer");
-    const int rc = hip_set(ctx);
-    if (rc) return rc;
-    return launch_sr_step_set(ctx, op->d_step, (uint64_t)step);
+    return step_word_seek(ctx, op->sr, step);
 }
 
 int dlrm_sr_sgd_step(dlrm_ctx* ctx, dlrm_sr_sgd* op, uint64_t* out) {
     CHECK_ARG(ctx && op && out, "dlrm_sr_sgd_step: null ctx/optimizer/out");
-    int rc = hip_set(ctx);
-    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMemcpy(out, op->d_step, sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy(sr step)");
-    return rc;
+    return step_word_read(ctx, op->sr, out, "sr step");
 }
 
 // ----------------------------------------------------------------------- training step

@@ -7,13 +7,5 @@
 #include "apply_kernel.hpp"
 
 namespace dlrm {
-
-// (r.state: the device array of per-table fp32 [nrows][D] state pointers)
-int launch_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T_, int D, int tdtype,
-                         int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
-                         const BoundRule& r, const SinglesArgs& sa, const PrepArgs*) {
-    return launch_apply_rule(ctx, ix, tabs, aligned16, T_, D, tdtype, L, N, grad, gdtype, grad_ld, grad_offset,
-                             Adagrad{r.lr, r.eps, (float* const*)r.state}, sa, nullptr);
-}
-
+template ApplyFn launch_rule_apply<Adagrad>;
 }  // namespace dlrm

@@ -200,8 +200,8 @@ struct Adagrad {
     typedef float State;
     static constexpr int kState = 1;
     static constexpr bool kStochastic = false;
-    // MODE >= 2 over the training step's fp32 dt, in a unit of its own (adagrad_step.hip:
-    // launch_adagrad_step_apply), so adagrad.hip stays the MODE 0 / 1 unit it was
+    // MODE >= 2 over the training step's fp32 dt, in a unit of its own (launch_rule_step_apply's), so the unit of
+    // launch_rule_apply stays the MODE 0 / 1 unit it was
     static constexpr bool kCarriesBuild = true;
     static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = true;
@@ -230,7 +230,7 @@ struct RowwiseAdagrad {
     typedef float State;
     static constexpr int kState = 2;
     static constexpr bool kStochastic = false;
-    // (MODE >= 2: adagrad_rowwise_step.hip, launch_rowwise_adagrad_step_apply)
+    // (MODE >= 2: as Adagrad)
     static constexpr bool kCarriesBuild = true;
     static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = true;
@@ -261,8 +261,7 @@ struct SplitDescent {
     typedef uint16_t State;
     static constexpr int kState = 3;
     static constexpr bool kStochastic = false;
-    // MODE >= 2 over bf16 tables and the training step's fp32 dt, in a unit of their own (split_step.hip:
-    // launch_split_step_apply), so split_sgd.hip stays the MODE 0 / 1 unit it was
+    // (MODE >= 2 over bf16 tables and the training step's fp32 dt: as Adagrad)
     static constexpr bool kCarriesBuild = true;
     static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = false;  // split rows live in bf16 tables
@@ -326,8 +325,7 @@ struct StochasticDescent {
     typedef float State;
     static constexpr int kState = 4;
     static constexpr bool kStochastic = true;  // (rule_store: its store<NE>; the kernels call its load_step)
-    // MODE >= 2 over the training step's fp32 dt, in a unit of its own (sr_step.hip: launch_sr_step_apply), so
-    // sr_sgd.hip stays the MODE 0 / 1 unit it was
+    // (MODE >= 2: as Adagrad)
     static constexpr bool kCarriesBuild = true;
     static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = false;  // fp32 tables: nothing to round
@@ -427,8 +425,7 @@ struct SrWord {
 
 struct StochasticAdagrad : Adagrad, SrWord {
     static constexpr bool kStochastic = true;
-    // MODE >= 2 over the training step's fp32 dt, in a unit of its own (sr_adagrad_step.hip), so sr_adagrad.hip stays
-    // the MODE 0 / 1 unit it was
+    // (MODE >= 2: as Adagrad)
     static constexpr bool kCarriesBuild = true;
     static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = false;     // fp32 tables: nothing to round
@@ -453,7 +450,7 @@ struct StochasticAdagrad : Adagrad, SrWord {
 
 struct StochasticRowwiseAdagrad : RowwiseAdagrad, SrWord {
     static constexpr bool kStochastic = true;
-    static constexpr bool kCarriesBuild = true;  // (sr_adagrad_rowwise_step.hip, as StochasticAdagrad)
+    static constexpr bool kCarriesBuild = true;
     static constexpr bool kBuildWithApply = false;
     static constexpr bool kF32Tables = false;
     // (the parent's count, and half of it for fp32 gradient rows of 16 vectors: as StochasticAdagrad)
@@ -481,6 +478,26 @@ struct StochasticRowwiseAdagrad : RowwiseAdagrad, SrWord {
         }
     }
 };
+
+// ---- a rule struct from the rule bound to a call (host): the one place that gives a BoundRule's untyped fields a
+// rule's types.  state_of: the handle's per-table pointers to the rule's second stream; sr_word: the seed's halves and
+// the step word (its value comes in the kernel, by load_step).  The step backward's StepUpdate types (interact.hip)
+// take theirs from the same two.
+template <typename E> inline E* const* state_of(const BoundRule& r) { return (E* const*)r.state; }
+inline SrWord sr_word(const BoundRule& r) { return {(uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.step, 0u, 0u}; }
+template <typename R> R make_rule(const BoundRule& r);
+template <> inline Descent make_rule(const BoundRule& r) { return {r.lr}; }
+template <> inline Adagrad make_rule(const BoundRule& r) { return {r.lr, r.eps, state_of<float>(r)}; }
+template <> inline RowwiseAdagrad make_rule(const BoundRule& r) { return {r.lr, r.eps, state_of<float>(r)}; }
+template <> inline SplitDescent make_rule(const BoundRule& r) { return {r.lr, state_of<uint16_t>(r)}; }
+template <> inline StochasticDescent make_rule(const BoundRule& r) {
+    const SrWord w = sr_word(r);
+    return {r.lr, w.k0, w.k1, w.step, w.s0, w.s1};
+}
+template <> inline StochasticAdagrad make_rule(const BoundRule& r) { return {make_rule<Adagrad>(r), sr_word(r)}; }
+template <> inline StochasticRowwiseAdagrad make_rule(const BoundRule& r) {
+    return {make_rule<RowwiseAdagrad>(r), sr_word(r)};
+}
 
 // Whether the apply kernel makes a lane's group constants again in every chunk and once-hit item (R::kRederiveLane):
 // the stochastic Adagrad rules, whose kernels hold a state stream and the Philox rounds under the 168 registers of

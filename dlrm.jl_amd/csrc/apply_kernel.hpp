@@ -1,9 +1,8 @@
 // apply_kernel.hpp -- the apply launch of update! (sgd_apply_kernel over apply.hpp's work items), its
-// any-D fallback kernels and their launchers, by update rule.  update.hip instantiates Descent
-// (every MODE), adagrad.hip and adagrad_rowwise.hip the Adagrad rules, split_sgd.hip the split rule and sr_sgd.hip
-// the stochastic rule (MODE 0 and 1), and split_step.hip, adagrad_step.hip, adagrad_rowwise_step.hip and sr_step.hip those four
-// rules' build-carrying launches (MODE 2 / 3 / 5), and sr_adagrad.hip and sr_adagrad_rowwise.hip the Adagrad rules with the
-// stochastic store (MODE 0 and 1): they compile side by side.
+// any-D fallback kernels and their launchers, by update rule.  A rule is a struct in apply.hpp, a row in abi.cpp's
+// kRules and two instantiation lines: `template ApplyFn launch_rule_apply<R>;` in one unit (MODE 0 and 1) and
+// `template ApplyFn launch_rule_step_apply<R>;` in another (MODE 2 / 3 / 5), so that the two sets of kernels compile
+// side by side.  (Descent, with kBuildWithApply, has every MODE behind launch_rule_apply, in update.hip.)
 #pragma once
 #include "apply.hpp"
 
@@ -436,8 +435,17 @@ static void by_dtypes(int tdtype, int gdtype, F&& f) {
     return gdtype == DLRM_F32 ? f(uint16_t(), float()) : f(uint16_t(), uint16_t());
 }
 
-// tabs_aligned16: every table row (and, for the element-wise Adagrad and the split rule, every state row) is
-// 16-B aligned
+// Whether the vector kernels take a launch: 16-B vectors of every row (tabs_aligned16: every table row and, for the
+// element-wise Adagrad and the split rule, every state row is 16-B aligned), item counts that stay in int.  TV: the
+// virtual tables.  (A shape that passes still needs a kernel of its D * gesz / 16 vectors per gradient row.)
+static bool apply_vectors(bool tabs_aligned16, int TV, int D, int tdtype, int64_t N, const void* grad, int gdtype,
+                          int64_t grad_ld, int64_t grad_offset) {
+    const int gesz = gdtype == DLRM_F32 ? 4 : 2;
+    const int tesz = tdtype == DLRM_F32 ? 4 : 2;
+    return tabs_aligned16 && (uintptr_t)grad % 16 == 0 && (grad_ld * gesz) % 16 == 0 && (grad_offset * gesz) % 16 == 0 &&
+           (D * gesz) % 16 == 0 && (D * tesz) % 16 == 0 && D % 4 == 0 && (int64_t)TV * (N + 1) < (1ll << 31);
+}
+
 template <typename R>
 static int launch_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool tabs_aligned16, int T_, int D,
                              int tdtype, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
@@ -446,14 +454,9 @@ static int launch_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tab
     T_ <<= ix.vshift;  // virtual tables (row-parity halves) of a forward-launch build
     hipStream_t s = ctx_stream(ctx);
     const unsigned* err = ctx_error_word(ctx);
-    const int gesz = gdtype == DLRM_F32 ? 4 : 2;
-    const int tesz = tdtype == DLRM_F32 ? 4 : 2;
-    const bool aligned = tabs_aligned16 && (uintptr_t)grad % 16 == 0 && (grad_ld * gesz) % 16 == 0 &&
-                         (grad_offset * gesz) % 16 == 0 && (D * gesz) % 16 == 0 && (D * tesz) % 16 == 0 && D % 4 == 0;
     bool done = false;
-    const int64_t slots = (int64_t)T_ * (N + 1);  // (item counts stay in int)
-    if (aligned && slots < (1ll << 31)) {
-        const int vpr = D * gesz / 16;
+    if (apply_vectors(tabs_aligned16, T_, D, tdtype, N, grad, gdtype, grad_ld, grad_offset)) {
+        const int vpr = D * (gdtype == DLRM_F32 ? 4 : 2) / 16;
         by_dtypes<R>(tdtype, gdtype, [&](auto tt, auto gt) {
             done = dispatch_apply<decltype(tt), decltype(gt), R>(vpr, s, ix, tabs, T_, L, grad, grad_ld, grad_offset, rule, N,
                                                                  err, sa, pa);
@@ -480,5 +483,70 @@ static int launch_apply_rule(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tab
     return ctx_hip(ctx, hipGetLastError(), "sgd_apply launch");
 }
 
+// The two ApplyFn bodies of a rule (common.hpp).  The update's: launch_apply_rule with the rule of the call.  A rule
+// without kF32Tables has bf16 tables (the caller checked); only a rule with kBuildWithApply takes `pa` here.  A
+// stochastic rule's ends with the advance of its step word, after the last launch that read it: when something was
+// launched.
+template <typename R>
+int launch_rule_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T_, int D, int tdtype,
+                      int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
+                      const BoundRule& r, const SinglesArgs& sa, const PrepArgs* pa) {
+    const int rc = launch_apply_rule(ctx, ix, tabs, aligned16, T_, D, R::kF32Tables ? tdtype : DLRM_BF16, L, N, grad,
+                                     gdtype, grad_ld, grad_offset, make_rule<R>(r), sa, R::kBuildWithApply ? pa : nullptr);
+    if constexpr (R::kStochastic) {
+        if (rc == DLRM_OK && T_ > 0 && N > 0) return launch_sr_step_advance(ctx, r.step);
+    }
+    return rc;
+}
+
+// The training step's, over its fp32 dt rows (L = 1): with `pa` and no once-hit items the launch carries the build
+// (MODE 2 / 3 / 5: the build's workgroups first, then chunks and hot slices) where the shape has a vector kernel, and
+// then advances a stochastic rule's step word itself.  Otherwise the rule's MODE 0 / 1 launches, which advance the word
+// themselves, then the build's own.  Only what the step needs is instantiated: fp32 (a rule with kF32Tables) and bf16
+// tables.
+template <typename R>
+int launch_rule_step_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T_, int D, int tdtype,
+                           int, int64_t N, const void* dt, int, int64_t dt_ld, int64_t dt_offset, const BoundRule& r,
+                           const SinglesArgs& sa, const PrepArgs* pa) {
+    if (!R::kF32Tables) tdtype = DLRM_BF16;
+    const int TV = T_ << ix.vshift;  // virtual tables (row-parity halves) of a forward-launch build
+    if (pa && !sa.single && T_ > 0 && N > 0 &&
+        apply_vectors(aligned16, TV, D, tdtype, N, dt, DLRM_F32, dt_ld, dt_offset)) {
+        hipStream_t s = ctx_stream(ctx);
+        const unsigned* err = ctx_error_word(ctx);
+        const R rule = make_rule<R>(r);
+        bool done = true;
+        switch (D / 4) {  // 16-B vectors per fp32 gradient row
+#define DLRM_CASE(V)                                                                                                   \
+    case V:                                                                                                            \
+        if (tdtype == DLRM_F32) {                                                                                      \
+            if constexpr (R::kF32Tables)                                                                               \
+                launch_apply_build_vec<float, float, V, R, 2>(s, ix, tabs, TV, 1, dt, dt_ld, dt_offset, rule, N, err, sa, \
+                                                              *pa);                                                    \
+        } else                                                                                                         \
+            launch_apply_build_vec<uint16_t, float, V, R, 2>(s, ix, tabs, TV, 1, dt, dt_ld, dt_offset, rule, N, err, sa, \
+                                                             *pa);                                                     \
+        break;
+            DLRM_CASE(2) DLRM_CASE(4) DLRM_CASE(8) DLRM_CASE(16) DLRM_CASE(32) DLRM_CASE(64) DLRM_CASE(128)
+#undef DLRM_CASE
+            default: done = false;
+        }
+        if (done) {
+            const int rc = ctx_hip(ctx, hipGetLastError(), "step apply(+build) launch");
+            if constexpr (R::kStochastic) {
+                if (rc == DLRM_OK) return launch_sr_step_advance(ctx, r.step);
+            }
+            return rc;
+        }
+    }
+    // once-hit items in this launch, or no vector kernel for the shape
+    const int rc = launch_rule_apply<R>(ctx, ix, tabs, aligned16, T_, D, tdtype, 1, N, dt, DLRM_F32, dt_ld, dt_offset, r,
+                                        sa, nullptr);
+    if (rc == DLRM_OK && pa) {
+        launch_step_index(ctx_stream(ctx), *pa);
+        return ctx_hip(ctx, hipGetLastError(), "step_index launch");
+    }
+    return rc;
+}
 
 }  // namespace dlrm

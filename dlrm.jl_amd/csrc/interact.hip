@@ -1839,13 +1839,12 @@ int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, con
     const GatherArgs ga{tabs, idx, itype, tstride, base, 1, ctx_error_word(ctx)};
     const BwdArgs a{d, T_ + 1, B, dout, dout_ld, nullptr, 0, dx, dt, dx_ld, dt_ld, ga, x, x_ld};
     const StepUpdate su{ix.single, ix.cap, r.lr, ctx_error_word(ctx)};
-    float* const* const state = (float* const*)r.state;
-    const uint32_t k0 = (uint32_t)r.seed, k1 = (uint32_t)(r.seed >> 32);
+    float* const* const state = state_of<float>(r);
+    const SrWord w = sr_word(r);
     const auto run = [&](auto e, const auto& rule) { return launch_step_bwd_rule<decltype(e)>(ctx, p, a, rule); };
     switch (r.kind) {
-        case kRuleSplit: return run(uint16_t{}, SplitStepUpdate{su, (uint16_t* const*)r.state});
-        case kRuleStochastic:
-            return run(uint16_t{}, StochasticStepUpdate{su, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.step});
+        case kRuleSplit: return run(uint16_t{}, SplitStepUpdate{su, state_of<uint16_t>(r)});
+        case kRuleStochastic: return run(uint16_t{}, StochasticStepUpdate{su, w.k0, w.k1, w.step});
         case kRuleAdagrad:
             return p.f32 ? run(float{}, AdagradStepUpdate<false>{su, state, r.eps})
                          : run(uint16_t{}, AdagradStepUpdate<false>{su, state, r.eps});
@@ -1855,9 +1854,9 @@ int launch_step_bwd(dlrm_ctx* ctx, const TableDesc* tabs, int T_, int dtype, con
         default: return p.f32 ? run(float{}, su) : run(uint16_t{}, su);
         // (the seeded Adagrad rules last: their kernels are emitted behind every other of the unit)
         case kRuleStochasticAdagrad:
-            return run(uint16_t{}, StochasticAdagradStepUpdate<false>{{su, state, r.eps}, k0, k1, r.step});
+            return run(uint16_t{}, StochasticAdagradStepUpdate<false>{{su, state, r.eps}, w.k0, w.k1, w.step});
         case kRuleStochasticRowwise:
-            return run(uint16_t{}, StochasticAdagradStepUpdate<true>{{su, state, r.eps}, k0, k1, r.step});
+            return run(uint16_t{}, StochasticAdagradStepUpdate<true>{{su, state, r.eps}, w.k0, w.k1, w.step});
     }
 }
 

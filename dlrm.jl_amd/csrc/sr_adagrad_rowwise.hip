@@ -11,18 +11,5 @@
 #include "apply_kernel.hpp"
 
 namespace dlrm {
-
-// (tdtype: bf16, the caller checked; r.state: the device array of per-table fp32 [nrows] state pointers)
-int launch_sr_rowwise_adagrad_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool aligned16, int T_, int D,
-                                    int, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld,
-                                    int64_t grad_offset, const BoundRule& r, const SinglesArgs& sa, const PrepArgs*) {
-    if (T_ == 0 || N == 0) return DLRM_OK;  // (nothing launched: the step stays)
-    const int rc = launch_apply_rule(ctx, ix, tabs, aligned16, T_, D, DLRM_BF16, L, N, grad, gdtype, grad_ld, grad_offset,
-                                     StochasticRowwiseAdagrad{{r.lr, r.eps, (float* const*)r.state},
-                                                              {(uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.step, 0u, 0u}},
-                                     sa, nullptr);
-    if (rc) return rc;
-    return launch_sr_step_advance(ctx, r.step);
-}
-
+template ApplyFn launch_rule_apply<StochasticRowwiseAdagrad>;
 }  // namespace dlrm

@@ -15,8 +15,8 @@
 //     positions.  The same workgroup then lists the segments (one per distinct row): those of
 //     <= kChunk positions as chunks, longer ones (hot rows of small tables: a 3-row table gets
 //     ~680 hits per row at B = 2048) as hot segments.
-//  2. sgd_apply (apply_kernel.hpp; instantiated here for Descent, in adagrad.hip and
-//     adagrad_rowwise.hip for the Adagrad rules): lane groups take one chunk each (grad rows summed in ascending position
+//  2. sgd_apply (apply_kernel.hpp; instantiated here for Descent, in units of their own for the
+//     other rules): lane groups take one chunk each (grad rows summed in ascending position
 //     order, 16-B lanes, 8 rows in flight, the table row prefetched meanwhile) and write the
 //     row once; each hot segment gets a whole workgroup whose lane groups sum fixed-size
 //     sub-chunks into LDS, combined in sub-chunk order before the row is written once.
@@ -836,12 +836,7 @@ int launch_indexer_build(dlrm_ctx* ctx, const IndexerDev& ix, const TableDesc* t
     return ctx_fail(ctx, DLRM_E_ARG, "indexer build: form %d split=%d has no launch of its own", (int)form, (int)split);
 }
 
-int launch_sgd_apply(dlrm_ctx* ctx, const IndexerDev& ix, TableDesc* tabs, bool tabs_aligned16, int T_, int D,
-                     int tdtype, int L, int64_t N, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
-                     const BoundRule& r, const SinglesArgs& sa, const PrepArgs* pa) {
-    return launch_apply_rule(ctx, ix, tabs, tabs_aligned16, T_, D, tdtype, L, N, grad, gdtype, grad_ld, grad_offset,
-                             Descent{r.lr}, sa, pa);
-}
+template ApplyFn launch_rule_apply<Descent>;  // (every MODE: the training step's too)
 
 int launch_sgd_atomic(dlrm_ctx* ctx, TableDesc* tabs, int T_, int D, const void* idx, int itype, int64_t tstride,
                       int base, int B, int L, const void* grad, int gdtype, int64_t grad_ld, int64_t grad_offset,
