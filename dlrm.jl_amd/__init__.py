@@ -15,6 +15,7 @@ from .embedding import (DefaultStrategy, EmbeddingTableSet, PackedIndices, Preal
 from .evaluate import Evaluator, eval_reference
 from .hotpath import HotPath
 from .mlp_bf16 import Bf16MLP, mlp_bf16_plan, mlp_bf16_reference
+from .mlp_train_bf16 import Bf16TrainMLP, mlp_train_bf16_reference, mlp_train_plan
 from .quant import Q8Inference, QuantizedTableSet, dequantize_rows, quantize_rows
 from .lazy import DeferredUpdate, HipTables, LazyGrad, LazyLookup
 from .interact import (POST_INTERACTION_PAD_TO_MUL, DotInteraction, cdiv, dot_back, dot_interaction, fast_vcat,
@@ -38,4 +39,5 @@ __all__ = [
     "StochasticDescent", "sr_round", "sr_bits", "philox4x32_10", "Evaluator", "eval_reference",
     "QuantizedTableSet", "Q8Inference", "quantize_rows", "dequantize_rows",
     "Bf16MLP", "mlp_bf16_plan", "mlp_bf16_reference",
+    "Bf16TrainMLP", "mlp_train_bf16_reference", "mlp_train_plan",
 ]

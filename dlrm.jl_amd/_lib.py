@@ -88,6 +88,13 @@ SIGNATURES = {
     "dlrm_mlp_bf16_destroy": (_i32, [_vp]),
     "dlrm_mlp_bf16_pack": (_i32, [_vp, _vp, _pp, _pi64, _pp]),
     "dlrm_mlp_bf16_infer": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _i32, _i64, _i32]),
+    "dlrm_mlp_train_plan": (_i32, [_i32, _pi32, _i32, _vp]),
+    "dlrm_mlp_train_create": (_i32, [_vp, _i32, _pi32, _i32, _pp]),
+    "dlrm_mlp_train_destroy": (_i32, [_vp]),
+    "dlrm_mlp_train_refresh": (_i32, [_vp, _vp, _pp, _pi64, _vp]),
+    "dlrm_mlp_train_forward": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _pp, _vp, _vp, _vp, _i32, _i64, _i32]),
+    "dlrm_mlp_train_backward": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _pp, _pi64,
+                                       _pp, _i32, _vp, _i32, _i64]),
     "dlrm_interact_bwd": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64]),
     "dlrm_interact_bwd_gather": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _i32,
                                         _vp, _i64, _vp, _i64]),

@@ -24,6 +24,7 @@
 #include "apply.hpp"
 #include "q8.hpp"
 #include "mlp_bf16.hpp"
+#include "mlp_train.hpp"
 
 using namespace dlrm;
 
@@ -68,6 +69,12 @@ struct dlrm_mlp_bf16 {
     void* packed = nullptr;
     int64_t packed_bytes = 0;
     bool is_packed = false;  // dlrm_mlp_bf16_pack has run
+};
+
+// A Dense chain for bf16 training: the widths and the layout of its max_batch (mlp_train_plan.hpp); no memory
+struct dlrm_mlp_train {
+    std::vector<int> sizes;  // layers + 1
+    dlrm_mlp_train_layout layout;
 };
 
 // An optimizer's state of one table set: the caller's per-table pointers, uploaded once
@@ -918,6 +925,87 @@ int dlrm_mlp_bf16_infer(dlrm_ctx* ctx, const dlrm_mlp_bf16* mlp, int batch, cons
     CHECK_ARG(batch == 0 || (x && out), "dlrm_mlp_bf16_infer: null buffer");
     if (!mlp->is_packed) return ctx_fail(ctx, DLRM_E_STATE, "dlrm_mlp_bf16_infer: dlrm_mlp_bf16_pack has not run");
     return launch_mlp_bf16_chain(ctx, p, mlp->packed, batch, x, x_dtype, x_ld, out, out_dtype, out_ld, last_relu != 0);
+}
+
+// ------------------------------------------------------------------- bf16 MLP training
+int dlrm_mlp_train_plan(int layers, const int* sizes, int batch, dlrm_mlp_train_layout* out) {
+    return plan_mlp_train(layers, sizes, batch, out);
+}
+
+int dlrm_mlp_train_create(dlrm_ctx* ctx, int layers, const int* sizes, int max_batch, dlrm_mlp_train** out) {
+    CHECK_ARG(ctx && sizes && out, "dlrm_mlp_train_create: null argument");
+    *out = nullptr;
+    dlrm_mlp_train_layout L;
+    const int rc = plan_mlp_train(layers, sizes, max_batch, &L);
+    if (rc != DLRM_OK)
+        return ctx_fail(ctx, rc, "dlrm_mlp_train_create: %d layers, max_batch %d: 1 .. %d layers of widths 1 .. %d and a "
+                        "batch >= 1 have a kernel", layers, max_batch, kMtMaxLayers, kMtMaxWidth);
+    dlrm_mlp_train* m = new (std::nothrow) dlrm_mlp_train();
+    if (!m) return DLRM_E_NOMEM;
+    m->sizes.assign(sizes, sizes + layers + 1);
+    m->layout = L;
+    *out = m;
+    return DLRM_OK;
+}
+
+int dlrm_mlp_train_destroy(dlrm_mlp_train* mlp) {
+    delete mlp;
+    return DLRM_OK;
+}
+
+static bool mlp_train_dtype(int d) { return d == DLRM_F32 || d == DLRM_BF16; }
+
+int dlrm_mlp_train_refresh(dlrm_ctx* ctx, const dlrm_mlp_train* mlp, const float* const* W, const int64_t* w_ld,
+                           void* w16) {
+    CHECK_ARG(ctx && mlp && W && w_ld && w16, "dlrm_mlp_train_refresh: null argument");
+    for (int l = 0; l < mlp->layout.layers; ++l) {
+        CHECK_ARG(W[l], "dlrm_mlp_train_refresh: layer %d has no weights", l);
+        CHECK_ARG(w_ld[l] >= mlp->sizes[l], "dlrm_mlp_train_refresh: layer %d: w_ld %lld < its %d inputs", l,
+                  (long long)w_ld[l], mlp->sizes[l]);
+    }
+    return launch_mlp_train_refresh(ctx, mlp->layout, mlp->sizes.data(), W, w_ld, w16);
+}
+
+int dlrm_mlp_train_forward(dlrm_ctx* ctx, const dlrm_mlp_train* mlp, int batch, const void* x, int x_dtype,
+                           int64_t x_ld, const float* const* b, const void* w16, void* acts, void* out,
+                           int out_dtype, int64_t out_ld, int last_relu) {
+    if (!mlp_train_dtype(x_dtype) || !mlp_train_dtype(out_dtype))
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_mlp_train_forward: x_dtype=%d out_dtype=%d: fp32 and bf16 only",
+                        x_dtype, out_dtype);
+    CHECK_ARG(ctx && mlp, "dlrm_mlp_train_forward: null ctx/mlp");
+    const int n = mlp->layout.layers;
+    CHECK_ARG(batch >= 1 && batch <= mlp->layout.batch, "dlrm_mlp_train_forward: batch %d is not in 1 .. max_batch %d",
+              batch, mlp->layout.batch);
+    CHECK_ARG(x && b && w16 && acts && out, "dlrm_mlp_train_forward: null buffer");
+    for (int l = 0; l < n; ++l) CHECK_ARG(b[l], "dlrm_mlp_train_forward: layer %d has no bias", l);
+    CHECK_ARG(x_ld >= mlp->sizes[0] && out_ld >= mlp->sizes[n], "dlrm_mlp_train_forward: x_ld %lld / out_ld %lld too small",
+              (long long)x_ld, (long long)out_ld);
+    return launch_mlp_train_forward(ctx, mlp->layout, mlp->sizes.data(), batch, x, x_dtype, x_ld, b, w16, acts, out,
+                                    out_dtype, out_ld, last_relu != 0);
+}
+
+int dlrm_mlp_train_backward(dlrm_ctx* ctx, const dlrm_mlp_train* mlp, int batch, const void* dy, int dy_dtype,
+                            int64_t dy_ld, const void* out, int out_dtype, int64_t out_ld, const void* w16,
+                            const void* acts, void* grads, void* part, float* const* gW, const int64_t* gw_ld,
+                            float* const* gb, int write_last_gb, void* dx, int dx_dtype, int64_t dx_ld) {
+    if (!mlp_train_dtype(dy_dtype) || (out && !mlp_train_dtype(out_dtype)) || (dx && !mlp_train_dtype(dx_dtype)))
+        return ctx_fail(ctx, DLRM_E_UNSUPPORTED, "dlrm_mlp_train_backward: dy_dtype=%d out_dtype=%d dx_dtype=%d: fp32 and "
+                        "bf16 only", dy_dtype, out_dtype, dx_dtype);
+    CHECK_ARG(ctx && mlp, "dlrm_mlp_train_backward: null ctx/mlp");
+    const int n = mlp->layout.layers;
+    CHECK_ARG(batch >= 1 && batch <= mlp->layout.batch, "dlrm_mlp_train_backward: batch %d is not in 1 .. max_batch %d",
+              batch, mlp->layout.batch);
+    CHECK_ARG(dy && w16 && acts && grads && part && gW && gw_ld && gb, "dlrm_mlp_train_backward: null buffer");
+    for (int l = 0; l < n; ++l) {
+        CHECK_ARG(gW[l] && gb[l], "dlrm_mlp_train_backward: layer %d has no gW or no gb", l);
+        CHECK_ARG(gw_ld[l] >= mlp->sizes[l], "dlrm_mlp_train_backward: layer %d: gw_ld %lld < its %d inputs", l,
+                  (long long)gw_ld[l], mlp->sizes[l]);
+    }
+    CHECK_ARG(dy_ld >= mlp->sizes[n] && (!out || out_ld >= mlp->sizes[n]) && (!dx || dx_ld >= mlp->sizes[0]),
+              "dlrm_mlp_train_backward: a leading dimension is too small");
+    return launch_mlp_train_backward(ctx, mlp->layout, mlp->sizes.data(), batch, dy, dy_dtype, dy_ld, out, out_dtype,
+                                     out_ld, w16, acts, grads, part, gW, gw_ld, gb, write_last_gb != 0, dx, dx_dtype,
+                                     dx_ld);
 }
 
 int dlrm_interact_bwd(dlrm_ctx* ctx, int dtype, int d, int num_features, int batch, const void* dout, int64_t dout_ld,

@@ -63,6 +63,7 @@ class DenseMLP:
         self._ws = {}  # (layer, batch) -> dlrm_relu_bwd_bias scratch
         self._context = None
         self._bf16 = None  # the packed bf16 chain (bf16_chain)
+        self._train16 = None  # the bf16 training state (train_bf16)
 
     def flatten(self):
         """Re-homes every weight/bias AND its gradient as views of two flat fp32 buffers with the
@@ -125,6 +126,15 @@ class DenseMLP:
             from .mlp_bf16 import Bf16MLP
             self._bf16 = Bf16MLP(self)
         return self._bf16
+
+    def train_bf16(self, max_batch):
+        """The MLP's mixed-precision training state (`mlp_train_bf16.Bf16TrainMLP`): bf16 operands of these fp32
+        masters, forward / dgrad / wgrad on the bf16 MFMA kernels, gW and gb written here.  Built on first use (a
+        larger `max_batch` builds it anew); `.refresh()` it after the weights change."""
+        if self._train16 is None or self._train16.max_batch < max_batch:
+            from .mlp_train_bf16 import Bf16TrainMLP
+            self._train16 = Bf16TrainMLP(self, max_batch)
+        return self._train16
 
     def infer(self, x, *, logits=False, bf16=False, out_dtype=None):
         """`forward` without keeping anything: the activations of the last training forward (what its
@@ -222,7 +232,9 @@ class DLRMModel:
     (a device scalar, no host sync).  `forward(dense, sparse)` is the model call (probabilities).
     """
 
-    def __init__(self, bottom, tables, top, batch, lookups=1, *, lr=0.1, index_base=0, **hot_kw):
+    def __init__(self, bottom, tables, top, batch, lookups=1, *, lr=0.1, index_base=0, mlp=None, **hot_kw):
+        if mlp not in (None, "fp32", "bf16"):
+            raise ValueError(f'mlp is "fp32" or "bf16", not {mlp!r}')
         self.bottom, self.top = bottom, top
         ts = tables if isinstance(tables, EmbeddingTableSet) else EmbeddingTableSet(tables)
         self.hot = HotPath(ts, batch, lookups, lr=lr, index_base=index_base, **hot_kw)
@@ -243,6 +255,14 @@ class DLRMModel:
         self._q8 = None  # (the QuantizedTableSet last scored with, its Q8Inference)
         bottom.flatten()  # one Descent launch per MLP
         top.flatten()
+        # mlp="bf16": `step` trains both MLPs on the bf16 MFMA kernels; the buffers after the
+        # flatten, so that the kernels write the flat gradient's views
+        self._mlp16 = None
+        if mlp == "bf16":
+            self._mlp16 = (bottom.train_bf16(self.hot.B), top.train_bf16(self.hot.B))
+            self._x16 = torch.empty((self.hot.B, d), dtype=self.tdtype, device=ts.device)
+            self._z16 = torch.empty((self.hot.B, 1), dtype=torch.float32, device=ts.device)
+            self._dout16 = torch.empty((self.hot.B, width), dtype=self.tdtype, device=ts.device)
 
     @property
     def tables(self):
@@ -345,6 +365,8 @@ class DLRMModel:
         """train.jl:215-227 + custom_update! (train.jl:232-292)."""
         if not dense.is_cuda:
             raise ValueError("DLRMModel.step runs on the GPU (the hot path has no CPU fallback)")
+        if self._mlp16 is not None:
+            return self._step_bf16(dense, sparse, labels)
         x = self.bottom.forward(dense)
         out = self.hot.forward(x.to(self.tdtype), sparse)
         z = self.top.forward(out.float(), logits=True)  # [B][1]
@@ -354,6 +376,24 @@ class DLRMModel:
         self.bottom.backward(dx, need_dx=False)
         self.top.sgd_(self.lr)
         self.bottom.sgd_(self.lr)
+        return self.loss
+
+
+    def _step_bf16(self, dense, sparse, labels):
+        """`step` with both MLPs on the bf16 kernels: no conversion and no relu seam is launched; the chains read and
+        write the hot path's buffers in the tables' dtype."""
+        bot, top = self._mlp16
+        x = bot.forward(dense, out=self._x16)
+        out = self.hot.forward(x, sparse)
+        z = top.forward(out, out=self._z16)
+        self.head(z, labels)
+        dout = top.backward(self._dz, dx=self._dout16)
+        dx = self.hot.backward(sparse, dout)  # tables updated here
+        bot.backward(dx, need_dx=False)
+        self.top.sgd_(self.lr)
+        self.bottom.sgd_(self.lr)
+        top.refresh()
+        bot.refresh()
         return self.loss
 
 

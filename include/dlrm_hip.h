@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DLRM_HIP_ABI_VERSION 4
+#define DLRM_HIP_ABI_VERSION 5
 
 typedef enum {
     DLRM_OK = 0,
@@ -919,6 +919,62 @@ int dlrm_mlp_bf16_pack(dlrm_ctx* ctx, dlrm_mlp_bf16* mlp, const float* const* W,
                        const float* const* b);
 int dlrm_mlp_bf16_infer(dlrm_ctx* ctx, const dlrm_mlp_bf16* mlp, int batch, const void* x, int x_dtype,
                         int64_t x_ld, void* out, int out_dtype, int64_t out_ld, int last_relu);
+
+/* ---- bf16 MLP training: forward, dgrad and wgrad of a Dense chain on bf16 MFMA ------------
+ * Mixed precision: fp32 master weights W_l [N][K] and biases, bf16 operands, fp32 accumulation
+ * (v_mfma_f32_16x16x32_bf16).  Layer l (1-based) has K = sizes[l-1], N = sizes[l]; "level" i is the chain's
+ * tensor of width sizes[i] (level 0 the input).  Every product is a C[i][j] = sum_k A[i][k] B[j][k] over rows
+ * whose contraction index is contiguous, so every bf16 tensor is kept twice, [rows][ld] and transposed:
+ *   refresh:  W16_l = bf16(W_l) as [N][ld[l-1]] and W16T_l as [K][ld[l]] (ties to even, zero where padded), all
+ *             layers in one launch.
+ *   forward:  level 0 = bf16(x), as [batch][ld[0]] and [K0][ldt] (one launch); then per layer one launch:
+ *             z = a W16^T + b in fp32; hidden levels store bf16(relu(z)) as [batch][ld[l]] and [N][ldt]; the
+ *             last layer stores once, relu(z) (last_relu) or z, in out_dtype.
+ *   backward: g_n = bf16(dy), masked with (out > 0) when `out` is given (a relu-last chain), both forms, one
+ *             launch; then for l = n .. 1: wgrad gW_l = g_l^T a_{l-1} (fp32, contracted over the batch, with
+ *             gb_l = column sums of g_l from the same launch: a ones operand) and dgrad
+ *             g_{l-1} = bf16((g_l W16_l) * (a_{l-1} > 0)), both forms; for l = 1 there is no mask and the
+ *             result is dx in dx_dtype (dx NULL: skipped).  The batch of a wgrad is cut into slabs[l] slabs
+ *             of slab_rows[l] rows where the output has fewer than 256 tiles; the slab partials are summed
+ *             in slab order by one launch at the end (no floating-point atomics: the same bits every run).
+ *             write_last_gb = 0 leaves gb of the last layer alone (dlrm_bce_head wrote it).
+ * Padding: ld[i] = ceil64(sizes[i]); ldt = ceil64(batch); columns sizes[i] .. ld[i] of a row-major bf16
+ * buffer and columns batch .. ceil64(batch) of a transposed one are written as zero; rows >= batch are never
+ * stored.  The layout of a handle is that of its max_batch; a call with batch <= max_batch keeps it.
+ * plan:    pure host, no device call.  Fills the layout: offsets in BYTES into the four caller-owned buffers
+ *          (w16: w_off / wt_off; acts: a_off / at_off of levels 0 .. layers-1; grads: g_off / gt_off of
+ *          levels 1 .. layers at index level-1; part: p_off (gW slab partials [slabs][N][K] fp32) / pb_off
+ *          (gb partials [slabs][N])), their sizes, the tile {first-operand rows, second-operand rows, k} of
+ *          each role (0 forward, 1 dgrad, 2 wgrad) and each layer's grid per role.  DLRM_E_ARG for
+ *          layers <= 0, a width <= 0 or batch <= 0; DLRM_E_UNSUPPORTED for more than 8 layers or a width
+ *          above 8192.
+ * Memory is the caller's; refresh, forward and backward allocate nothing and do not synchronise
+ * (hipGraph-capturable).  Dtypes (x, out, dy, dx): DLRM_F32 or DLRM_BF16, anything else DLRM_E_UNSUPPORTED.
+ * W, w_ld, b, gW, gw_ld, gb: host arrays of `layers` entries. */
+typedef struct dlrm_mlp_train_layout {
+    int layers, batch, ldt;
+    int tile[3][3];
+    int ld[9];
+    int slabs[8], slab_rows[8];
+    int grid[8][3][3];
+    int64_t w_off[8], wt_off[8], w_bytes;
+    int64_t a_off[8], at_off[8], a_bytes;
+    int64_t g_off[8], gt_off[8], g_bytes;
+    int64_t p_off[8], pb_off[8], p_bytes;
+} dlrm_mlp_train_layout;
+typedef struct dlrm_mlp_train dlrm_mlp_train;
+int dlrm_mlp_train_plan(int layers, const int* sizes, int batch, dlrm_mlp_train_layout* out);
+int dlrm_mlp_train_create(dlrm_ctx* ctx, int layers, const int* sizes, int max_batch, dlrm_mlp_train** out);
+int dlrm_mlp_train_destroy(dlrm_mlp_train* mlp);
+int dlrm_mlp_train_refresh(dlrm_ctx* ctx, const dlrm_mlp_train* mlp, const float* const* W, const int64_t* w_ld,
+                           void* w16);
+int dlrm_mlp_train_forward(dlrm_ctx* ctx, const dlrm_mlp_train* mlp, int batch, const void* x, int x_dtype,
+                           int64_t x_ld, const float* const* b, const void* w16, void* acts, void* out,
+                           int out_dtype, int64_t out_ld, int last_relu);
+int dlrm_mlp_train_backward(dlrm_ctx* ctx, const dlrm_mlp_train* mlp, int batch, const void* dy, int dy_dtype,
+                            int64_t dy_ld, const void* out, int out_dtype, int64_t out_ld, const void* w16,
+                            const void* acts, void* grads, void* part, float* const* gW, const int64_t* gw_ld,
+                            float* const* gb, int write_last_gb, void* dx, int dx_dtype, int64_t dx_ld);
 
 #ifdef __cplusplus
 }
