@@ -16,7 +16,8 @@ from .evaluate import Evaluator, eval_reference
 from .hotpath import HotPath
 from .mlp_bf16 import Bf16MLP, mlp_bf16_plan, mlp_bf16_reference
 from .mlp_train_bf16 import Bf16TrainMLP, mlp_train_bf16_reference, mlp_train_plan
-from .quant import Q8Inference, QuantizedTableSet, dequantize_rows, quantize_rows
+from .quant import (Q4Inference, Q8Inference, Quantized4TableSet, QuantizedTableSet, dequantize_rows, dequantize_rows4,
+                    pack_rows4, q4_bound, quantize_rows, quantize_rows4, unpack_rows4)
 from .lazy import DeferredUpdate, HipTables, LazyGrad, LazyLookup
 from .interact import (POST_INTERACTION_PAD_TO_MUL, DotInteraction, cdiv, dot_back, dot_interaction, fast_vcat,
                        interaction_sizes, rrule, rrule_dot_interaction, rrule_self_batched_mul, rrule_triangular_slice,
@@ -38,6 +39,7 @@ __all__ = [
     "LazyGrad", "DeferredUpdate", "ADAGrad", "RowwiseADAGrad", "SplitDescent", "split_f32", "merge_split",
     "StochasticDescent", "sr_round", "sr_bits", "philox4x32_10", "Evaluator", "eval_reference",
     "QuantizedTableSet", "Q8Inference", "quantize_rows", "dequantize_rows",
+    "Quantized4TableSet", "Q4Inference", "quantize_rows4", "dequantize_rows4", "pack_rows4", "unpack_rows4", "q4_bound",
     "Bf16MLP", "mlp_bf16_plan", "mlp_bf16_reference",
     "Bf16TrainMLP", "mlp_train_bf16_reference", "mlp_train_plan",
 ]

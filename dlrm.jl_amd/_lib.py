@@ -83,6 +83,14 @@ SIGNATURES = {
     "dlrm_q8_maplookup": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64]),
     "dlrm_q8_lookup_interact_fwd": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64,
                                             _i32]),
+    "dlrm_q4_row_bytes": (_i32, [_i32]),
+    "dlrm_q4_tables_create": (_i32, [_vp, _i32, _i32, _pp, _pi64, _pp]),
+    "dlrm_q4_tables_destroy": (_i32, [_vp]),
+    "dlrm_q4_quantize": (_i32, [_vp, _vp, _vp]),
+    "dlrm_q4_dequantize": (_i32, [_vp, _vp, _vp]),
+    "dlrm_q4_maplookup": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64]),
+    "dlrm_q4_lookup_interact_fwd": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64,
+                                            _i32]),
     "dlrm_mlp_bf16_plan": (_i32, [_i32, _pi32, _i32, _i32, _i32, _pi32, _pi32, _pi64, _pi64, _pi32, _pi32]),
     "dlrm_mlp_bf16_create": (_i32, [_vp, _i32, _pi32, _pp]),
     "dlrm_mlp_bf16_destroy": (_i32, [_vp]),

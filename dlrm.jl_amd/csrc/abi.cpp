@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "apply.hpp"
 #include "q8.hpp"
+#include "q4.hpp"
 #include "mlp_bf16.hpp"
 #include "mlp_train.hpp"
 
@@ -60,6 +61,15 @@ struct dlrm_q8_tables {
     std::vector<Q8Desc> h_desc;
     int64_t rows = 0;  // of every table
     int q_align = 16;  // the largest power of two <= 16 that divides every q pointer (q8_plan.hpp)
+};
+
+// int4 row-quantized tables: the caller's row arrays ({scale, bias} and codes in one row)
+struct dlrm_q4_tables {
+    dlrm_ctx* ctx = nullptr;
+    int T = 0, D = 0;
+    Q4Desc* d_desc = nullptr;
+    std::vector<Q4Desc> h_desc;
+    int64_t rows = 0;  // of every table
 };
 
 // A Dense chain for the fused bf16 inference: the widths and the packed weights and biases (mlp_plan.hpp), owned
@@ -841,6 +851,121 @@ int dlrm_q8_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const v
     CHECK_ARG(batch == 0 || (x && out), "dlrm_q8_lookup_interact_fwd: null buffer");
     return launch_q8_lookup_interact_fwd(ctx, q8->h_desc.data(), q8->q_align, q8->T, d, indices, itype, table_stride,
                                          index_base, batch, lookups, dtype, x, x_ld, out, out_ld, padding);
+}
+
+// ------------------------------------------------------------- int4 row-quantized tables
+int dlrm_q4_row_bytes(int dim) {
+    if (dim <= 0 || dim > (1 << 30)) return DLRM_E_ARG;
+    return (int)q4_row_bytes(dim);
+}
+
+int dlrm_q4_tables_create(dlrm_ctx* ctx, int num_tables, int dim, uint8_t* const* rows, const int64_t* nrows,
+                          dlrm_q4_tables** out) {
+    CHECK_ARG(ctx && out, "dlrm_q4_tables_create: null argument");
+    *out = nullptr;
+    CHECK_ARG(num_tables >= 0 && dim > 0 && dim <= (1 << 30), "dlrm_q4_tables_create: num_tables=%d dim=%d", num_tables,
+              dim);
+    CHECK_ARG(num_tables == 0 || (rows && nrows), "dlrm_q4_tables_create: null rows/nrows");
+    for (int t = 0; t < num_tables; ++t) {
+        CHECK_ARG(nrows[t] >= 0 && nrows[t] < 0xFFFFFFFFll && (nrows[t] == 0 || rows[t]),
+                  "dlrm_q4_tables_create: table %d has nrows=%lld", t, (long long)nrows[t]);
+        CHECK_ARG((uintptr_t)rows[t] % 8 == 0, "dlrm_q4_tables_create: rows[%d] is not 8-B aligned", t);
+    }
+    dlrm_q4_tables* qt = new (std::nothrow) dlrm_q4_tables();
+    if (!qt) return DLRM_E_NOMEM;
+    qt->ctx = ctx;
+    qt->T = num_tables;
+    qt->D = dim;
+    qt->h_desc.resize(num_tables);
+    for (int t = 0; t < num_tables; ++t) {
+        qt->h_desc[t] = Q4Desc{rows[t], nrows[t], qt->rows, 0};
+        qt->rows += nrows[t];
+    }
+    int rc = hip_set(ctx);
+    if (rc == DLRM_OK && num_tables > 0) {
+        rc = ctx_hip(ctx, hipMalloc((void**)&qt->d_desc, sizeof(Q4Desc) * num_tables), "hipMalloc(q4 tables)");
+        if (rc == DLRM_OK)
+            rc = ctx_hip(ctx, hipMemcpy(qt->d_desc, qt->h_desc.data(), sizeof(Q4Desc) * num_tables, hipMemcpyHostToDevice),
+                         "hipMemcpy(q4 tables)");
+    }
+    if (rc != DLRM_OK) {
+        if (qt->d_desc) (void)hipFree(qt->d_desc);
+        delete qt;
+        return rc;
+    }
+    *out = qt;
+    return DLRM_OK;
+}
+
+int dlrm_q4_tables_destroy(dlrm_q4_tables* q4) {
+    if (!q4) return DLRM_OK;
+    if (q4->d_desc) (void)hipFree(q4->d_desc);
+    delete q4;
+    return DLRM_OK;
+}
+
+// the two sets describe the same rows
+static int check_q4_pair(dlrm_ctx* ctx, const dlrm_tables* tb, const dlrm_q4_tables* q4, const char* fn) {
+    CHECK_ARG(tb->T == q4->T && tb->D == q4->D, "%s: %d tables of dim %d against %d quantized tables of dim %d", fn, tb->T,
+              tb->D, q4->T, q4->D);
+    for (int t = 0; t < tb->T; ++t)
+        CHECK_ARG(tb->h_desc[t].nrows == q4->h_desc[t].nrows, "%s: table %d has %lld rows against %lld quantized rows", fn,
+                  t, (long long)tb->h_desc[t].nrows, (long long)q4->h_desc[t].nrows);
+    return DLRM_OK;
+}
+
+int dlrm_q4_quantize(dlrm_ctx* ctx, const dlrm_tables* src, dlrm_q4_tables* dst) {
+    CHECK_ARG(ctx && src && dst, "dlrm_q4_quantize: null ctx/tables");
+    const int rc = check_q4_pair(ctx, src, dst, "dlrm_q4_quantize");
+    if (rc) return rc;
+    return launch_q4_quantize(ctx, src->d_desc, src->dtype, src->aligned16, dst->d_desc, dst->T, dst->D, dst->rows);
+}
+
+int dlrm_q4_dequantize(dlrm_ctx* ctx, const dlrm_q4_tables* src, dlrm_tables* dst) {
+    CHECK_ARG(ctx && src && dst, "dlrm_q4_dequantize: null ctx/tables");
+    const int rc = check_q4_pair(ctx, dst, src, "dlrm_q4_dequantize");
+    if (rc) return rc;
+    return launch_q4_dequantize(ctx, src->d_desc, dst->d_desc, dst->dtype, dst->aligned16, src->T, src->D, src->rows);
+}
+
+static int check_q4_indices(dlrm_ctx* ctx, const dlrm_q4_tables* q4, const void* indices, int itype, int64_t tstride,
+                            int batch, int lookups, int dtype) {
+    CHECK_ARG(dtype == DLRM_F32 || dtype == DLRM_BF16, "unknown dtype %d", dtype);
+    CHECK_ARG(itype == DLRM_I32 || itype == DLRM_I64, "unknown index type %d", itype);
+    CHECK_ARG(batch >= 0 && lookups >= 1, "batch=%d lookups=%d", batch, lookups);
+    CHECK_ARG((int64_t)batch * lookups < (1ll << 31), "batch*lookups exceeds 2^31");
+    CHECK_ARG(batch == 0 || q4->T == 0 || indices, "null indices");
+    CHECK_ARG(q4->T <= 1 || tstride >= (int64_t)batch * lookups, "table_stride %lld < batch*lookups %lld",
+              (long long)tstride, (long long)batch * lookups);
+    return DLRM_OK;
+}
+
+int dlrm_q4_maplookup(dlrm_ctx* ctx, const dlrm_q4_tables* q4, const void* indices, int itype, int64_t table_stride,
+                      int index_base, int batch, int lookups, int dtype, void* out, int64_t out_ld, int64_t out_offset) {
+    CHECK_ARG(ctx && q4, "dlrm_q4_maplookup: null ctx/tables");
+    const int rc = check_q4_indices(ctx, q4, indices, itype, table_stride, batch, lookups, dtype);
+    if (rc) return rc;
+    CHECK_ARG(batch == 0 || q4->T == 0 || out, "dlrm_q4_maplookup: null out");
+    CHECK_ARG(out_offset >= 0 && out_ld >= out_offset + (int64_t)q4->T * q4->D,
+              "dlrm_q4_maplookup: out_ld %lld < out_offset %lld + T*D %lld", (long long)out_ld, (long long)out_offset,
+              (long long)q4->T * q4->D);
+    return launch_q4_maplookup(ctx, q4->d_desc, q4->T, q4->D, indices, itype, table_stride, index_base, batch, lookups,
+                               dtype, out, out_ld, out_offset);
+}
+
+int dlrm_q4_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_q4_tables* q4, const void* indices, int itype,
+                                int64_t table_stride, int index_base, int batch, int lookups, int dtype, const void* x,
+                                int64_t x_ld, void* out, int64_t out_ld, int padding) {
+    CHECK_ARG(ctx && q4, "dlrm_q4_lookup_interact_fwd: null ctx/tables");
+    const int rc = check_q4_indices(ctx, q4, indices, itype, table_stride, batch, lookups, dtype);
+    if (rc) return rc;
+    const int d = q4->D, F = q4->T + 1;
+    const int64_t P = (int64_t)F * (F - 1) / 2;
+    CHECK_ARG(padding >= 0 && x_ld >= d && out_ld >= d + P + padding,
+              "dlrm_q4_lookup_interact_fwd: leading dimensions too small");
+    CHECK_ARG(batch == 0 || (x && out), "dlrm_q4_lookup_interact_fwd: null buffer");
+    return launch_q4_lookup_interact_fwd(ctx, q4->h_desc.data(), q4->T, d, indices, itype, table_stride, index_base,
+                                         batch, lookups, dtype, x, x_ld, out, out_ld, padding);
 }
 
 // ------------------------------------------------------------- fused bf16 MLP inference

@@ -253,6 +253,7 @@ class DLRMModel:
         self._dz = self._head_prob = None
         self._pad_to = hot_kw.get("pad_to", 1)
         self._q8 = None  # (the QuantizedTableSet last scored with, its Q8Inference)
+        self._q4 = None  # (the Quantized4TableSet last scored with, its Q4Inference)
         bottom.flatten()  # one Descent launch per MLP
         top.flatten()
         # mlp="bf16": `step` trains both MLPs on the bf16 MFMA kernels; the buffers after the
@@ -274,12 +275,15 @@ class DLRMModel:
         self.prob = self.top.forward(out.float()).reshape(-1)
         return self.prob
 
-    def quantize(self):
+    def quantize(self, bits=8):
         """The model's tables as int8 rows with a per-row scale and bias (`QuantizedTableSet.from_tables`): what
         `predict(..., q8=)` and `test(..., q8=)` score.  The tables are quantized as the lookup reads them (for
-        `SplitDescent` the bf16 high halves of the merged values)."""
-        from .quant import QuantizedTableSet
-        return QuantizedTableSet.from_tables(self.tables)
+        `SplitDescent` the bf16 high halves of the merged values).  bits=4: 4-bit rows with the scale and bias in
+        the row (`Quantized4TableSet.from_tables`), for `predict(..., q4=)` and `test(..., q4=)`."""
+        from .quant import Quantized4TableSet, QuantizedTableSet
+        if bits not in (8, 4):
+            raise ValueError(f"quantize: bits is 8 or 4, not {bits!r}")
+        return (QuantizedTableSet if bits == 8 else Quantized4TableSet).from_tables(self.tables)
 
     def _q8_engine(self, q8):
         from .quant import Q8Inference
@@ -290,12 +294,21 @@ class DLRMModel:
                                         index_base=self.hot.index_base, pad_to=self._pad_to))
         return self._q8[1]
 
+    def _q4_engine(self, q4):
+        from .quant import Q4Inference
+        if self._q4 is None or self._q4[0] is not q4:
+            if len(q4) != len(self.tables) or q4.D != self.tables.D:
+                raise ValueError("q4 does not match the model's tables (count, feature size)")
+            self._q4 = (q4, Q4Inference(q4, self.hot.B, self.hot.L, d=self.hot.d, dtype=self.tdtype,
+                                        index_base=self.hot.index_base, pad_to=self._pad_to))
+        return self._q4[1]
+
     def repack(self):
         """Packs both MLPs' current weights for `predict(..., mlp="bf16")` (two launches): after training steps."""
         self.bottom.bf16_chain().repack()
         self.top.bf16_chain().repack()
 
-    def predict(self, dense, sparse, q8=None, mlp=None):
+    def predict(self, dense, sparse, q8=None, mlp=None, q4=None):
         """The model call for evaluation: the logits [B][1] of a batch (the sigmoid is `Evaluator.add`'s, with
         dlrm_bce_head's expression).  Bottom MLP, `HotPath.infer`, top MLP: nothing a training step keeps is
         touched -- no indexer, no saved activation, no optimizer state -- so it can run between two steps.
@@ -303,36 +316,46 @@ class DLRMModel:
         `Q8Inference.infer` over it.
         mlp="bf16": each MLP is one fused bf16 launch (`DenseMLP.infer(bf16=True)`) on the weights as last packed
         (`repack()`): the bottom chain writes x in the tables' dtype, the top chain reads the hot path's output in
-        that dtype and writes the fp32 logits, so no conversion is launched.  Composes with q8."""
+        that dtype and writes the fp32 logits, so no conversion is launched.  Composes with q8.
+        q4: a `Quantized4TableSet` (`quantize(bits=4)`), scored by `Q4Inference.infer`; as q8, and not with it."""
         if mlp not in (None, "fp32", "bf16"):
             raise ValueError(f'mlp is "fp32" or "bf16", not {mlp!r}')
+        if q8 is not None and q4 is not None:
+            raise ValueError("predict: q8 or q4, not both")
         if not isinstance(sparse, PackedIndices):
             sparse = PackedIndices(sparse, device=self.tables.device)
         if mlp == "bf16":
             x = self.bottom.infer(dense, bf16=True, out_dtype=self.tdtype)
-            out = self.hot.infer(x, sparse) if q8 is None else self._q8_engine(q8).infer(x, sparse)
+            if q4 is not None:
+                out = self._q4_engine(q4).infer(x, sparse)
+            else:
+                out = self.hot.infer(x, sparse) if q8 is None else self._q8_engine(q8).infer(x, sparse)
             return self.top.infer(out, logits=True, bf16=True)
         x = self.bottom.infer(dense)
-        if q8 is None:
+        if q4 is not None:
+            out = self._q4_engine(q4).infer(x.to(self.tdtype), sparse)
+        elif q8 is None:
             out = self.hot.infer(x.to(self.tdtype), sparse)
         else:
             out = self._q8_engine(q8).infer(x.to(self.tdtype), sparse)
         return self.top.infer(out.float(), logits=True)
 
-    def test(self, data, record=None, evaluator=None, probs=None, q8=None, mlp=None):
+    def test(self, data, record=None, evaluator=None, probs=None, q8=None, mlp=None, q4=None):
         """The reference's `test(model, data; record, strategy)` (src/train/utils.jl:31-46): for every
         (labels, dense, sparse) of `data` (a `DACLoader`, or any iterable of such batches of the model's batch
         size), `predict` and one `Evaluator.add`; one synchronisation, at the end.  Appends the accuracy
         (correct / total) to `record` and returns `Evaluator.result()`: dict(total, correct, accuracy, logloss,
         auc, positives, negatives).  evaluator: an `Evaluator` to use (reset first; its state holds this pass
         afterwards); probs: a list that receives every batch's probabilities (a device tensor each); q8: score
-        the quantized tables (`predict`'s q8); mlp: `predict`'s mlp ("bf16": the MLPs are packed once, here)."""
+        the quantized tables (`predict`'s q8; q4: its q4, not both); mlp: `predict`'s mlp ("bf16": the MLPs are packed once, here)."""
+        if q8 is not None and q4 is not None:
+            raise ValueError("test: q8 or q4, not both")
         dev = self.tables.device
         ev = Evaluator(dev) if evaluator is None else evaluator.reset()
         if mlp == "bf16":
             self.repack()
         for labels, dense, sparse in data:
-            z = self.predict(dense, sparse, q8=q8, mlp=mlp)
+            z = self.predict(dense, sparse, q8=q8, mlp=mlp, q4=q4)
             check_labels(labels, z)
             p = None
             if probs is not None:

@@ -1398,6 +1398,92 @@ function infer(dot::HipDotInteraction, x::DeviceMatrix{T}, q8::HipQ8Tables{D}, s
 end
 
 #####
+##### int4 row-quantized tables with in-row scale and bias (inference and evaluation; include/dlrm_hip.h)
+#####
+
+"""
+    HipQ4Tables(tables::AbstractVector{<:HipEmbedding})
+
+The tables as 4-bit rows: one array `r[t]` (`S × N` of `UInt8`, `S = 8 + 8 cld(D, 16)`) per table, a row being
+`{scale, bias}` and then two codes per byte, allocated here and filled by one `dlrm_q4_quantize` launch.
+`v = (q * scale) + bias` in two fp32 roundings with `scale = range / 15`.
+"""
+mutable struct HipQ4Tables{D}
+    ctx::Context
+    r::Vector{DeviceMatrix{UInt8}}
+    ptr::Ptr{Cvoid}
+end
+function HipQ4Tables(tables::AbstractVector{<:HipEmbedding{Static{D},T}}) where {D,T}
+    ctx = first(tables).data.ctx
+    poll_bounds!(tables)
+    flush!(tables)
+    S = Int(ccall((:dlrm_q4_row_bytes, libdlrm), Cint, (Cint,), D))
+    r = [DeviceMatrix{UInt8}(ctx, S, size(t, 2)) for t in tables]
+    rp = [m.ptr for m in r]
+    rows = Int64[size(t, 2) for t in tables]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ctx, ccall((:dlrm_q4_tables_create, libdlrm), Cint,
+                     (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ref{Ptr{Cvoid}}),
+                     ctx.ptr, length(tables), D, rp, rows, out))
+    q4 = HipQ4Tables{D}(ctx, r, out[])
+    finalizer(x -> ccall((:dlrm_q4_tables_destroy, libdlrm), Cint, (Ptr{Cvoid},), x.ptr), q4)
+    check(ctx, ccall((:dlrm_q4_quantize, libdlrm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     ctx.ptr, tableset(tables), q4.ptr))
+    return q4
+end
+Base.length(q4::HipQ4Tables) = length(q4.r)
+nbytes(q4::HipQ4Tables) = sum(prod(size(m)) for m in q4.r)
+
+function dequantize!(tables::AbstractVector{<:HipEmbedding{Static{D}}}, q4::HipQ4Tables{D}) where {D}
+    flush!(tables)
+    check(q4.ctx, ccall((:dlrm_q4_dequantize, libdlrm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                        q4.ctx.ptr, q4.ptr, tableset(tables)))
+    return tables
+end
+
+function _maplookup(q4::HipQ4Tables{D}, sparse, P::Integer, ::Type{T} = Float32) where {D,T}
+    ctx = q4.ctx
+    idx = sparse isa PackedIndices ? sparse : pack(ctx, sparse)
+    ys = DeviceMatrix{T}(ctx, P + D * length(q4), idx.batch)
+    check(ctx, ccall((:dlrm_q4_maplookup, libdlrm), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Int64, Int64),
+                     ctx.ptr, q4.ptr, idx.data.ptr, DLRM_I32, idx.batch * idx.lookups, 1,
+                     idx.batch, idx.lookups, dtype_code(T), ys.ptr, size(ys, 1), P))
+    return ys, idx
+end
+EmbeddingTables.maplookup(s::PreallocationStrategy, q4::HipQ4Tables, sparse) =
+    first(_maplookup(q4, sparse, prealloc_rows(s)))
+
+"""
+    infer(dot::HipDotInteraction, x::DeviceMatrix, q4::HipQ4Tables, sparse)
+
+The inference forward on 4-bit rows: one launch (`dlrm_q4_lookup_interact_fwd`) where the fused kernel exists,
+else the gather and `dlrm_interact_fwd`, with the same bits.
+"""
+function infer(dot::HipDotInteraction, x::DeviceMatrix{T}, q4::HipQ4Tables{D}, sparse) where {D,T}
+    ctx = q4.ctx
+    idx = sparse isa PackedIndices ? sparse : pack(ctx, sparse)
+    d, B = size(x)
+    F = length(q4) + 1
+    width, padding = interaction_sizes(d, F, dot.pad_to)
+    out = DeviceMatrix{T}(ctx, width, B)
+    rc = ccall((:dlrm_q4_lookup_interact_fwd, libdlrm), Cint,
+               (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Int64,
+                Ptr{Cvoid}, Int64, Cint),
+               ctx.ptr, q4.ptr, idx.data.ptr, DLRM_I32, idx.batch * idx.lookups, 1, B, idx.lookups,
+               dtype_code(T), x.ptr, d, out.ptr, width, padding)
+    if rc == Cint(-4)  # DLRM_E_UNSUPPORTED: no fused kernel for this shape
+        ys, _ = _maplookup(q4, idx, d, T)
+        check(ctx, ccall((:dlrm_interact_fwd, libdlrm), Cint,
+                         (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cint),
+                         ctx.ptr, dtype_code(T), d, F, B, x.ptr, d, ys.ptr, size(ys, 1), out.ptr, width, padding))
+    else
+        check(ctx, rc)
+    end
+    return out
+end
+
+#####
 ##### fused bf16 MLP inference: a Dense chain in one launch (include/dlrm_hip.h)
 #####
 

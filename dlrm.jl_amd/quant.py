@@ -8,6 +8,11 @@ add); they play the role `sr_round` and `eval_reference` play for their features
 
 `QuantizedTableSet` owns the arrays and the library handle, `Q8Inference` is `HotPath.infer` over them, and
 `DLRMModel.quantize()` / `predict(..., q8=)` / `test(..., q8=)` score a trained model on its quantized tables.
+
+The 4-bit format ("q4") is the same arithmetic with 15 levels and one array per table: a row
+is `{scale, bias}` followed by two codes per byte, `8 + 8 * ceil(D / 16)` bytes.  `quantize_rows4` /
+`dequantize_rows4` / `pack_rows4` / `unpack_rows4` restate it, `Quantized4TableSet` and `Q4Inference` are the 8-bit
+classes' counterparts, reached by `DLRMModel.quantize(bits=4)` and `predict(..., q4=)` / `test(..., q4=)`.
 """
 import ctypes
 
@@ -75,6 +80,67 @@ def q8_bound(w, scale):
     w = _as_f32_rows(w).astype(np.float64)
     m = np.maximum(np.abs(w.min(axis=1)), np.abs(w.max(axis=1)))
     return (0.5 + 2.0 ** -10) * np.asarray(scale, dtype=np.float64) + 2.0 ** -22 * m
+
+
+# ---- the 4-bit format
+def row_bytes4(D):
+    """Bytes of a 4-bit row of D codes: the header and whole 8-byte pieces of 16 codes (dlrm_q4_row_bytes)."""
+    return 8 + 8 * ((int(D) + 15) // 16)
+
+
+def quantize_rows4(w):
+    """`quantize_rows` with 15 levels: (q [N][D] uint8 in 0 .. 15, scale [N], bias [N]); scale = range / 15,
+    inv = 15 / range (0 for a constant row), q = min(15, max(0, rint((w - lo) * inv))), bias = lo."""
+    w = _as_f32_rows(w)
+    lo = w.min(axis=1)
+    hi = w.max(axis=1)
+    with np.errstate(all="ignore"):
+        rng = (hi - lo).astype(_F)
+        scale = (rng / _F(15.0)).astype(_F)
+        inv = np.where(rng > 0, _F(15.0) / np.where(rng > 0, rng, _F(1.0)), _F(0.0)).astype(_F)
+        t = ((w - lo[:, None]).astype(_F) * inv[:, None]).astype(_F)
+        q = np.minimum(_F(15.0), np.maximum(_F(0.0), np.rint(t))).astype(np.uint8)
+    return q, scale, lo.astype(_F)
+
+
+def dequantize_rows4(q, scale, bias, dtype=np.float32):
+    """`dequantize_rows` of codes 0 .. 15: v = (q * scale) + bias in two float32 roundings, bf16 rounded once."""
+    if np.asarray(q).size and int(np.asarray(q).max()) > 15:
+        raise ValueError("4-bit codes are 0 .. 15")
+    return dequantize_rows(q, scale, bias, dtype)
+
+
+def pack_rows4(q, scale, bias):
+    """Codes [N][D] with scale and bias -> the [N][S] uint8 byte image of a table, S = row_bytes4(D): float32 scale
+    and bias in native order, then code c in byte 8 + c // 2 (low nibble for even c); pads are zero."""
+    q = np.asarray(q)
+    if q.dtype != np.uint8 or q.ndim != 2:
+        raise TypeError("codes are [N][D] uint8")
+    N, D = q.shape
+    img = np.zeros((N, row_bytes4(D)), dtype=np.uint8)
+    img[:, 0:4] = np.ascontiguousarray(scale, dtype=_F).reshape(N, 1).view(np.uint8)
+    img[:, 4:8] = np.ascontiguousarray(bias, dtype=_F).reshape(N, 1).view(np.uint8)
+    img[:, 8:8 + (D + 1) // 2] |= q[:, 0::2] & 15
+    img[:, 8:8 + D // 2] |= (q[:, 1::2] & 15) << 4
+    return img
+
+
+def unpack_rows4(img, D):
+    """The [N][S] byte image of a table of D codes per row -> (q [N][D] uint8, scale [N], bias [N])."""
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8 or img.ndim != 2 or img.shape[1] != row_bytes4(D):
+        raise TypeError(f"a table of {D} codes per row is [N][{row_bytes4(D)}] uint8")
+    N = img.shape[0]
+    q = np.empty((N, D), dtype=np.uint8)
+    q[:, 0::2] = img[:, 8:8 + (D + 1) // 2] & 15
+    q[:, 1::2] = img[:, 8:8 + D // 2] >> 4
+    return q, img[:, 0:4].copy().view(_F).reshape(N), img[:, 4:8].copy().view(_F).reshape(N)
+
+
+def q4_bound(w, scale):
+    """`q8_bound` with the 4-bit scale: (0.5 + 2^-10) * scale + 2^-22 * max(|lo|, |hi|).  The slack term was
+    derived for values of (w - lo) * inv up to 255 and is only looser at 15."""
+    return q8_bound(w, scale)
 
 
 class QuantizedTableSet:
@@ -165,18 +231,21 @@ class Q8Inference:
     dlrm_q8_maplookup + dlrm_interact_fwd through a `ys` allocated on its first call (allocate before a graph
     capture by one eager call), with the same bits.  `route` says which ran last: "fused" or "two-launch"."""
 
+    _set_type = QuantizedTableSet  # (Q4Inference: the 4-bit set and its two entry points)
+    _fwd, _gather = "dlrm_q8_lookup_interact_fwd", "dlrm_q8_maplookup"
+
     def __init__(self, q8, batch, lookups=1, *, d=None, dtype=None, index_base=0, pad_to=1):
         import torch
         from .interact import interaction_sizes
         from .runtime import dtype_code
-        if not isinstance(q8, QuantizedTableSet):
-            raise TypeError("Q8Inference: q8 is a QuantizedTableSet")
+        if not isinstance(q8, self._set_type):
+            raise TypeError(f"{type(self).__name__}: the tables are a {self._set_type.__name__}")
         self.q8 = q8
         self.B, self.L = int(batch), int(lookups)
         self.T, self.D = len(q8), q8.D
         self.d = self.D if d is None else int(d)
         if self.d != self.D:
-            raise ValueError(f"Q8Inference: the dense vector length {self.d} must equal the feature size {self.D}")
+            raise ValueError(f"{type(self).__name__}: the dense vector length {self.d} must equal the feature size {self.D}")
         self.F = self.T + 1
         self.dtype = torch.float32 if dtype is None else dtype
         self.dcode = dtype_code(self.dtype)
@@ -195,9 +264,9 @@ class Q8Inference:
         """The raw fused call's status: _lib.OK (launched) or _lib.E_UNSUPPORTED (nothing launched)."""
         from .runtime import ptr
         out = self.out if out is None else out
-        rc = self.lib.dlrm_q8_lookup_interact_fwd(self.ctx.bind(), self.q8.handle, ptr(idx.data), idx.itype, idx.stride,
-                                                  self.index_base, self.B, self.L, self.dcode, ptr(x), x.stride(0),
-                                                  ptr(out), out.stride(0), self.padding)
+        rc = getattr(self.lib, self._fwd)(self.ctx.bind(), self.q8.handle, ptr(idx.data), idx.itype, idx.stride,
+                                          self.index_base, self.B, self.L, self.dcode, ptr(x), x.stride(0), ptr(out),
+                                          out.stride(0), self.padding)
         if rc != _lib.E_UNSUPPORTED:
             self._check(rc)
         return rc
@@ -210,8 +279,9 @@ class Q8Inference:
         if self.ys is None:
             self.ys = torch.empty((self.B, self.F * self.D), dtype=self.dtype, device=self.q8.device)
         h, ys = self.ctx.bind(), self.ys
-        self._check(self.lib.dlrm_q8_maplookup(h, self.q8.handle, ptr(idx.data), idx.itype, idx.stride, self.index_base,
-                                               self.B, self.L, self.dcode, ptr(ys), ys.stride(0), self.d))
+        self._check(getattr(self.lib, self._gather)(h, self.q8.handle, ptr(idx.data), idx.itype, idx.stride,
+                                                    self.index_base, self.B, self.L, self.dcode, ptr(ys), ys.stride(0),
+                                                    self.d))
         self._check(self.lib.dlrm_interact_fwd(h, self.dcode, self.d, self.F, self.B, ptr(x), x.stride(0), ptr(ys),
                                                ys.stride(0), ptr(out), out.stride(0), self.padding))
         self.route = "two-launch"
@@ -227,3 +297,88 @@ class Q8Inference:
 
     def check_bounds(self):
         self.ctx.check_bounds()
+
+
+class Quantized4TableSet:
+    """T 4-bit tables of one feature size registered with the library (one dlrm_q4_tables): `rows[t]` a
+    [N_t][S] uint8 device tensor, S = row_bytes4(D), 8-B aligned ({scale, bias}, then the codes, per row)."""
+
+    def __init__(self, rows, dim):
+        import torch
+        from .runtime import context
+        rows = list(rows)
+        if not rows:
+            raise ValueError("Quantized4TableSet needs at least one table")
+        self.D, dev = int(dim), rows[0].device
+        S = row_bytes4(self.D)
+        for r in rows:
+            if r.dtype != torch.uint8 or r.dim() != 2 or r.shape[1] != S or not r.is_contiguous():
+                raise ValueError(f"4-bit tables of {self.D} codes per row are contiguous [N][{S}] uint8 tensors")
+            if not r.is_cuda or r.device != dev:
+                raise ValueError("quantized tables live on one GPU")
+        self.rows, self.S, self.device = rows, S, dev
+        self.ctx = context(dev)
+        T = len(rows)
+        rp = (ctypes.c_void_p * T)(*[r.data_ptr() for r in rows])
+        nrows = (ctypes.c_int64 * T)(*[r.shape[0] for r in rows])
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx.lib.dlrm_q4_tables_create(self.ctx.bind(), T, self.D, rp, nrows, ctypes.byref(h)))
+        self.handle = h
+
+    @classmethod
+    def from_arrays(cls, rows, dim):
+        """Wraps given device tensors ([N_t][row_bytes4(dim)] uint8, 8-B aligned)."""
+        return cls(rows, dim)
+
+    @classmethod
+    def from_tables(cls, ts):
+        """Allocates the row arrays of `ts` (an EmbeddingTableSet, fp32 or bf16) and quantizes it
+        (dlrm_q4_quantize: one launch over every table)."""
+        import torch
+        from .embedding import as_table_set
+        ts = as_table_set(ts)
+        rows = [torch.empty((len(t), row_bytes4(ts.D)), dtype=torch.uint8, device=ts.device) for t in ts]
+        return cls(rows, ts.D).quantize_from(ts)
+
+    def quantize_from(self, ts):
+        """Quantizes `ts` (same table count, feature size and row counts) into this set's arrays."""
+        self.ctx.check(self.ctx.lib.dlrm_q4_quantize(self.ctx.bind(), ts.handle, self.handle))
+        return self
+
+    def dequantize(self, dtype=None):
+        """An EmbeddingTableSet of v (float32, the default) or bf16(v) (dlrm_q4_dequantize)."""
+        import torch
+        from .embedding import EmbeddingTableSet
+        dtype = torch.float32 if dtype is None else dtype
+        ts = EmbeddingTableSet([torch.empty((r.shape[0], self.D), dtype=dtype, device=self.device) for r in self.rows])
+        self.ctx.check(self.ctx.lib.dlrm_q4_dequantize(self.ctx.bind(), self.handle, ts.handle))
+        return ts
+
+    def __len__(self):
+        return len(self.rows)
+
+    @property
+    def dim(self):
+        return self.D
+
+    def nrows(self):
+        return [r.shape[0] for r in self.rows]
+
+    @property
+    def nbytes(self):
+        """Bytes of the row arrays (headers included)."""
+        return sum(r.numel() for r in self.rows)
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.ctx.lib.dlrm_q4_tables_destroy(self.handle)
+        except Exception:
+            pass
+
+
+class Q4Inference(Q8Inference):
+    """`Q8Inference` over 4-bit tables: dlrm_q4_lookup_interact_fwd where the fused kernel exists, else
+    dlrm_q4_maplookup + dlrm_interact_fwd, with the same bits.  `route`: "fused" or "two-launch"."""
+    _set_type = Quantized4TableSet
+    _fwd, _gather = "dlrm_q4_lookup_interact_fwd", "dlrm_q4_maplookup"

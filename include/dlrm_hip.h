@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DLRM_HIP_ABI_VERSION 5
+#define DLRM_HIP_ABI_VERSION 6
 
 typedef enum {
     DLRM_OK = 0,
@@ -886,6 +886,59 @@ int dlrm_q8_maplookup(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const void* indic
  * d % 4 == 0 (fp32) or d % 8 == 0 (bf16); every q pointer 4-B (fp32) or 8-B (bf16) aligned; x 16-B aligned
  * with x_ld % 4 == 0 (fp32) or x_ld % 8 == 0 (bf16).  out and out_ld need no alignment. */
 int dlrm_q8_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_q8_tables* q8, const void* indices, int itype,
+                                int64_t table_stride, int index_base, int batch, int lookups, int dtype,
+                                const void* x, int64_t x_ld, void* out, int64_t out_ld, int padding);
+
+/* ---- int4 row-quantized tables with in-row scale and bias (inference and evaluation) -----
+ * A quantized table t is ONE caller-owned device array of bytes, r[nrows[t]][S], S = dlrm_q4_row_bytes(dim) =
+ * 8 + 8 * ceil(dim / 16), 8-B aligned (so every row is: dim = 128 gives S = 72, dim = 16 gives 16).  A row is
+ *   float scale, float bias   (fp32, native order), then the codes: code c in byte 8 + c / 2, in the low nibble for
+ *   even c and the high nibble for odd c; pad nibbles and pad bytes are written as zero by the quantizer.
+ * A row of all-zero bytes dequantizes to a zero row: what an out-of-range index reads.  On average a dim = 128
+ * row lies in 1.5 128-B lines (2 for bf16 and int8 rows, 4 for fp32).
+ * The arithmetic is the int8 tables' with 15 levels, every operation a separately rounded fp32 operation (bf16
+ * elements first converted to fp32):
+ *   lo = min_c w[c]   hi = max_c w[c]   range = hi - lo
+ *   scale = range / 15.0f                       inv = range > 0 ? 15.0f / range : 0.0f    (IEEE division)
+ *   q[c]  = (uint8) min(15, max(0, rintf((w[c] - lo) * inv)))   (ties to even)        bias = lo
+ * Dequantizing is two roundings, never an fma:  v[c] = ((float)q[c] * scale) + bias; a bf16 consumer gets
+ * v[c] rounded to nearest even, once.  Every element of a finite row with a finite range satisfies
+ *   |v - w| <= (0.5 + 2^-10) * scale + 2^-22 * max(|lo|, |hi|);
+ * for any other row nothing faults and what is stored is unspecified.  Bitwise reproducible.  No reference
+ * counterpart (DLRM.jl trains and scores fp32); the format is FBGEMM's fused 4-bit rowwise idea with the
+ * header in front.
+ * row_bytes: pure host; S, or DLRM_E_ARG for dim <= 0.
+ * create: no device work but the upload of the descriptors; the arrays stay caller-owned.  DLRM_E_ARG for a
+ *         rows pointer that is not 8-B aligned.
+ * quantize: src is fp32 or bf16; table count, dim and row counts must match (else DLRM_E_ARG); one launch
+ *           over every table, 64-bit row offsets.  16 elements per lane in 16-B vectors where dim % 16 == 0 and
+ *           the source rows are 16-B aligned, element by element otherwise, with the same results.
+ * dequantize: writes v (fp32) or bf16(v) into an existing table set of the same shape: the way back.
+ * The launching calls allocate nothing and do not synchronise (hipGraph-capturable); an out-of-range
+ * index never faults, contributes a zero row and raises the flag dlrm_check_bounds reads. */
+typedef struct dlrm_q4_tables dlrm_q4_tables;
+int dlrm_q4_row_bytes(int dim);
+int dlrm_q4_tables_create(dlrm_ctx* ctx, int num_tables, int dim, uint8_t* const* rows, const int64_t* nrows,
+                          dlrm_q4_tables** out);
+int dlrm_q4_tables_destroy(dlrm_q4_tables* q4);
+int dlrm_q4_quantize(dlrm_ctx* ctx, const dlrm_tables* src, dlrm_q4_tables* dst);
+int dlrm_q4_dequantize(dlrm_ctx* ctx, const dlrm_q4_tables* src, dlrm_tables* dst);
+
+/* dlrm_maplookup reading 4-bit rows: the contract of dlrm_q8_maplookup -- out (of `dtype`) receives exactly what
+ * dlrm_maplookup over the dlrm_q4_dequantize'd set of that dtype writes, pooled (lookups > 1) included.  Any
+ * dim >= 1; 16-B output stores where dim % 16 == 0 and the output rows are 16-B aligned, element stores
+ * otherwise, with the same results. */
+int dlrm_q4_maplookup(dlrm_ctx* ctx, const dlrm_q4_tables* q4, const void* indices, int itype,
+                      int64_t table_stride, int index_base, int batch, int lookups, int dtype,
+                      void* out, int64_t out_ld, int64_t out_offset);
+
+/* The inference forward on 4-bit rows in ONE launch, no ys: the contract of dlrm_q8_lookup_interact_fwd -- out
+ * (of `dtype`, as x) receives exactly what dlrm_q4_maplookup(out_offset = d, into a ys) + dlrm_interact_fwd
+ * write.  Requires q4->dim == d.  Returns DLRM_E_UNSUPPORTED, with nothing launched, where there is no fused
+ * kernel; the caller then takes those two calls.  The fused kernel exists exactly for: lookups == 1;
+ * 1 <= num_tables <= 31; d % 16 == 0; x 16-B aligned with x_ld % 4 == 0 (fp32) or x_ld % 8 == 0 (bf16).  The
+ * rows need nothing beyond their 8-B alignment; out and out_ld need no alignment. */
+int dlrm_q4_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_q4_tables* q4, const void* indices, int itype,
                                 int64_t table_stride, int index_base, int batch, int lookups, int dtype,
                                 const void* x, int64_t x_ld, void* out, int64_t out_ld, int padding);
 
