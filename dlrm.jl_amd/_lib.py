@@ -91,6 +91,8 @@ SIGNATURES = {
     "dlrm_q4_maplookup": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64]),
     "dlrm_q4_lookup_interact_fwd": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64,
                                             _i32]),
+    "dlrm_q4_bags_interact_fwd": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64,
+                                          _i32]),
     "dlrm_mlp_bf16_plan": (_i32, [_i32, _pi32, _i32, _i32, _i32, _pi32, _pi32, _pi64, _pi64, _pi32, _pi32]),
     "dlrm_mlp_bf16_create": (_i32, [_vp, _i32, _pi32, _pp]),
     "dlrm_mlp_bf16_destroy": (_i32, [_vp]),

@@ -968,6 +968,21 @@ int dlrm_q4_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_q4_tables* q4, const v
                                          batch, lookups, dtype, x, x_ld, out, out_ld, padding);
 }
 
+int dlrm_q4_bags_interact_fwd(dlrm_ctx* ctx, const dlrm_q4_tables* q4, const void* indices, int itype,
+                              int64_t table_stride, int index_base, int batch, int lookups, int dtype, const void* x,
+                              int64_t x_ld, void* out, int64_t out_ld, int padding) {
+    CHECK_ARG(ctx && q4, "dlrm_q4_bags_interact_fwd: null ctx/tables");
+    const int rc = check_q4_indices(ctx, q4, indices, itype, table_stride, batch, lookups, dtype);
+    if (rc) return rc;
+    const int d = q4->D, F = q4->T + 1;
+    const int64_t P = (int64_t)F * (F - 1) / 2;
+    CHECK_ARG(padding >= 0 && x_ld >= d && out_ld >= d + P + padding,
+              "dlrm_q4_bags_interact_fwd: leading dimensions too small");
+    CHECK_ARG(batch == 0 || (x && out), "dlrm_q4_bags_interact_fwd: null buffer");
+    return launch_q4_bags_interact_fwd(ctx, q4->d_desc, q4->T, d, indices, itype, table_stride, index_base, batch,
+                                       lookups, dtype, x, x_ld, out, out_ld, padding);
+}
+
 // ------------------------------------------------------------- fused bf16 MLP inference
 // (DLRM_MLP_MT = 16 / 32: the comparison knob that takes the plan's tile height out of its rule's hands)
 static int mlp_force_mt() {

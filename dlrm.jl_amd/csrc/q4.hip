@@ -14,7 +14,9 @@
 // write: the same MFMA lane layout (fwd_onehot.hpp: lane (c, q) holds columns step * COLS + q * PER_LANE .. of row
 // 16 I + c) and the same even / odd column-step partials.  Its loads are wide: the four lanes that own a row fetch
 // 16 bytes of it each and bring the nibbles into operand order by a 4 x 4 dword transpose in registers
-// (v_permlane32_swap, v_permlane16_swap).
+// (v_permlane32_swap, v_permlane16_swap).  The pooled forward (q4_bags_fwd_kernel) serves bags of
+// any size and up to 95 tables with the same bits: a workgroup per sample pools the bags into an LDS operand tile in the
+// gather's rounds and runs the Gram from it.
 #include <type_traits>
 
 #include "fwd_onehot.hpp"
@@ -189,14 +191,67 @@ __global__ __launch_bounds__(256) void q4_dequantize_kernel(const Q4Desc* __rest
     }
 }
 
+// ---------------------------------------------------------------------------- pooling round
+// One round of KB lookups, k0 .. k0 + KB - 1, of a lane's U (table, sample) items, shared by the gather and the
+// pooled fused forward.  Item u is the 8-byte piece (16 codes) at column c0[u] of table td[u]'s bag whose first index
+// sits at position ip[u]; a dead item (live[u] false) reads the zero row and sums to zero.  Every index load is issued
+// first, then every piece load together with its row's header load -- the first 8 bytes of the same row, one address
+// computation off the index and as a rule the same 128-B line, not a second array -- then the k-ordered fp32 sums
+// (seeded with the first row) of the rows as their consumer holds them (v, or bf16(v)).  An out-of-range index reads
+// 16 bytes of the zero row (scale = bias = 0: a zero row) and sets bad in the lane that owns the row's first piece.
+template <typename T, int U, int KB>
+__device__ __forceinline__ void q4_pool_round(const Q4Desc* td, const bool* live, const int* c0, const int64_t* ip,
+                                              int k0, int L, int64_t S, const void* __restrict__ idx, int itype, int base,
+                                              float (*acc)[16], bool& bad) {
+    const uint8_t* zero8 = (const uint8_t*)g_zero_row;
+    int64_t ri[U][KB];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk) ri[u][kk] = load_index_if(live[u] && k0 + kk < L, idx, itype, ip[u] + k0 + kk);
+    const uint8_t* hp[U][KB];  // the row (its header), and this lane's piece of it
+    const uint8_t* pp[U][KB];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk) {
+            const bool use = live[u] && k0 + kk < L;
+            const int64_t r = ri[u][kk] - base;
+            const bool ok = use & (r >= 0) & (r < td[u].nrows);
+            bad |= use & !ok & (c0[u] == 0);
+            hp[u][kk] = ok ? td[u].r + r * S : zero8;
+            pp[u][kk] = ok ? td[u].r + r * S + 8 + (c0[u] >> 1) : zero8 + 8;
+        }
+    __builtin_amdgcn_sched_barrier(0);
+    u32x2_t raw[U][KB];
+    float2 sb[U][KB];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk) {
+            raw[u][kk] = ldg<u32x2_t>(pp[u][kk]);
+            sb[u][kk] = q4_load_header(hp[u][kk]);
+        }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk) {
+            if (k0 + kk >= L) break;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                // a bf16 consumer's row is bf16(v), as the dequantized set holds it (fp32: the identity)
+                const float f = to_f32(from_f32<T>(q4_value(q4_nibble(raw[u][kk], e), sb[u][kk].x, sb[u][kk].y)));
+                acc[u][e] = (k0 + kk == 0) ? f : acc[u][e] + f;
+            }
+        }
+}
+
 // ---------------------------------------------------------------------------- gather
 // dlrm_maplookup on quantized rows, in q8_maplookup_kernel's round structure: a lane owns one 8-byte piece (16 codes)
-// of U (sample, table) items; per round of KB lookups every index load (with the descriptors) is issued first, then
-// every piece load together with its row's header load -- the first 8 bytes of the same row, one address computation
-// off the index and as a rule the same 128-B line, not a second array -- then the k-ordered fp32 sums (seeded with
-// the first row) of the rows as their consumer holds them (v, or bf16(v)), converted once: dlrm_maplookup over the
-// dequantized set, bit for bit.  An out-of-range index reads 16 bytes of the zero row (scale = bias = 0: a zero row)
-// and raises the flag after the stores.  VEC: how the output row is written (q4_store_elems).
+// of U (sample, table) items and sums it over the bag in rounds of KB lookups (q4_pool_round), converted once:
+// dlrm_maplookup over the dequantized set, bit for bit.  The bounds flag is raised after the stores.  VEC: how the
+// output row is written (q4_store_elems).
 template <typename T, bool VEC, int U, int KB>
 __global__ __launch_bounds__(256) void q4_maplookup_kernel(const Q4Desc* __restrict__ tabs, int ntab, int D, int64_t S,
                                                            const void* __restrict__ idx, int itype, int64_t tstride,
@@ -205,7 +260,6 @@ __global__ __launch_bounds__(256) void q4_maplookup_kernel(const Q4Desc* __restr
     const int cpr = (D + 15) >> 4;
     const int64_t total = (int64_t)ntab * B * cpr;
     const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-    const uint8_t* zero8 = (const uint8_t*)g_zero_row;
     bool bad = false;
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < total; i0 += nthreads * U) {
         bool live[U];
@@ -223,51 +277,11 @@ __global__ __launch_bounds__(256) void q4_maplookup_kernel(const Q4Desc* __restr
             tt[u] = (int)(bt - bb[u] * ntab);
             td[u] = load_q4(tabs, tt[u]);
         }
+        int64_t ip[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) ip[u] = tt[u] * tstride + bb[u] * L;
         float acc[U][16];
-        for (int k0 = 0; k0 < L; k0 += KB) {
-            int64_t ri[U][KB];
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int kk = 0; kk < KB; ++kk)
-                    ri[u][kk] = load_index_if(live[u] && k0 + kk < L, idx, itype, tt[u] * tstride + bb[u] * L + k0 + kk);
-            const uint8_t* hp[U][KB];  // the row (its header), and this lane's piece of it
-            const uint8_t* pp[U][KB];
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int kk = 0; kk < KB; ++kk) {
-                    const bool use = live[u] && k0 + kk < L;
-                    const int64_t r = ri[u][kk] - base;
-                    const bool ok = use & (r >= 0) & (r < td[u].nrows);
-                    bad |= use & !ok & (c0[u] == 0);
-                    hp[u][kk] = ok ? td[u].r + r * S : zero8;
-                    pp[u][kk] = ok ? td[u].r + r * S + 8 + (c0[u] >> 1) : zero8 + 8;
-                }
-            __builtin_amdgcn_sched_barrier(0);
-            u32x2_t raw[U][KB];
-            float2 sb[U][KB];
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int kk = 0; kk < KB; ++kk) {
-                    raw[u][kk] = ldg<u32x2_t>(pp[u][kk]);
-                    sb[u][kk] = q4_load_header(hp[u][kk]);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int kk = 0; kk < KB; ++kk) {
-                    if (k0 + kk >= L) break;
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        // a bf16 consumer's row is bf16(v), as the dequantized set holds it (fp32: the identity)
-                        const float f = to_f32(from_f32<T>(q4_value(q4_nibble(raw[u][kk], e), sb[u][kk].x, sb[u][kk].y)));
-                        acc[u][e] = (k0 + kk == 0) ? f : acc[u][e] + f;
-                    }
-                }
-        }
+        for (int k0 = 0; k0 < L; k0 += KB) q4_pool_round<T, U, KB>(td, live, c0, ip, k0, L, S, idx, itype, base, acc, bad);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (!live[u]) continue;
@@ -501,6 +515,144 @@ __global__ __launch_bounds__(256, 2) void q4_fwd_kernel(int d_, int F, int B, co
     if (bad_any) raise_index_error(err);
 }
 
+// ---------------------------------------------------------------------------- fused forward, pooled bags
+// Lookup (bags of L >= 1 rows, summed) + interaction over quantized rows of 1 .. 95 tables, one launch, no ys: the
+// bits of q4_maplookup_kernel + interact.hip's forward.  One workgroup of four waves per sample, grid-strided over the
+// batch; per column block of CB columns (q4_plan.hpp: the whole d, or 128 at a time) two phases around a barrier.
+// Phase A, pool: the block's T x CB / 16 pieces are dealt over the 256 lanes, one to a lane at a time, and summed
+//   over the bag by q4_pool_round (the gather's rounds of 4 lookups, its arithmetic and its order); the pooled piece,
+//   rounded to T once, goes to row t + 1 of the LDS operand tile rows[16 NB][CB + pad].  Row 0 is x, loaded in 16-B
+//   fragments before the gather is issued and also copied to the head of the output row; rows F .. 16 NB - 1 are
+//   zeroed once per workgroup.  A piece past d inside the block's last column step (bf16, d % 32 == 16) is a dead
+//   item: it pools the zero row and so clears its 16 columns of the tile.
+// Phase B, Gram: tile k = I (I + 1) / 2 + J of the NB (NB + 1) / 2 lower-triangle 16 x 16 tiles belongs to wave k % 4.
+//   A wave walks the block's column steps in ascending order; lane (c, q) reads columns step * COLS + q * PER_LANE ..
+//   of rows 16 I + c and 16 J + c from the tile (fwd_onehot.hpp's operand layout, one 16-B LDS read each) and issues
+//   Frag<T>::mma into the tile's accumulator, which lives across column blocks.  NB <= 2: even and odd steps in two
+//   partials, Z = even + odd; NB >= 3: one chain -- dlrm_interact_fwd's orders.  (A multi-block CB is 128 columns,
+//   an even number of steps, so a step's parity within its block is its parity within the row.)
+// Output: Z[i][j], i > j, i-major after x, stored from the accumulators (lanes c = 0 .. 15 write 16 consecutive
+// elements), then the padding zeros.  out needs no alignment.
+extern __shared__ __attribute__((aligned(16))) unsigned char q4_bags_lds[];
+
+template <typename T, int NB>
+__global__ __launch_bounds__(256, NB <= 4 ? 4 : 2) void q4_bags_fwd_kernel(const Q4Desc* __restrict__ tabs, int d, int F, int B, int CB,
+                                                             const T* __restrict__ x, int64_t x_ld, T* __restrict__ out,
+                                                             int64_t out_ld, int padding, const void* __restrict__ idx,
+                                                             int itype, int64_t tstride, int base, int L,
+                                                             unsigned* __restrict__ err) {
+    typedef Frag<T> FR;
+    typedef typename FR::type frag;
+    constexpr int PL = FR::PER_LANE, COLS = FR::COLS;  // PL elements = 16 bytes
+    constexpr int NT = NB * (NB + 1) / 2, MT = (NT + 3) / 4, NPART = NB <= 2 ? 2 : 1;
+    constexpr int U = 1, KB = 4;
+    T* rows = (T*)q4_bags_lds;
+    const int LD = CB + PL;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 15, q = lane >> 4;
+    const int ntab = F - 1;
+    const int64_t S = 8 + (d >> 1);  // (d % 16 == 0: q4_row_bytes)
+    const int P = F * (F - 1) / 2, W = d + P + padding;
+    const T* zero = (const T*)g_zero_row;
+    for (int i = F * (LD / PL) + tid; i < 16 * NB * (LD / PL); i += 256) *(frag*)(rows + i * PL) = FR::zero();
+    int tI[MT], tJ[MT];  // this wave's tiles
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const int k = w + 4 * m;
+        int I = 0;
+        while ((I + 1) * (I + 2) / 2 <= k) ++I;
+        tI[m] = I;
+        tJ[m] = k - I * (I + 1) / 2;
+    }
+    bool bad = false;
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        const T* xb = x + b * x_ld;
+        T* orow = out + b * out_ld;
+        f32x4_t acc[NPART][MT];
+#pragma unroll
+        for (int pp = 0; pp < NPART; ++pp)
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[pp][m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int u0 = 0; u0 < d; u0 += CB) {
+            const int valid = d - u0 < CB ? d - u0 : CB;         // columns of this block inside d ...
+            const int vpad = (valid + COLS - 1) / COLS * COLS;  // ... and up to the end of its last column step
+            // ---- phase A
+            const int xc = tid * PL;
+            frag xf = FR::zero();
+            if (xc < vpad) xf = ldg<frag>(xc < valid ? xb + u0 + xc : zero);
+            const int ppb = vpad >> 4, nitems = ntab * ppb;
+            for (int it0 = tid; it0 < nitems; it0 += 256 * U) {
+                bool have[U], live[U];
+                int c0[U], tt[U];
+                int64_t ip[U];
+                Q4Desc td[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int item = it0 + 256 * u;
+                    have[u] = item < nitems;
+                    tt[u] = have[u] ? item / ppb : 0;
+                    const int col = (have[u] ? item - tt[u] * ppb : 0) * 16;
+                    c0[u] = u0 + col;
+                    live[u] = have[u] && col < valid;
+                    td[u] = load_q4(tabs, tt[u]);
+                    ip[u] = tt[u] * tstride + b * L;
+                }
+                float sum[U][16];
+                for (int k0 = 0; k0 < L; k0 += KB)
+                    q4_pool_round<T, U, KB>(td, live, c0, ip, k0, L, S, idx, itype, base, sum, bad);
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (!have[u]) continue;
+                    T* dst = rows + (tt[u] + 1) * LD + (c0[u] - u0);
+#pragma unroll
+                    for (int e = 0; e < 16; e += PL) *(frag*)(dst + e) = FR::from_f(sum[u] + e);
+                }
+            }
+            if (xc < vpad) {
+                *(frag*)(rows + xc) = xf;
+                if (xc < valid) {
+                    float f[PL];
+                    FR::to_f(f, xf);
+#pragma unroll
+                    for (int k = 0; k < PL; ++k) stg<T>(orow + u0 + xc + k, from_f32<T>(f[k]));
+                }
+            }
+            __syncthreads();
+            // ---- phase B
+            const int nsteps = vpad / COLS;
+            for (int v = 0; v < nsteps; v += 2) {
+#pragma unroll
+                for (int pp = 0; pp < 2; ++pp) {
+                    if (v + pp >= nsteps) break;
+                    const int col = (v + pp) * COLS + q * PL;
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) {
+                        if (w + 4 * m >= NT) break;  // (wave-uniform)
+                        const frag a = *(const frag*)(rows + (16 * tI[m] + c) * LD + col);
+                        const frag bj = *(const frag*)(rows + (16 * tJ[m] + c) * LD + col);
+                        FR::mma(acc[NPART == 2 ? pp : 0][m], a, bj);
+                    }
+                }
+            }
+            __syncthreads();  // the next block, or the next sample, rewrites the tile
+        }
+        // Z[i][j], i > j: triangular_slice_kernel! order (i-major), after x
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            if (w + 4 * m >= NT) break;
+            const f32x4_t z = NPART == 2 ? acc[0][m] + acc[NPART - 1][m] : acc[0][m];
+            const int j = tJ[m] * 16 + c;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = tI[m] * 16 + 4 * q + r;
+                if (i < F && j < i) stg<T>(orow + d + i * (i - 1) / 2 + j, from_f32<T>(z[r]));
+            }
+        }
+        for (int e = d + P + tid; e < W; e += 256) stg<T>(orow + e, from_f32<T>(0.0f));
+    }
+    if (bad) raise_index_error(err);
+}
+
 // ---------------------------------------------------------------------------- launchers
 static unsigned q4_grid(int64_t items, int per_block, int cus, int per_cu) {
     int64_t g = (items + per_block - 1) / per_block;
@@ -596,6 +748,42 @@ int launch_q4_lookup_interact_fwd(dlrm_ctx* ctx, const Q4Desc* htabs, int T_, in
         launch_q4_fwd<uint16_t>(ctx_stream(ctx), grid, NB, d, F, B, x, x_ld, out, out_ld, padding, idx, itype, tstride,
                                 base, ctx_error_word(ctx), tp);
     return ctx_hip(ctx, hipGetLastError(), "q4_lookup_interact_fwd launch");
+}
+
+template <typename T>
+static void launch_q4_bags(hipStream_t s, unsigned grid, unsigned lds, int NB, const Q4Desc* tabs, int d, int F, int B,
+                           int CB, const void* x, int64_t x_ld, void* out, int64_t out_ld, int padding, const void* idx,
+                           int itype, int64_t tstride, int base, int L, unsigned* err) {
+#define DLRM_Q4_GO(NB_)                                                                                               \
+    hipLaunchKernelGGL((q4_bags_fwd_kernel<T, NB_>), dim3(grid), dim3(256), lds, s, tabs, d, F, B, CB, (const T*)x, x_ld, \
+                       (T*)out, out_ld, padding, idx, itype, tstride, base, L, err)
+    switch (NB) {
+    case 1: DLRM_Q4_GO(1); break;
+    case 2: DLRM_Q4_GO(2); break;
+    case 3: DLRM_Q4_GO(3); break;
+    case 4: DLRM_Q4_GO(4); break;
+    case 5: DLRM_Q4_GO(5); break;
+    default: DLRM_Q4_GO(6); break;
+    }
+#undef DLRM_Q4_GO
+}
+
+int launch_q4_bags_interact_fwd(dlrm_ctx* ctx, const Q4Desc* tabs, int T_, int d, const void* idx, int itype,
+                                int64_t tstride, int base, int B, int L, int dtype, const void* x, int64_t x_ld, void* out,
+                                int64_t out_ld, int padding) {
+    if (!q4_bags_fused(dtype, d, T_, L, x, x_ld)) return DLRM_E_UNSUPPORTED;
+    if (B == 0) return DLRM_OK;
+    const int F = T_ + 1, NB = (F + 15) / 16, CB = q4_bags_cb(dtype, d);
+    const unsigned lds = (unsigned)q4_bags_lds_bytes(dtype, d, T_);
+    // a workgroup per sample; at most 8 per CU in flight (registers allow 4 at NB <= 4, else 2), the rest grid-strides
+    const unsigned grid = q4_grid(B, 1, ctx_num_cus(ctx), 8);
+    if (dtype == DLRM_F32)
+        launch_q4_bags<float>(ctx_stream(ctx), grid, lds, NB, tabs, d, F, B, CB, x, x_ld, out, out_ld, padding, idx, itype,
+                              tstride, base, L, ctx_error_word(ctx));
+    else
+        launch_q4_bags<uint16_t>(ctx_stream(ctx), grid, lds, NB, tabs, d, F, B, CB, x, x_ld, out, out_ld, padding, idx,
+                                 itype, tstride, base, L, ctx_error_word(ctx));
+    return ctx_hip(ctx, hipGetLastError(), "q4_bags_interact_fwd launch");
 }
 
 }  // namespace dlrm

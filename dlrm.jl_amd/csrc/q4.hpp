@@ -27,5 +27,9 @@ int launch_q4_maplookup(dlrm_ctx* ctx, const Q4Desc* tabs, int T, int D, const v
 int launch_q4_lookup_interact_fwd(dlrm_ctx* ctx, const Q4Desc* htabs, int T, int d, const void* idx, int itype,
                                   int64_t tstride, int base, int B, int L, int dtype, const void* x, int64_t x_ld,
                                   void* out, int64_t out_ld, int padding);
+// tabs: the device descriptors.  DLRM_E_UNSUPPORTED, nothing launched: q4_plan.hpp q4_bags_fused says no.
+int launch_q4_bags_interact_fwd(dlrm_ctx* ctx, const Q4Desc* tabs, int T, int d, const void* idx, int itype,
+                                int64_t tstride, int base, int B, int L, int dtype, const void* x, int64_t x_ld,
+                                void* out, int64_t out_ld, int padding);
 
 }  // namespace dlrm

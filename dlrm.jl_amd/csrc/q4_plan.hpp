@@ -38,4 +38,28 @@ inline bool q4_fwd_fused(int dtype, int d, int T, int lookups, const void* x, in
     return lookups == 1 && T >= 1 && T <= kQ4ArgTables && d % 16 == 0 && q4_at(x, 16) && x_ld % vec == 0;
 }
 
+// dlrm_q4_bags_interact_fwd (q4_bags_fwd_kernel: a workgroup per sample pools the bags into an LDS operand tile and
+// runs the Gram from it) has a kernel exactly here (else DLRM_E_UNSUPPORTED, nothing launched):
+//  - lookups >= 1 (bags of any size, one-hot included) of 1 .. 95 tables (F = T + 1 <= 96 features: NB = 1 .. 6 MFMA
+//    row blocks, the range in which dlrm_interact_fwd runs its MFMA kernel);
+//  - d % 16 == 0 and x as for q4_fwd_fused.
+constexpr int kQ4BagTables = 95;
+inline bool q4_bags_fused(int dtype, int d, int T, int lookups, const void* x, int64_t x_ld) {
+    const int vec = dtype == DLRM_F32 ? 4 : 8;
+    return lookups >= 1 && T >= 1 && T <= kQ4BagTables && d % 16 == 0 && q4_at(x, 16) && x_ld % vec == 0;
+}
+
+// The operand tile rows[16 NB][CB + pad] of the element type.  CB, the column block: the whole d, rounded up to a
+// column step (16 fp32 or 32 bf16 columns), where a row of it is at most 512 B (d <= 128 fp32, d <= 256 bf16), else 128
+// columns at a time.  pad = 16 B: the row stride is an odd number of 16-B units, so the 16-B reads of 16 consecutive
+// rows at one column fall in 16 distinct quarters of the 64 banks.  At most 96 * 528 = 50688 B (F = 96).
+inline int q4_bags_cb(int dtype, int d) {
+    const int esz = dtype == DLRM_F32 ? 4 : 2, cols = dtype == DLRM_F32 ? 16 : 32;
+    return (int64_t)d * esz <= 512 ? (d + cols - 1) / cols * cols : 128;
+}
+inline int q4_bags_lds_bytes(int dtype, int d, int T) {
+    const int esz = dtype == DLRM_F32 ? 4 : 2, NB = (T + 1 + 15) / 16;
+    return 16 * NB * (q4_bags_cb(dtype, d) * esz + 16);
+}
+
 }  // namespace dlrm

@@ -299,7 +299,8 @@ class DLRMModel:
         if self._q4 is None or self._q4[0] is not q4:
             if len(q4) != len(self.tables) or q4.D != self.tables.D:
                 raise ValueError("q4 does not match the model's tables (count, feature size)")
-            self._q4 = (q4, Q4Inference(q4, self.hot.B, self.hot.L, d=self.hot.d, dtype=self.tdtype,
+            # bags: pooled models and models of 32 .. 95 tables score in one launch too
+            self._q4 = (q4, Q4Inference(q4, self.hot.B, self.hot.L, bags=True, d=self.hot.d, dtype=self.tdtype,
                                         index_base=self.hot.index_base, pad_to=self._pad_to))
         return self._q4[1]
 

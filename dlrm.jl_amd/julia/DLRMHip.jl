@@ -1457,8 +1457,9 @@ EmbeddingTables.maplookup(s::PreallocationStrategy, q4::HipQ4Tables, sparse) =
 """
     infer(dot::HipDotInteraction, x::DeviceMatrix, q4::HipQ4Tables, sparse)
 
-The inference forward on 4-bit rows: one launch (`dlrm_q4_lookup_interact_fwd`) where the fused kernel exists,
-else the gather and `dlrm_interact_fwd`, with the same bits.
+The inference forward on 4-bit rows: one launch where a fused kernel exists (`dlrm_q4_lookup_interact_fwd` for
+one-hot indices of up to 31 tables, then `dlrm_q4_bags_interact_fwd` for pooled bags and up to 95 tables), else
+the gather and `dlrm_interact_fwd`, with the same bits.
 """
 function infer(dot::HipDotInteraction, x::DeviceMatrix{T}, q4::HipQ4Tables{D}, sparse) where {D,T}
     ctx = q4.ctx
@@ -1472,7 +1473,14 @@ function infer(dot::HipDotInteraction, x::DeviceMatrix{T}, q4::HipQ4Tables{D}, s
                 Ptr{Cvoid}, Int64, Cint),
                ctx.ptr, q4.ptr, idx.data.ptr, DLRM_I32, idx.batch * idx.lookups, 1, B, idx.lookups,
                dtype_code(T), x.ptr, d, out.ptr, width, padding)
-    if rc == Cint(-4)  # DLRM_E_UNSUPPORTED: no fused kernel for this shape
+    if rc == Cint(-4)  # DLRM_E_UNSUPPORTED: the pooled-bag kernel next
+        rc = ccall((:dlrm_q4_bags_interact_fwd, libdlrm), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Int64,
+                    Ptr{Cvoid}, Int64, Cint),
+                   ctx.ptr, q4.ptr, idx.data.ptr, DLRM_I32, idx.batch * idx.lookups, 1, B, idx.lookups,
+                   dtype_code(T), x.ptr, d, out.ptr, width, padding)
+    end
+    if rc == Cint(-4)  # no fused kernel for this shape
         ys, _ = _maplookup(q4, idx, d, T)
         check(ctx, ccall((:dlrm_interact_fwd, libdlrm), Cint,
                          (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cint),

@@ -379,6 +379,35 @@ class Quantized4TableSet:
 
 class Q4Inference(Q8Inference):
     """`Q8Inference` over 4-bit tables: dlrm_q4_lookup_interact_fwd where the fused kernel exists, else
-    dlrm_q4_maplookup + dlrm_interact_fwd, with the same bits.  `route`: "fused" or "two-launch"."""
+    dlrm_q4_maplookup + dlrm_interact_fwd, with the same bits.  `route`: "fused" or "two-launch".
+
+    bags=True puts dlrm_q4_bags_interact_fwd between the two: pooled bags (lookups > 1) and 32 .. 95 tables in one
+    launch with no `ys` (`route` "bags"), the same bits again."""
     _set_type = Quantized4TableSet
     _fwd, _gather = "dlrm_q4_lookup_interact_fwd", "dlrm_q4_maplookup"
+
+    def __init__(self, q4, batch, lookups=1, *, bags=False, **kw):
+        super().__init__(q4, batch, lookups, **kw)
+        self.bags = bool(bags)
+
+    def bags_fused(self, x, idx, out=None):
+        """The raw dlrm_q4_bags_interact_fwd call's status: _lib.OK (launched) or _lib.E_UNSUPPORTED (nothing launched)."""
+        from .runtime import ptr
+        out = self.out if out is None else out
+        rc = self.lib.dlrm_q4_bags_interact_fwd(self.ctx.bind(), self.q8.handle, ptr(idx.data), idx.itype, idx.stride,
+                                                self.index_base, self.B, self.L, self.dcode, ptr(x), x.stride(0),
+                                                ptr(out), out.stride(0), self.padding)
+        if rc != _lib.E_UNSUPPORTED:
+            self._check(rc)
+        return rc
+
+    def infer(self, x, idx, out=None):
+        """`Q8Inference.infer`; with bags=True the routes in order: "fused", "bags", "two-launch"."""
+        if self.route != "two-launch":
+            if self.fused(x, idx, out) == _lib.OK:
+                self.route = "fused"
+                return self.out if out is None else out
+            if self.bags and self.bags_fused(x, idx, out) == _lib.OK:
+                self.route = "bags"
+                return self.out if out is None else out
+        return self.two_launch(x, idx, out)

@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DLRM_HIP_ABI_VERSION 6
+#define DLRM_HIP_ABI_VERSION 7
 
 typedef enum {
     DLRM_OK = 0,
@@ -941,6 +941,17 @@ int dlrm_q4_maplookup(dlrm_ctx* ctx, const dlrm_q4_tables* q4, const void* indic
 int dlrm_q4_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_q4_tables* q4, const void* indices, int itype,
                                 int64_t table_stride, int index_base, int batch, int lookups, int dtype,
                                 const void* x, int64_t x_ld, void* out, int64_t out_ld, int padding);
+
+/* The same forward for pooled bags and up to 95 tables, in ONE launch, no ys: the argument list and contract of
+ * dlrm_q4_lookup_interact_fwd -- out receives exactly what dlrm_q4_maplookup(out_offset = d, into a ys) +
+ * dlrm_interact_fwd write (each looked-up row as `dtype` holds it, summed in fp32 in lookup order, rounded once; the
+ * Gram in dlrm_interact_fwd's MFMA order).  A workgroup per sample pools the bags into an LDS operand tile and runs
+ * the Gram from it.  Returns DLRM_E_UNSUPPORTED, with nothing launched, outside its domain, which is exactly:
+ * lookups >= 1; 1 <= num_tables <= 95; d % 16 == 0; x 16-B aligned with x_ld % 4 == 0 (fp32) or x_ld % 8 == 0
+ * (bf16).  The rows need nothing beyond their 8-B alignment; out and out_ld need no alignment. */
+int dlrm_q4_bags_interact_fwd(dlrm_ctx* ctx, const dlrm_q4_tables* q4, const void* indices, int itype,
+                              int64_t table_stride, int index_base, int batch, int lookups, int dtype,
+                              const void* x, int64_t x_ld, void* out, int64_t out_ld, int padding);
 
 /* ---- fused bf16 MLP inference: a whole Dense chain in one launch -------------------------
  * A chain of `layers` Dense layers, a_{l+1} = act_l(a_l W_l^T + b_l), with sizes[0 .. layers] the widths

@@ -14,6 +14,13 @@ median (min - max) of the five windows, in us per batch:
     q4_f32_us           Q4Inference.infer, fp32 x / out (one launch)
     q4_bf16_us          Q4Inference.infer, bf16 x / out (one launch)
     q4_two_launch_us    dlrm_q4_maplookup + dlrm_interact_fwd, bf16 x / out
+    q4_two_launch_f32_us   the same, fp32 x / out
+    q4_bags_f32_us      dlrm_q4_bags_interact_fwd, fp32 x / out (one launch)
+    q4_bags_bf16_us     dlrm_q4_bags_interact_fwd, bf16 x / out (one launch)
+
+A pooled workload (lookups > 1, e.g. pooled-64x256-l10) or one of more than 31 tables has no one-hot fused kernel:
+q4_f32_us, q4_bf16_us and q8_bf16_us are left out there, and the comparison that matters is q4_bags_* against
+q4_two_launch_* of the same run.
 
 --quantizer: dlrm_q4_quantize's rate over the workload's whole set in one launch (bytes read + written per second,
 best of five) beside bench.py's measured copy rate.  Prints one JSON line.  No threshold: the yardsticks are the
@@ -34,7 +41,9 @@ sys.path.insert(0, ROOT)
 import dlrm_pkg  # noqa: E402
 
 NB = 8
-NAMES = ("infer_f32_us", "infer_bf16_us", "q8_bf16_us", "q4_f32_us", "q4_bf16_us", "q4_two_launch_us")
+NAMES = ("infer_f32_us", "infer_bf16_us", "q8_bf16_us", "q4_f32_us", "q4_bf16_us", "q4_two_launch_us",
+         "q4_two_launch_f32_us", "q4_bags_f32_us", "q4_bags_bf16_us")
+ONEHOT = ("q8_bf16_us", "q4_f32_us", "q4_bf16_us")  # the one-hot fused kernels: lookups == 1, at most 31 tables
 
 
 def graph_of(fn):
@@ -61,20 +70,20 @@ def main():
     pkg = dlrm_pkg.load()
     dev = torch.device("cuda:0")
     w = pkg.WORKLOADS[a.workload]
-    if w["lookups"] != 1:
-        raise SystemExit("bench_q4_infer: one-hot workloads only")
-    rows, D, B = w["rows"], w["dim"], w["batch"]
+    rows, D, B, L = w["rows"], w["dim"], w["batch"], w["lookups"]
     T = len(rows)
     only = [n for n in a.only.split(",") if n] or list(NAMES)
+    if L != 1 or T > 31:
+        only = [n for n in only if n not in ONEHOT]
     gen = torch.Generator(device=dev).manual_seed(51234)
     rng = np.random.default_rng(51234)
     if w.get("zipf"):
         perms = [pkg.zipf_perm(rng, n) for n in rows]
-        idx = [np.stack([pkg.zipf_rows(rng, n, B, w["zipf"], perm=perms[t]) for t, n in enumerate(rows)])
+        idx = [np.stack([pkg.zipf_rows(rng, n, B * L, w["zipf"], perm=perms[t]) for t, n in enumerate(rows)])
                for _ in range(NB)]
     else:
-        idx = [np.stack([rng.integers(0, n, size=B).astype(np.int32) for n in rows]) for _ in range(NB)]
-    packs = [pkg.PackedIndices(torch.from_numpy(i).to(dev).reshape(T, B, 1).contiguous()) for i in idx]
+        idx = [np.stack([rng.integers(0, n, size=B * L).astype(np.int32) for n in rows]) for _ in range(NB)]
+    packs = [pkg.PackedIndices(torch.from_numpy(i).to(dev).reshape(T, B, L).contiguous()) for i in idx]
     xs = {dt: [torch.randn((B, D), device=dev, generator=gen).to(dt) for _ in range(NB)]
           for dt in (torch.float32, torch.bfloat16)}
     sdt = torch.bfloat16 if w["dtype"] == "bf16" else torch.float32
@@ -114,7 +123,7 @@ def main():
     variants = {}  # name -> (graph, what keeps its memory alive)
     for name, dt in (("infer_f32_us", torch.float32), ("infer_bf16_us", torch.bfloat16)):
         if name in only:
-            hp = pkg.HotPath(tables(dt), B, 1, index_base=0)
+            hp = pkg.HotPath(tables(dt), B, L, index_base=0)
             variants[name] = (lambda k, hp=hp, dt=dt: hp.infer(xs[dt][k], packs[k]), hp)
     if "q8_bf16_us" in only:
         q8 = quantized(pkg.QuantizedTableSet)
@@ -124,20 +133,22 @@ def main():
     if any(n.startswith("q4") for n in only):
         q4 = quantized(pkg.Quantized4TableSet)
         out["q4_bytes"] = q4.nbytes
-        for name, dt, two in (("q4_f32_us", torch.float32, False), ("q4_bf16_us", torch.bfloat16, False),
-                              ("q4_two_launch_us", torch.bfloat16, True)):
+        for name, dt, how in (("q4_f32_us", torch.float32, "infer"), ("q4_bf16_us", torch.bfloat16, "infer"),
+                              ("q4_two_launch_us", torch.bfloat16, "two_launch"),
+                              ("q4_two_launch_f32_us", torch.float32, "two_launch"),
+                              ("q4_bags_f32_us", torch.float32, "bags_fused"),
+                              ("q4_bags_bf16_us", torch.bfloat16, "bags_fused")):
             if name in only:
-                eng = pkg.Q4Inference(q4, B, 1, dtype=dt)
-                fn = ((lambda k, eng=eng, dt=dt: eng.two_launch(xs[dt][k], packs[k])) if two
-                      else (lambda k, eng=eng, dt=dt: eng.infer(xs[dt][k], packs[k])))
-                variants[name] = (fn, eng)
+                eng = pkg.Q4Inference(q4, B, L, dtype=dt)
+                variants[name] = (lambda k, call=getattr(eng, how), dt=dt: call(xs[dt][k], packs[k]), eng)
     graphs = {}
     for name, (fn, eng) in variants.items():
         for k in range(NB):  # eager warm-up of every batch
-            fn(k)
+            r = fn(k)
+            assert "bags" not in name or r == pkg._lib.OK, (name, r)  # (the raw call's status: launched)
         torch.cuda.synchronize()
         eng.check_bounds()
-        if name.startswith("q"):
+        if name.startswith("q") and "bags" not in name:
             assert eng.route == ("two-launch" if "two_launch" in name else "fused"), (name, eng.route)
         graphs[name] = graph_of(fn)
         graphs[name].replay()
@@ -159,7 +170,7 @@ def main():
     print(json.dumps({
         "metric": "inference forward (lookup + interaction), int4 rows against fp32 / bf16 / int8 rows, 1 MI355X",
         "unit": "us per batch", **out,
-        "config": {"workload": a.workload, "tables": T, "dim": D, "batch": B, "indices": "zipf" if w.get("zipf") else "uniform",
+        "config": {"workload": a.workload, "tables": T, "dim": D, "batch": B, "lookups": L, "indices": "zipf" if w.get("zipf") else "uniform",
                    "launch": f"hipGraph replay ({NB} batches per graph), variants alternating", "windows": 5,
                    "replays_per_window": a.reps},
     }))
