@@ -15,6 +15,7 @@ from .embedding import (DefaultStrategy, EmbeddingTableSet, PackedIndices, Preal
 from .evaluate import Evaluator, eval_reference
 from .hotpath import HotPath
 from .mlp_bf16 import Bf16MLP, mlp_bf16_plan, mlp_bf16_reference
+from .mlp_fp8 import Fp8MLP, mlp_fp8_plan, mlp_fp8_reference, mx_quantize
 from .mlp_train_bf16 import Bf16TrainMLP, mlp_train_bf16_reference, mlp_train_plan
 from .quant import (Q4Inference, Q8Inference, Quantized4TableSet, QuantizedTableSet, dequantize_rows, dequantize_rows4,
                     pack_rows4, q4_bound, quantize_rows, quantize_rows4, unpack_rows4)
@@ -42,4 +43,5 @@ __all__ = [
     "Quantized4TableSet", "Q4Inference", "quantize_rows4", "dequantize_rows4", "pack_rows4", "unpack_rows4", "q4_bound",
     "Bf16MLP", "mlp_bf16_plan", "mlp_bf16_reference",
     "Bf16TrainMLP", "mlp_train_bf16_reference", "mlp_train_plan",
+    "Fp8MLP", "mlp_fp8_plan", "mlp_fp8_reference", "mx_quantize",
 ]

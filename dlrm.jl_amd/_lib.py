@@ -98,6 +98,11 @@ SIGNATURES = {
     "dlrm_mlp_bf16_destroy": (_i32, [_vp]),
     "dlrm_mlp_bf16_pack": (_i32, [_vp, _vp, _pp, _pi64, _pp]),
     "dlrm_mlp_bf16_infer": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _i32, _i64, _i32]),
+    "dlrm_mlp_fp8_plan": (_i32, [_i32, _pi32, _i32, _i32, _i32, _pi32, _pi32, _pi64, _pi64, _pi32, _pi32, _pi64]),
+    "dlrm_mlp_fp8_create": (_i32, [_vp, _i32, _pi32, _pp]),
+    "dlrm_mlp_fp8_destroy": (_i32, [_vp]),
+    "dlrm_mlp_fp8_pack": (_i32, [_vp, _vp, _pp, _pi64, _pp]),
+    "dlrm_mlp_fp8_infer": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _i32, _i64, _i32]),
     "dlrm_mlp_train_plan": (_i32, [_i32, _pi32, _i32, _vp]),
     "dlrm_mlp_train_create": (_i32, [_vp, _i32, _pi32, _i32, _pp]),
     "dlrm_mlp_train_destroy": (_i32, [_vp]),

@@ -25,6 +25,7 @@
 #include "q8.hpp"
 #include "q4.hpp"
 #include "mlp_bf16.hpp"
+#include "mlp_fp8.hpp"
 #include "mlp_train.hpp"
 
 using namespace dlrm;
@@ -79,6 +80,15 @@ struct dlrm_mlp_bf16 {
     void* packed = nullptr;
     int64_t packed_bytes = 0;
     bool is_packed = false;  // dlrm_mlp_bf16_pack has run
+};
+
+// A Dense chain for the fused MXFP8 inference: the widths and the packed codes, scales and biases (mlp_fp8_plan.hpp), owned
+struct dlrm_mlp_fp8 {
+    dlrm_ctx* ctx = nullptr;
+    std::vector<int> sizes;  // layers + 1
+    void* packed = nullptr;
+    int64_t packed_bytes = 0;
+    bool is_packed = false;  // dlrm_mlp_fp8_pack has run
 };
 
 // A Dense chain for bf16 training: the widths and the layout of its max_batch (mlp_train_plan.hpp); no memory
@@ -1065,6 +1075,91 @@ int dlrm_mlp_bf16_infer(dlrm_ctx* ctx, const dlrm_mlp_bf16* mlp, int batch, cons
     CHECK_ARG(batch == 0 || (x && out), "dlrm_mlp_bf16_infer: null buffer");
     if (!mlp->is_packed) return ctx_fail(ctx, DLRM_E_STATE, "dlrm_mlp_bf16_infer: dlrm_mlp_bf16_pack has not run");
     return launch_mlp_bf16_chain(ctx, p, mlp->packed, batch, x, x_dtype, x_ld, out, out_dtype, out_ld, last_relu != 0);
+}
+
+// ------------------------------------------------------------- fused MXFP8 MLP inference
+// (DLRM_MLP_FP8_MT = 16 / 32 / 64: the comparison knob that takes the plan's tile height out of its rule's hands)
+static int mlp_fp8_force_mt() {
+    static const int mt = env_int("DLRM_MLP_FP8_MT", 0);
+    return mt == 16 || mt == 32 || mt == 64 ? mt : 0;
+}
+
+int dlrm_mlp_fp8_plan(int layers, const int* sizes, int batch, int x_dtype, int out_dtype, int* mt, int* grid,
+                      int64_t* lds_bytes, int64_t* packed_bytes, int* kp, int* np, int64_t* offsets) {
+    MlpFp8Plan p;
+    const int rc = plan_mlp_fp8(layers, sizes, batch, x_dtype, out_dtype, mlp_fp8_force_mt(), &p);
+    if (rc != DLRM_OK) return rc;
+    if (mt) *mt = p.MT;
+    if (grid) *grid = p.grid;
+    if (lds_bytes) *lds_bytes = p.lds_bytes;
+    if (packed_bytes) *packed_bytes = p.packed_bytes;
+    for (int l = 0; l < layers; ++l) {
+        if (kp) kp[l] = p.Kp[l];
+        if (np) np[l] = p.Np[l];
+        if (offsets) offsets[3 * l] = p.w_off[l], offsets[3 * l + 1] = p.s_off[l], offsets[3 * l + 2] = p.b_off[l];
+    }
+    return DLRM_OK;
+}
+
+int dlrm_mlp_fp8_create(dlrm_ctx* ctx, int layers, const int* sizes, dlrm_mlp_fp8** out) {
+    CHECK_ARG(ctx && sizes && out, "dlrm_mlp_fp8_create: null argument");
+    *out = nullptr;
+    MlpFp8Plan p;
+    int rc = plan_mlp_fp8(layers, sizes, 0, DLRM_F32, DLRM_F32, 0, &p);
+    if (rc != DLRM_OK)
+        return ctx_fail(ctx, rc, "dlrm_mlp_fp8_create: %d layers: 1 .. %d of widths 1 .. %d have a kernel", layers,
+                        kFp8MaxLayers, kFp8MaxWidth);
+    dlrm_mlp_fp8* m = new (std::nothrow) dlrm_mlp_fp8();
+    if (!m) return DLRM_E_NOMEM;
+    m->ctx = ctx;
+    m->sizes.assign(sizes, sizes + layers + 1);
+    m->packed_bytes = p.packed_bytes;
+    rc = hip_set(ctx);
+    if (rc == DLRM_OK) rc = mlp_fp8_prepare(ctx);
+    if (rc == DLRM_OK) rc = ctx_hip(ctx, hipMalloc(&m->packed, (size_t)p.packed_bytes), "hipMalloc(mlp_fp8 packed)");
+    if (rc != DLRM_OK) {
+        delete m;
+        return rc;
+    }
+    *out = m;
+    return DLRM_OK;
+}
+
+int dlrm_mlp_fp8_destroy(dlrm_mlp_fp8* mlp) {
+    if (!mlp) return DLRM_OK;
+    if (mlp->packed) (void)hipFree(mlp->packed);
+    delete mlp;
+    return DLRM_OK;
+}
+
+int dlrm_mlp_fp8_pack(dlrm_ctx* ctx, dlrm_mlp_fp8* mlp, const float* const* W, const int64_t* w_ld,
+                      const float* const* b) {
+    CHECK_ARG(ctx && mlp && W && w_ld && b, "dlrm_mlp_fp8_pack: null argument");
+    const int layers = (int)mlp->sizes.size() - 1;
+    for (int l = 0; l < layers; ++l) {
+        CHECK_ARG(W[l] && b[l], "dlrm_mlp_fp8_pack: layer %d has no weights or no bias", l);
+        CHECK_ARG(w_ld[l] >= mlp->sizes[l], "dlrm_mlp_fp8_pack: layer %d: w_ld %lld < its %d inputs", l,
+                  (long long)w_ld[l], mlp->sizes[l]);
+    }
+    MlpFp8Plan p;
+    int rc = plan_mlp_fp8(layers, mlp->sizes.data(), 0, DLRM_F32, DLRM_F32, 0, &p);
+    if (rc == DLRM_OK) rc = launch_mlp_fp8_pack(ctx, p, mlp->packed, W, w_ld, b);
+    if (rc == DLRM_OK) mlp->is_packed = true;
+    return rc;
+}
+
+int dlrm_mlp_fp8_infer(dlrm_ctx* ctx, const dlrm_mlp_fp8* mlp, int batch, const void* x, int x_dtype, int64_t x_ld,
+                       void* out, int out_dtype, int64_t out_ld, int last_relu) {
+    CHECK_ARG(ctx && mlp, "dlrm_mlp_fp8_infer: null ctx/mlp");
+    const int layers = (int)mlp->sizes.size() - 1;
+    MlpFp8Plan p;
+    const int rc = plan_mlp_fp8(layers, mlp->sizes.data(), batch, x_dtype, out_dtype, mlp_fp8_force_mt(), &p);
+    if (rc != DLRM_OK) return ctx_fail(ctx, rc, "dlrm_mlp_fp8_infer: batch=%d x_dtype=%d out_dtype=%d", batch, x_dtype, out_dtype);
+    CHECK_ARG(x_ld >= mlp->sizes[0] && out_ld >= mlp->sizes[layers], "dlrm_mlp_fp8_infer: x_ld %lld / out_ld %lld too small",
+              (long long)x_ld, (long long)out_ld);
+    CHECK_ARG(batch == 0 || (x && out), "dlrm_mlp_fp8_infer: null buffer");
+    if (!mlp->is_packed) return ctx_fail(ctx, DLRM_E_STATE, "dlrm_mlp_fp8_infer: dlrm_mlp_fp8_pack has not run");
+    return launch_mlp_fp8_chain(ctx, p, mlp->packed, batch, x, x_dtype, x_ld, out, out_dtype, out_ld, last_relu != 0);
 }
 
 // ------------------------------------------------------------------- bf16 MLP training

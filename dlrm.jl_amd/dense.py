@@ -64,6 +64,7 @@ class DenseMLP:
         self._context = None
         self._bf16 = None  # the packed bf16 chain (bf16_chain)
         self._train16 = None  # the bf16 training state (train_bf16)
+        self._fp8 = None  # the packed MXFP8 chain (fp8_chain)
 
     def flatten(self):
         """Re-homes every weight/bias AND its gradient as views of two flat fp32 buffers with the
@@ -127,6 +128,14 @@ class DenseMLP:
             self._bf16 = Bf16MLP(self)
         return self._bf16
 
+    def fp8_chain(self):
+        """The MLP's packed MXFP8 form (`mlp_fp8.Fp8MLP`), built and packed on first use; `.repack()` it after the
+        weights change."""
+        if self._fp8 is None:
+            from .mlp_fp8 import Fp8MLP
+            self._fp8 = Fp8MLP(self)
+        return self._fp8
+
     def train_bf16(self, max_batch):
         """The MLP's mixed-precision training state (`mlp_train_bf16.Bf16TrainMLP`): bf16 operands of these fp32
         masters, forward / dgrad / wgrad on the bf16 MFMA kernels, gW and gb written here.  Built on first use (a
@@ -136,13 +145,16 @@ class DenseMLP:
             self._train16 = Bf16TrainMLP(self, max_batch)
         return self._train16
 
-    def infer(self, x, *, logits=False, bf16=False, out_dtype=None):
+    def infer(self, x, *, logits=False, bf16=False, out_dtype=None, fp8=False):
         """`forward` without keeping anything: the activations of the last training forward (what its
         backward reads) stay as they are.  bf16: the whole chain in one launch on bf16 operands
         (`bf16_chain().infer`, x float32 or bfloat16, the result of `out_dtype`, default float32), from the
-        weights as last packed; a chain without that kernel raises."""
-        if bf16:
-            y = self.bf16_chain().infer(x, out_dtype=out_dtype)
+        weights as last packed; a chain without that kernel raises.  fp8: the same on MXFP8 operands
+        (`fp8_chain().infer`)."""
+        if bf16 and fp8:
+            raise ValueError("infer: bf16 or fp8, not both")
+        if bf16 or fp8:
+            y = (self.fp8_chain() if fp8 else self.bf16_chain()).infer(x, out_dtype=out_dtype)
             return torch.sigmoid(y) if self.sigmoid_last and not logits else y
         n = len(self.W)
         for i in range(n):
@@ -304,8 +316,15 @@ class DLRMModel:
                                         index_base=self.hot.index_base, pad_to=self._pad_to))
         return self._q4[1]
 
-    def repack(self):
-        """Packs both MLPs' current weights for `predict(..., mlp="bf16")` (two launches): after training steps."""
+    def repack(self, mlp="bf16"):
+        """Packs both MLPs' current weights for `predict(..., mlp="bf16")` (two launches): after training steps.
+        mlp="fp8": the MXFP8 chains of `predict(..., mlp="fp8")` instead."""
+        if mlp not in ("bf16", "fp8"):
+            raise ValueError(f'repack: mlp is "bf16" or "fp8", not {mlp!r}')
+        if mlp == "fp8":
+            self.bottom.fp8_chain().repack()
+            self.top.fp8_chain().repack()
+            return
         self.bottom.bf16_chain().repack()
         self.top.bf16_chain().repack()
 
@@ -318,20 +337,22 @@ class DLRMModel:
         mlp="bf16": each MLP is one fused bf16 launch (`DenseMLP.infer(bf16=True)`) on the weights as last packed
         (`repack()`): the bottom chain writes x in the tables' dtype, the top chain reads the hot path's output in
         that dtype and writes the fp32 logits, so no conversion is launched.  Composes with q8.
-        q4: a `Quantized4TableSet` (`quantize(bits=4)`), scored by `Q4Inference.infer`; as q8, and not with it."""
-        if mlp not in (None, "fp32", "bf16"):
-            raise ValueError(f'mlp is "fp32" or "bf16", not {mlp!r}')
+        q4: a `Quantized4TableSet` (`quantize(bits=4)`), scored by `Q4Inference.infer`; as q8, and not with it.
+        mlp="fp8": as "bf16" with each MLP one fused MXFP8 launch (`DenseMLP.infer(fp8=True)`, `repack(mlp="fp8")`)."""
+        if mlp not in (None, "fp32", "bf16", "fp8"):
+            raise ValueError(f'mlp is "fp32", "bf16" or "fp8", not {mlp!r}')
         if q8 is not None and q4 is not None:
             raise ValueError("predict: q8 or q4, not both")
         if not isinstance(sparse, PackedIndices):
             sparse = PackedIndices(sparse, device=self.tables.device)
-        if mlp == "bf16":
-            x = self.bottom.infer(dense, bf16=True, out_dtype=self.tdtype)
+        if mlp in ("bf16", "fp8"):
+            kind = {mlp: True}  # DenseMLP.infer's keyword
+            x = self.bottom.infer(dense, out_dtype=self.tdtype, **kind)
             if q4 is not None:
                 out = self._q4_engine(q4).infer(x, sparse)
             else:
                 out = self.hot.infer(x, sparse) if q8 is None else self._q8_engine(q8).infer(x, sparse)
-            return self.top.infer(out, logits=True, bf16=True)
+            return self.top.infer(out, logits=True, **kind)
         x = self.bottom.infer(dense)
         if q4 is not None:
             out = self._q4_engine(q4).infer(x.to(self.tdtype), sparse)
@@ -348,13 +369,14 @@ class DLRMModel:
         (correct / total) to `record` and returns `Evaluator.result()`: dict(total, correct, accuracy, logloss,
         auc, positives, negatives).  evaluator: an `Evaluator` to use (reset first; its state holds this pass
         afterwards); probs: a list that receives every batch's probabilities (a device tensor each); q8: score
-        the quantized tables (`predict`'s q8; q4: its q4, not both); mlp: `predict`'s mlp ("bf16": the MLPs are packed once, here)."""
+        the quantized tables (`predict`'s q8; q4: its q4, not both); mlp: `predict`'s mlp ("bf16", "fp8": the MLPs are
+        packed once, here)."""
         if q8 is not None and q4 is not None:
             raise ValueError("test: q8 or q4, not both")
         dev = self.tables.device
         ev = Evaluator(dev) if evaluator is None else evaluator.reset()
-        if mlp == "bf16":
-            self.repack()
+        if mlp in ("bf16", "fp8"):
+            self.repack(mlp)
         for labels, dense, sparse in data:
             z = self.predict(dense, sparse, q8=q8, mlp=mlp, q4=q4)
             check_labels(labels, z)

@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DLRM_HIP_ABI_VERSION 7
+#define DLRM_HIP_ABI_VERSION 8
 
 typedef enum {
     DLRM_OK = 0,
@@ -983,6 +983,42 @@ int dlrm_mlp_bf16_pack(dlrm_ctx* ctx, dlrm_mlp_bf16* mlp, const float* const* W,
                        const float* const* b);
 int dlrm_mlp_bf16_infer(dlrm_ctx* ctx, const dlrm_mlp_bf16* mlp, int batch, const void* x, int x_dtype,
                         int64_t x_ld, void* out, int out_dtype, int64_t out_ld, int last_relu);
+
+/* ---- fused MXFP8 MLP inference: a Dense chain on the block-scaled fp8 MFMA -----------------
+ * The chain of dlrm_mlp_bf16_* in OCP MXFP8: e4m3 codes (finite only, largest value 448) with one shared E8M0
+ * scale per 32 consecutive k of a row -- per (output feature, k-block) for W_l, per (sample, k-block) for the
+ * activations.  A block v[0..31] with m = max |v| gets X = clamp(floor(log2 m) - 8, -127, 127), the byte
+ * X + 127 (0 for a zero block) and the codes RNE_e4m3(v 2^-X) saturated to +-448.  A layer is
+ * z[m][n] = sum over blocks of 2^(Xa + Xw) * sum_k a8 w8 + b[n] with fp32 accumulation
+ * (v_mfma_scale_f32_16x16x128_f8f6f4, the scales applied by the instruction) and the fp32 bias; relu on
+ * every layer but the last, whose activation is relu (last_relu != 0) or the identity; every hidden
+ * activation is quantised once from the fp32 relu(z) and kept in LDS; the input (fp32 or bf16) is quantised
+ * on load; the last layer's fp32 value is stored as it is or rounded once to bf16.  Scoring only.
+ * plan:    pure host, no device call.  mt (16, 32 or 64 batch rows per workgroup of 256 threads), the grid
+ *          ceil(batch / mt), the dynamic LDS bytes 2 * mt * (wmax + 16 + wmax / 32) with wmax the largest
+ *          kp[l], the bytes of the packed buffer, per layer kp[l] = ceil128(sizes[l]) and
+ *          np[l] = ceil16(sizes[l+1]), and offsets[3 l .. 3 l + 2], the byte offsets of layer l's codes, scale
+ *          bytes and bias in the packed buffer, each a multiple of 64 (kp, np: `layers` entries, offsets:
+ *          3 * layers, or NULL).  DLRM_E_UNSUPPORTED for more than 8 layers or a width whose ceil16 exceeds
+ *          1024; DLRM_E_ARG for layers <= 0, a width <= 0, a negative batch or a dtype that is neither DLRM_F32
+ *          nor DLRM_BF16.
+ * create:  allocates the packed buffer, owned by the handle: layer l's codes [np/16][kp/128][64 lanes][32 B],
+ *          lane (c = lane % 16, q = lane / 16) of block (nb, kb) holding W[16 nb + c][128 kb + 32 q .. + 31],
+ *          zero where padded; its scale bytes [np/16][kp/128][64 lanes], the lane's row and 32 elements; then
+ *          the fp32 biases [np], zero-padded.
+ * pack:    one launch quantises the fp32 device arrays W[l] (leading dimension w_ld[l] >= sizes[l]) and copies
+ *          b[l]; call it again after the weights change.  W, w_ld, b: host arrays of `layers` entries.
+ * infer:   one launch: x is [batch][x_ld] of x_dtype, out [batch][out_ld] of out_dtype; DLRM_E_STATE before
+ *          the first pack.  pack and infer allocate nothing and do not synchronise (hipGraph-capturable). */
+typedef struct dlrm_mlp_fp8 dlrm_mlp_fp8;
+int dlrm_mlp_fp8_plan(int layers, const int* sizes, int batch, int x_dtype, int out_dtype, int* mt, int* grid,
+                      int64_t* lds_bytes, int64_t* packed_bytes, int* kp, int* np, int64_t* offsets);
+int dlrm_mlp_fp8_create(dlrm_ctx* ctx, int layers, const int* sizes, dlrm_mlp_fp8** out);
+int dlrm_mlp_fp8_destroy(dlrm_mlp_fp8* mlp);
+int dlrm_mlp_fp8_pack(dlrm_ctx* ctx, dlrm_mlp_fp8* mlp, const float* const* W, const int64_t* w_ld,
+                      const float* const* b);
+int dlrm_mlp_fp8_infer(dlrm_ctx* ctx, const dlrm_mlp_fp8* mlp, int batch, const void* x, int x_dtype,
+                       int64_t x_ld, void* out, int out_dtype, int64_t out_ld, int last_relu);
 
 /* ---- bf16 MLP training: forward, dgrad and wgrad of a Dense chain on bf16 MFMA ------------
  * Mixed precision: fp32 master weights W_l [N][K] and biases, bf16 operands, fp32 accumulation

@@ -4,15 +4,16 @@
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_mlp_bf16.py --trace     (kernel times, a run of its own)
 
 The Kaggle model (bottom 13-512-256-D, top W-1024-1024-512-256-1, D = 128, 26 tables), synthetic inputs as
-tools/bench_eval.py.  Per batch size, `predict` three ways, 8 batches per hipGraph replay:
+tools/bench_eval.py.  Per batch size, `predict` four ways, 8 batches per hipGraph replay:
 
     fp32        the fp32 MLPs on hipBLASLt (predict as it was)
     fused       predict(mlp="bf16"): one launch per MLP (csrc/mlp_bf16.hip)
+    fused_fp8   predict(mlp="fp8"): one MXFP8 launch per MLP (csrc/mlp_fp8.hip)
     torch_bf16  the yardstick: per-layer torch bf16 `_addmm_activation` on bf16 copies of the weights
 
-The three alternate window by window in one process; each figure is the median and the min .. max of five windows
-of `reps` replays.  The tile height is the plan's (printed as mt); DLRM_MLP_MT=16|32 in the environment overrides it
-for the comparison of the two.  Prints one JSON line per batch size.  --trace: no timing, 20 eager calls of each
+The four alternate window by window in one process; each figure is the median and the min .. max of five windows
+of `reps` replays.  The tile height is the plan's (printed as mt); DLRM_MLP_MT=16|32 (bf16) and
+DLRM_MLP_FP8_MT=16|32|64 (fp8) in the environment override it for the comparison of the tiles.  Prints one JSON line per batch size.  --trace: no timing, 20 eager calls of each
 variant at the first batch size, for the profiler.
 """
 import argparse
@@ -85,11 +86,14 @@ def main():
         def fused(k):
             return model.predict(dense[k], packs[k], mlp="bf16")
 
+        def fused_fp8(k):
+            return model.predict(dense[k], packs[k], mlp="fp8")
+
         def torch_bf16(k):
             x = bot16(dense[k].to(torch.bfloat16))
             return top16(model.hot.infer(x.to(tdtype), packs[k]).to(torch.bfloat16)).float()
 
-        variants = (("fp32", fp32), ("fused", fused), ("torch_bf16", torch_bf16))
+        variants = (("fp32", fp32), ("fused", fused), ("fused_fp8", fused_fp8), ("torch_bf16", torch_bf16))
         if a.trace:
             for _, fn in variants:
                 for i in range(20):
@@ -117,9 +121,12 @@ def main():
                 windows[name].append((time.perf_counter() - t0) * 1e6 / (a.reps * NB))
         plan = [pkg.mlp_bf16_plan(s, B, pkg._lib.F32 if i == 0 or a.dtype == "f32" else pkg._lib.BF16) for i, s in
                 enumerate((bsz, tsz))]
+        plan8 = [pkg.mlp_fp8_plan(s, B, pkg._lib.F32 if i == 0 or a.dtype == "f32" else pkg._lib.BF16) for i, s in
+                 enumerate((bsz, tsz))]
         print(json.dumps({
             "metric": "DLRMModel.predict per batch, 1 MI355X", "unit": "us", "batch": B, "tables_dtype": a.dtype,
             "mt": [p["mt"] for p in plan], "grid": [p["grid"] for p in plan], "lds_bytes": [p["lds_bytes"] for p in plan],
+            "mt_fp8": [p["mt"] for p in plan8], "lds_bytes_fp8": [p["lds_bytes"] for p in plan8],
             **{name: {"median": round(statistics.median(w), 2), "min": round(min(w), 2), "max": round(max(w), 2)}
                for name, w in windows.items()},
             "max_abs_logit_difference_from_fp32": {k: round(v, 5) for k, v in diff.items()},
