@@ -24,6 +24,7 @@
 #include "apply.hpp"
 #include "q8.hpp"
 #include "q4.hpp"
+#include "bags.hpp"
 #include "mlp_bf16.hpp"
 #include "mlp_fp8.hpp"
 #include "mlp_train.hpp"
@@ -749,6 +750,22 @@ int dlrm_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_tables* tb, const void* i
                           index_base, batch, lookups, ys, ys_ld, d, tb->h_desc.data());
     if (rc) return rc;
     return launch_interact_fwd(ctx, tb->dtype, d, F, batch, x, x_ld, ys, ys_ld, out, out_ld, padding);
+}
+
+// The pooled forward of bags.hip: dlrm_lookup_interact_fwd's checks, one launch or DLRM_E_UNSUPPORTED (bags_plan.hpp)
+int dlrm_bags_interact_fwd(dlrm_ctx* ctx, const dlrm_tables* tb, const void* indices, int itype, int64_t table_stride,
+                           int index_base, int batch, int lookups, const void* x, int64_t x_ld, void* ys,
+                           int64_t ys_ld, void* out, int64_t out_ld, int padding) {
+    CHECK_ARG(ctx && tb, "dlrm_bags_interact_fwd: null ctx/tables");
+    int rc = check_indices(ctx, tb, indices, itype, table_stride, batch, lookups);
+    if (rc) return rc;
+    const int d = tb->D, F = tb->T + 1;
+    const int64_t P = (int64_t)F * (F - 1) / 2;
+    CHECK_ARG(padding >= 0 && x_ld >= d && (!ys || ys_ld >= (int64_t)F * d) && out_ld >= d + P + padding,
+              "dlrm_bags_interact_fwd: leading dimensions too small");
+    CHECK_ARG(batch == 0 || (x && out), "dlrm_bags_interact_fwd: null buffer");
+    return launch_bags_interact_fwd(ctx, tb->d_desc, tb->aligned16, tb->T, tb->dtype, indices, itype, table_stride,
+                                    index_base, lookups, d, batch, x, x_ld, ys, ys_ld, out, out_ld, padding);
 }
 
 // ------------------------------------------------------------- int8 row-quantized tables

@@ -62,6 +62,15 @@ they do for Descent.  The backward and the apply of a step read the same value o
 advances by one after the apply; every row ends up bit for bit what the operator path gives from the same step.
 Opt-in, a keyword of its own: without it the rule keeps the operator path.
 
+`bags=True`: in `infer`, pooled bags (lookups > 1) and 32 .. 95 tables take dlrm_bags_interact_fwd, one launch with a
+workgroup per sample, with the bits of dlrm_maplookup + dlrm_interact_fwd (pooled-64x256-l10:
+624 -> 204 us on fp32 tables, 219 -> 109 us on bf16).  `bags_forward=True` (with `bags=True`) also sends the operator
+route's training forward with ys kept (not the step kernels) there; it is off by default because that forward, which
+writes ys as well, measured slower than the two launches it replaces (229 vs 207 us fp32, 122 vs 99 us bf16).
+`infer_route` / `fwd_route` say what the last call took: "bags", "fused" (dlrm_lookup_interact_fwd, as without the
+keyword) or "two-launch"; set to "two-launch" they force dlrm_maplookup + dlrm_interact_fwd.  Opt-in: without the
+keywords every launch is what it was.
+
 `infer(x, idx)` is the inference forward (evaluation, `DLRMModel.predict`): lookup + interaction into `out` with no
 indexer build and no change to what a training step left or a pipelined one prepared.
 """
@@ -79,7 +88,7 @@ class HotPath:
     def __init__(self, tables, batch, lookups=1, *, lr=0.1, index_base=0, deterministic=True,
                  overlap_indexer=None, pad_to=1, fused=True, materialize_ys=None, pipeline=False, chunk=None,
                  parts=None, opt=None, fused_step=False, adagrad_step=False, stochastic_step=False,
-                 sr_adagrad_step=False):
+                 sr_adagrad_step=False, bags=False, bags_forward=False):
         if opt is not None and not isinstance(opt, _StatefulOpt):
             raise TypeError("HotPath: opt is an ADAGrad, RowwiseADAGrad, SplitDescent or StochasticDescent "
                             "(None: Descent(lr))")
@@ -113,6 +122,11 @@ class HotPath:
         self.index_base = int(index_base)
         self.deterministic = deterministic
         self.fused = fused
+        self.bags = bool(bags)
+        if bags_forward and not bags:
+            raise ValueError("HotPath: bags_forward=True is the training forward of bags=True")
+        self.bags_forward = bool(bags_forward)
+        self.infer_route = self.fwd_route = None  # what the last infer / forward took; "two-launch" forces it
         _, self.width, self.padding = interaction_sizes(self.d, self.F, pad_to)
         dev, dt = self.ts.device, self.ts.dtype
         can_skip = fused and self.L == 1
@@ -217,6 +231,20 @@ class HotPath:
                                                       self.index_base, self.B, self.L, ptr(x), x.stride(0), ys,
                                                       ys_ld, ptr(self.out), self.out.stride(0), self.padding))
         self._fwd_x, self._fwd_idx = x, idx
+
+    def bags_interact_fwd(self, x, idx, ys=None, out=None):
+        """The raw dlrm_bags_interact_fwd call's status: _lib.OK (launched) or _lib.E_UNSUPPORTED (nothing launched)."""
+        out = self.out if out is None else out
+        rc = self.lib.dlrm_bags_interact_fwd(self.ctx.bind(), self.ts.handle, ptr(idx.data), idx.itype, idx.stride,
+                                             self.index_base, self.B, self.L, ptr(x), x.stride(0),
+                                             None if ys is None else ptr(ys), 0 if ys is None else ys.stride(0),
+                                             ptr(out), out.stride(0), self.padding)
+        if rc != _lib.E_UNSUPPORTED:
+            self._check(rc)
+        return rc
+
+    # the shapes that bags=True sends to dlrm_bags_interact_fwd first: the one-hot kernel keeps its own (<= 31 tables)
+    _bags_shape = property(lambda self: self.bags and (self.L > 1 or self.T > 31))
 
     def build_indexer(self, idx):
         h = self.ctx.bind()
@@ -419,8 +447,14 @@ class HotPath:
                 self.build_indexer(idx)
                 self._indexer_done = torch.cuda.Event()
                 self._indexer_done.record(self._side)
-        if self.fused:
+        if self.fused and not (self.fwd_route == "two-launch" and self.materialize_ys):
+            if (self._bags_shape and self.bags_forward and self.materialize_ys and
+                    self.bags_interact_fwd(x, idx, self.ys) == _lib.OK):
+                self._fwd_x, self._fwd_idx = x, idx
+                self.fwd_route = "bags"
+                return self.out
             self.lookup_interact_fwd(x, idx)
+            self.fwd_route = "fused"
         else:
             self.lookup(idx)
             self.interact_fwd(x)
@@ -433,19 +467,26 @@ class HotPath:
         kernels it rebuilds the current indexer).  One launch (dlrm_lookup_interact_fwd without ys); a shape
         without the fused kernel takes dlrm_maplookup + dlrm_interact_fwd through a ys of its own."""
         h = self.ctx.bind()
-        if self._infer_ys is None:
+        forced = self.infer_route == "two-launch"
+        if self._bags_shape and not forced and self.bags_interact_fwd(x, idx) == _lib.OK:
+            self.infer_route = "bags"
+            return self.out
+        if self._infer_ys is None and not forced:
             rc = self.lib.dlrm_lookup_interact_fwd(h, self.ts.handle, ptr(idx.data), idx.itype, idx.stride,
                                                    self.index_base, self.B, self.L, ptr(x), x.stride(0), None, 0,
                                                    ptr(self.out), self.out.stride(0), self.padding)
             if rc != _lib.E_UNSUPPORTED:
                 self._check(rc)
+                self.infer_route = "fused"
                 return self.out
+        if self._infer_ys is None:
             self._infer_ys = torch.empty((self.B, self.F * self.D), dtype=self.ts.dtype, device=self.ts.device)
         ys = self._infer_ys
         self._check(self.lib.dlrm_maplookup(h, self.ts.handle, ptr(idx.data), idx.itype, idx.stride, self.index_base,
                                             self.B, self.L, ptr(ys), ys.stride(0), self.d))
         self._check(self.lib.dlrm_interact_fwd(h, self.dcode, self.d, self.F, self.B, ptr(x), x.stride(0), ptr(ys),
                                                ys.stride(0), ptr(self.out), self.out.stride(0), self.padding))
+        self.infer_route = "two-launch"
         return self.out
 
     def backward(self, idx, dout):

@@ -255,6 +255,33 @@ function _maplookup(tables::AbstractVector{<:HipEmbedding{Static{D},T}}, sparse,
     return ys, idx
 end
 
+"""
+    bags_interact_fwd!(out, dot, x, tables, sparse; ys = nothing)
+
+`dlrm_bags_interact_fwd`: lookup (bags of any size, 1 .. 95 tables) + interaction in one launch, a workgroup per
+sample, into `out` and, where given, `ys` -- the bits of `dlrm_maplookup` + `dlrm_interact_fwd`.  Returns `false`,
+with nothing launched, where the shape has no such kernel (DLRM_E_UNSUPPORTED); the caller then takes those two.
+"""
+function bags_interact_fwd!(out::DeviceMatrix{T}, dot::HipDotInteraction, x::DeviceMatrix{T},
+                            tables::AbstractVector{<:HipEmbedding{Static{D},T}}, sparse;
+                            ys::Union{Nothing,DeviceMatrix{T}} = nothing) where {D,T}
+    ctx = first(tables).data.ctx
+    idx = sparse isa PackedIndices ? sparse : pack(ctx, sparse)
+    poll_bounds!(tables)
+    flush!(tables)
+    d, B = size(x)
+    _, padding = interaction_sizes(d, length(tables) + 1, dot.pad_to)
+    rc = ccall((:dlrm_bags_interact_fwd, libdlrm), Cint,
+               (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cint, Cint, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64,
+                Ptr{Cvoid}, Int64, Cint),
+               ctx.ptr, tableset(tables), idx.data.ptr, DLRM_I32, idx.batch * idx.lookups, 1, B, idx.lookups,
+               x.ptr, d, ys === nothing ? C_NULL : ys.ptr, ys === nothing ? 0 : size(ys, 1), out.ptr, size(out, 1),
+               padding)
+    rc == Cint(-4) && return false  # DLRM_E_UNSUPPORTED
+    check(ctx, rc)
+    return true
+end
+
 EmbeddingTables.maplookup(s::PreallocationStrategy, tables::AbstractVector{<:HipEmbedding}, sparse) =
     first(tables).data.ctx.fused ? _fused_maplookup(tables, sparse, prealloc_rows(s)) :
                                    first(_maplookup(tables, sparse, prealloc_rows(s)))

@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DLRM_HIP_ABI_VERSION 8
+#define DLRM_HIP_ABI_VERSION 9
 
 typedef enum {
     DLRM_OK = 0,
@@ -178,6 +178,20 @@ int dlrm_lookup_interact_fwd(dlrm_ctx* ctx, const dlrm_tables* tables,
                              int batch, int lookups,
                              const void* x, int64_t x_ld, void* ys, int64_t ys_ld,
                              void* out, int64_t out_ld, int padding);
+
+/* The same forward for pooled bags and up to 95 tables, in ONE launch: dlrm_lookup_interact_fwd's argument list and
+ * argument checks, and its contract -- out and ys (if given; ys may be NULL) receive exactly what
+ * dlrm_maplookup(out_offset = d) + dlrm_interact_fwd write (each bag summed in fp32 in lookup order and rounded once;
+ * the Gram in dlrm_interact_fwd's MFMA order).  A workgroup per sample pools the bags into an LDS operand tile and runs
+ * the Gram from it, the gather of one column block under the MFMAs of the block before.  Returns DLRM_E_UNSUPPORTED,
+ * with nothing launched, outside its domain, which is exactly: lookups >= 1; 1 <= num_tables <= 95; d % 4 == 0 (fp32)
+ * or d % 8 == 0 (bf16) and every table row 16-B aligned; x 16-B aligned with x_ld % 4 == 0 (fp32) or x_ld % 8 == 0
+ * (bf16); ys NULL, or aligned as x is.  out and out_ld need no alignment.  batch == 0 is DLRM_OK. */
+int dlrm_bags_interact_fwd(dlrm_ctx* ctx, const dlrm_tables* tables,
+                           const void* indices, int itype, int64_t table_stride, int index_base,
+                           int batch, int lookups,
+                           const void* x, int64_t x_ld, void* ys, int64_t ys_ld,
+                           void* out, int64_t out_ld, int padding);
 
 /* ---- Implementation 2 of the interaction, as separate operators --------------------------
  * dot_interaction (src/model/interact.jl:503-517; the default of dlrm(), model.jl:180) composes

@@ -17,6 +17,11 @@ median (min - max) of the five windows, in us per batch:
     q4_two_launch_f32_us   the same, fp32 x / out
     q4_bags_f32_us      dlrm_q4_bags_interact_fwd, fp32 x / out (one launch)
     q4_bags_bf16_us     dlrm_q4_bags_interact_fwd, bf16 x / out (one launch)
+    infer_bags_f32_us   HotPath(bags=True).infer on the fp32 tables of infer_f32_us (dlrm_bags_interact_fwd, one launch)
+    infer_bags_bf16_us  the same on the bf16 tables of infer_bf16_us
+    fwd_f32_us          HotPath.forward, the operator route's training forward with ys kept, on the fp32 tables
+    fwd_bags_f32_us     the same with bags=True, bags_forward=True (dlrm_bags_interact_fwd with ys, one launch)
+    fwd_bf16_us, fwd_bags_bf16_us   the two on the bf16 tables
 
 A pooled workload (lookups > 1, e.g. pooled-64x256-l10) or one of more than 31 tables has no one-hot fused kernel:
 q4_f32_us, q4_bf16_us and q8_bf16_us are left out there, and the comparison that matters is q4_bags_* against
@@ -42,7 +47,13 @@ import dlrm_pkg  # noqa: E402
 
 NB = 8
 NAMES = ("infer_f32_us", "infer_bf16_us", "q8_bf16_us", "q4_f32_us", "q4_bf16_us", "q4_two_launch_us",
-         "q4_two_launch_f32_us", "q4_bags_f32_us", "q4_bags_bf16_us")
+         "q4_two_launch_f32_us", "q4_bags_f32_us", "q4_bags_bf16_us", "infer_bags_f32_us", "infer_bags_bf16_us",
+         "fwd_f32_us", "fwd_bags_f32_us", "fwd_bf16_us", "fwd_bags_bf16_us")
+HOT = {  # HotPath variants: name -> (table dtype, bags=, the training forward with ys kept instead of infer)
+    "infer_f32_us": (torch.float32, False, False), "infer_bf16_us": (torch.bfloat16, False, False),
+    "infer_bags_f32_us": (torch.float32, True, False), "infer_bags_bf16_us": (torch.bfloat16, True, False),
+    "fwd_f32_us": (torch.float32, False, True), "fwd_bags_f32_us": (torch.float32, True, True),
+    "fwd_bf16_us": (torch.bfloat16, False, True), "fwd_bags_bf16_us": (torch.bfloat16, True, True)}
 ONEHOT = ("q8_bf16_us", "q4_f32_us", "q4_bf16_us")  # the one-hot fused kernels: lookups == 1, at most 31 tables
 
 
@@ -75,6 +86,8 @@ def main():
     only = [n for n in a.only.split(",") if n] or list(NAMES)
     if L != 1 or T > 31:
         only = [n for n in only if n not in ONEHOT]
+    else:  # the bags forward and the kept ys are for pooled bags and more than 31 tables
+        only = [n for n in only if "bags" not in n and not n.startswith("fwd")]
     gen = torch.Generator(device=dev).manual_seed(51234)
     rng = np.random.default_rng(51234)
     if w.get("zipf"):
@@ -121,10 +134,15 @@ def main():
         return cls.from_arrays([p.rows[0] for p in parts], D)
 
     variants = {}  # name -> (graph, what keeps its memory alive)
-    for name, dt in (("infer_f32_us", torch.float32), ("infer_bf16_us", torch.bfloat16)):
+    sets = {}      # one table set per dtype, shared by the HotPath variants on it
+    for name, (dt, bags, fwd) in HOT.items():
         if name in only:
-            hp = pkg.HotPath(tables(dt), B, L, index_base=0)
-            variants[name] = (lambda k, hp=hp, dt=dt: hp.infer(xs[dt][k], packs[k]), hp)
+            if dt not in sets:
+                sets[dt] = tables(dt)
+            # (the training forward: ys kept, no side-stream indexer build inside the timed graph)
+            hp = pkg.HotPath(sets[dt], B, L, index_base=0, bags=bags, **({"materialize_ys": True, "overlap_indexer": False,
+                                                                         "deterministic": False, "bags_forward": bags} if fwd else {}))
+            variants[name] = (lambda k, call=hp.forward if fwd else hp.infer, dt=dt: call(xs[dt][k], packs[k]), hp)
     if "q8_bf16_us" in only:
         q8 = quantized(pkg.QuantizedTableSet)
         out["q8_bytes"] = q8.nbytes
@@ -145,11 +163,13 @@ def main():
     for name, (fn, eng) in variants.items():
         for k in range(NB):  # eager warm-up of every batch
             r = fn(k)
-            assert "bags" not in name or r == pkg._lib.OK, (name, r)  # (the raw call's status: launched)
+            assert "q4_bags" not in name or r == pkg._lib.OK, (name, r)  # (the raw call's status: launched)
         torch.cuda.synchronize()
         eng.check_bounds()
         if name.startswith("q") and "bags" not in name:
             assert eng.route == ("two-launch" if "two_launch" in name else "fused"), (name, eng.route)
+        if name in HOT and HOT[name][1]:
+            assert (eng.fwd_route if HOT[name][2] else eng.infer_route) == "bags", name
         graphs[name] = graph_of(fn)
         graphs[name].replay()
     torch.cuda.synchronize()
